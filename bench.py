@@ -7,7 +7,12 @@ timed region starts; outputs stay in HBM.  With N > 1 every rank processes its o
 (weak scaling, frames are independent units) and the per-frame result slabs are gathered to rank 0 over
 RCCL inside the timed region (BASELINE.json north_star; disable with --no-gather).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mono640|hd1080|stereo640] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload mono640|hd1080|stereo640] [--batch B] [--full] [--dump-outputs DIR]
+
+A plain run sets up, primes and warms up, times the K steps and prints the line.  Everything else the line can carry (the oracle
+check of the timed slab, the per-kernel event profile and roofline, the CPU baseline, the sustained-load window, the secondary
+workloads and call shapes, configs[4] and rank 0's kernels under the gather at N > 1) takes runs of its own and comes with --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64).
 
 `python bench.py --gpus N` works as typed: when no launcher has set RANK, the process — before it imports torch or touches the
 GPU in any way — starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD, relays rank 0's JSON line and
@@ -73,6 +78,24 @@ VALU_PEAK_GINSTR = 1024 * 2.4 / 4.0
 # ... and the ceiling as MEASURED (profiles/r03_valu_issue_rate.md): the half-rate class takes 4.14 true cycles per wave64 instruction, and k_fast's
 # waves run at 2.375 GHz in the benchmark's launch shape (tools/fast_clock.py, -DORBX_FAST_CLOCK build): 1024 x 2.375 / 4.14
 VALU_MEASURED_GINSTR = 1024 * 2.375 / 4.14
+DUMP_ROWS = 64              # --dump-outputs: frames (pairs) per array, a seeded sample; keeps the dump of every workload under DUMP_LIMIT
+DUMP_LIMIT = 64 << 20
+
+
+def sample_rows(n):
+    """the sorted row indices --dump-outputs keeps of an array with n rows: all of them up to DUMP_ROWS, else a sample seeded by n alone"""
+    return np.sort(np.random.default_rng(n).choice(n, min(n, DUMP_ROWS), replace=False))
+
+
+def dump_outputs(path, arrays):
+    """writes each array as path/<name>.npy: float64 stays float64, everything else (u8 / i32 / f32) becomes float32, exact for these values"""
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def _search_rounds():
@@ -152,7 +175,13 @@ def main():
                     "N > 1 control flow of this file (double-buffered slabs, the asynchronous gather, the waits before a slab is overwritten, "
                     "configs[4], the max-over-ranks clock, the per-rank check of what arrived) runs at world size 2 in the CPU test suite "
                     "(tests/test_bench_world2.py with tests/bench_stub.py).  The line it prints carries value = null")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need (see the module docstring); "
+                    "--no-verify / --no-cpu-baseline / --no-extras / --sustained-seconds trim it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "(rank 0) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if bool(args.extractor_factory) != (args.backend == "gloo"):
         raise SystemExit("--backend gloo and --extractor-factory go together (the HIP path runs under nccl = RCCL only)")
     if "RANK" not in os.environ and (args.gpus > 1 or args.spawn):
@@ -386,7 +415,7 @@ def main():
     # below the rate the same process holds for seconds (secondary.sustained: the chip's clock settles over the first ~100 ms of load).  A fixed number of
     # untimed steps (the same on every rank: the gather is a collective) brings the timed K steps into that steady state; `priming_steps` is in the line.
     unprimed = None
-    if prime_steps > 0 and not distributed and args.steps > 0:
+    if args.full and prime_steps > 0 and not distributed:
         # the protocol of rounds 1-4, kept beside the headline so that rounds stay comparable: W warm-up steps, K timed steps, no priming
         for _ in range(args.warmup):
             step()
@@ -413,6 +442,39 @@ def main():
     elapsed = time.perf_counter() - t0
     exposed["on"] = False
     kl_timed = (counter[0] - 1) % len(slabs)      # the slab the LAST TIMED step wrote (what `verified` checks)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step hands its caller, before any later step overwrites it: rank 0's slab (keypoint fields and descriptor
+        # bytes of a seeded sample of frames, rows past each frame's count zeroed; every frame's count and mono index) and the
+        # workload's further outputs, DUMP_ROWS sampled rows each
+        hs = slabs[kl_timed].cpu().numpy()
+        h_n = hs[off_n:off_n + 4 * B].view(np.int32)
+        pick = sample_rows(B)
+        kps = hs[off_k:off_d].view(X.KEYPOINT_DTYPE).reshape(B, cap)[pick]
+        live = np.arange(cap)[None, :] < h_n[pick, None]
+
+        def fields(kp):      # keypoint records -> float32 (..., 7): x, y, size, angle, response, octave, class_id; rows past the count zeroed
+            return np.stack([kp[f].astype(np.float32) for f in X.KEYPOINT_DTYPE.names], -1) * live[..., None]
+
+        outs = dict(n_keypoints=h_n, mono_index=hs[off_m:off_m + 4 * B].view(np.int32), sampled_frames=pick, keypoints=fields(kps),
+                    descriptors=hs[off_d:off_n].reshape(B, cap, 32)[pick] * live[..., None])
+        more = {}
+        if match:
+            more.update(stereo_u_right=d_u, stereo_depth=d_z, stereo_n_matched=d_nm)
+        if init_match or track:
+            more.update(kps_un=d_un, grid_off=d_goff, grid_idx=d_gidx, n_inside=d_nin)
+        if init_match:
+            more.update(init_matches12=d_m12, init_n_matches=d_nm12)
+        if track:
+            more.update(projection_matches=d_mt, projection_n_matches=d_nmt)
+        if bow:
+            more.update(bow_word_ids=d_wid, bow_word_weights=d_ww, bow_n_words=d_nw, bow_feat_nodes=d_fn, bow_feat_idx=d_fi, bow_n_feat=d_nfv)
+        if refkf:
+            more.update(bow_matches=d_mb, bow_n_matches=d_nmb)
+        for k, v in more.items():
+            outs[k] = v[torch.from_numpy(sample_rows(v.shape[0])).to(v.device)].cpu().numpy()
+        if "kps_un" in outs:      # keypoint records (int octave / class_id) held in a float tensor: decoded per field, as the slab's
+            outs["kps_un"] = fields(outs["kps_un"].view(X.KEYPOINT_DTYPE)[..., 0])
+        dump_outputs(args.dump_outputs, outs)
     multi = None
     if distributed:
         # every rank's own clock and exposed gather time in ONE all-reduce: slot r / world + r are written by rank r only, MAX collects them
@@ -440,7 +502,7 @@ def main():
     # ---- BASELINE.json configs[4] as a secondary figure of every N > 1 line: 64 frames per GPU per step (512 frames on 8 GPUs),
     #      result slabs gathered to rank 0; same step / fence / max-over-ranks rules as the main figure ----
     cfg5 = None
-    if distributed and (N > 1 or os.environ.get("ORBX_BENCH_CONFIGS4_AT_ANY_N")) and args.workload == "mono640" and not args.no_extras:      # (the env switch: the test reaches this code on a one-GPU box)
+    if args.full and distributed and (N > 1 or os.environ.get("ORBX_BENCH_CONFIGS4_AT_ANY_N")) and args.workload == "mono640" and not args.no_extras:      # (the env switch: the test reaches this code on a one-GPU box)
         B5 = min(64, B)
         if stub:
             e5 = ex
@@ -490,7 +552,7 @@ def main():
     #      gather rank 0 checks what ARRIVED: frames of every rank's gathered slab (it rebuilds that rank's inputs: stream_frames) ----
     verified = None
     bad = []
-    if rank == 0 and not args.no_verify and args.steps > 0:
+    if rank == 0 and args.full and not args.no_verify:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O      # the checker; never the product path
         kl = kl_timed
@@ -537,7 +599,7 @@ def main():
     # ---- rank 0's kernels WITH the gather running (N > 1 diagnostics): RCCL's receive kernels take CUs on rank 0 while its own k_fast wants
     #      every issue slot; the event profile of the same steps shows it as a number next to roofline.kernel_ms_per_step (no gather).
     #      Every rank runs the same steps (the gather is a collective); only rank 0 brackets its kernels with events. ----
-    if multi is not None and gather and not stub:
+    if multi is not None and gather and not stub and args.full:
         psteps_g = max(3, min(args.steps, 10))
         if rank == 0:
             ex.profile(True)
@@ -557,7 +619,8 @@ def main():
                                              "profile without a gather)" % psteps_g)
     elif multi is not None:
         multi["rank0_kernel_ms_per_step"] = None
-        multi["rank0_kernel_ms_note"] = "not measured: " + ("--extractor-factory rehearsal (no HIP kernels)" if stub else "gather disabled")
+        multi["rank0_kernel_ms_note"] = "not measured: " + ("--extractor-factory rehearsal (no HIP kernels)" if stub else "gather disabled" if not gather
+                                                            else "a --full run measures it")
 
     result = None
     if rank == 0 and stub:
@@ -643,13 +706,15 @@ def main():
                         path_traffic_bytes_per_frame=path_traffic,
                         kernel_ms_per_step={k: round(v, 4) for k, v in sorted(per_.items())}, valu_issue=valu_)
 
-        psteps = max(3, min(args.steps, 20))
-        per_step_ms, dominant, dom_avg_ms = event_profile(ex, profiled_step, psteps)
-        n_mean = float(n_host.mean())
-        b_alg = ex.algorithmic_bytes(rows, cols, int(round(n_mean)))   # P0 + 2*S + 60*n_out per frame
-        default_variant = variant == WORKLOADS[args.workload]["variant"]   # the PMC files were collected on the default variant
-        roofline = roofline_block(args.workload, B, per_step_ms, dominant, dom_avg_ms, b_alg, fps / N, default_variant)
-        valu = roofline["valu_issue"]
+        roofline = valu = None
+        if args.full:
+            psteps = max(3, min(args.steps, 20))
+            per_step_ms, dominant, dom_avg_ms = event_profile(ex, profiled_step, psteps)
+            n_mean = float(n_host.mean())
+            b_alg = ex.algorithmic_bytes(rows, cols, int(round(n_mean)))   # P0 + 2*S + 60*n_out per frame
+            default_variant = variant == WORKLOADS[args.workload]["variant"]   # the PMC files were collected on the default variant
+            roofline = roofline_block(args.workload, B, per_step_ms, dominant, dom_avg_ms, b_alg, fps / N, default_variant)
+            valu = roofline["valu_issue"]
 
         def cgroup_cpu_share():
             """CPUs the box's cgroup grants this job (a GPU box may show every core of the host - 256 - while the job gets 16 per GPU)"""
@@ -688,7 +753,7 @@ def main():
                                % (smp, variant_, cols_, rows_, nf_, th, sec_, n_single, sec1_))
 
         cpu = None
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O      # the checker, timed as the CPU baseline; never the product path
             # one frame per thread over ALL host cores.  A GPU box may show every core of the host (256) while its
@@ -718,7 +783,7 @@ def main():
         if unprimed is not None:
             extras["unprimed"] = unprimed
         value_basis = "the %d timed steps" % args.steps
-        if N == 1 and not args.no_extras and not distributed and args.sustained_seconds > 0:
+        if args.full and N == 1 and not args.no_extras and not distributed and args.sustained_seconds > 0:
             # ---- (0) the headline under SUSTAINED load: the same step looped for >= 5 s, the rate over the whole
             #      window and over its last second (GPU timestamps: an event every 32 steps), and the shader clock the chip ran at meanwhile
             #      (orbx_debug_clock_probe: a sleeping wave per CU stamps s_memtime against the 100-MHz s_memrealtime, every 256 steps, on
@@ -782,7 +847,7 @@ def main():
                 valu["peak_ginstr_s_at_measured_clock"] = round(1024 * clk / 4.0, 1)
                 valu["frac_at_measured_clock"] = round(valu["achieved_ginstr_s"] / (1024 * clk / 4.0), 4)
                 valu["frac_of_measured_ceiling_at_measured_clock"] = round(valu["achieved_ginstr_s"] / (1024 * clk / 4.14), 4)
-        if N == 1 and args.workload == "mono640" and not args.no_extras and not distributed:
+        if args.full and N == 1 and args.workload == "mono640" and not args.no_extras and not distributed:
             if not (args.no_verify and args.no_cpu_baseline):
                 sys.path.insert(0, os.path.join(ROOT, "tests"))
                 import oracle_lib as O      # the checker (hd1080 / stereo640: verified + cpu_baseline); never the product path

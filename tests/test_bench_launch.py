@@ -59,7 +59,7 @@ def test_spawn_path_end_to_end_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ORBX_BENCH_CONFIGS4_AT_ANY_N"] = "1"            # the N > 1 line's secondary figure (BASELINE.json configs[4]) at the world size this box has
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--spawn", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1
@@ -68,3 +68,33 @@ def test_spawn_path_end_to_end_on_one_gpu():
     assert j["verified"]["bit_exact"] is True and len(j["verified"]["frames"]) == 4
     c4 = j["secondary"]["configs4_64_per_gpu"]
     assert c4["frames_per_gpu_per_step"] == 64 and c4["fps"] > 0 and "gathered to rank 0" in c4["note"]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain one-GPU run: the line carries the timed figure and none of the --full legs; --dump-outputs writes the slab the last timed
+    step computed, bit for bit the oracle's keypoints and descriptors on the sampled frames."""
+    import numpy as np
+    import oracle_lib as O
+    from extractorb_amd import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "96",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert j["steps"] == 4 and j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "frames/s" and j["higher_is_better"] is True
+    assert j["verified"] is None and j["roofline"] is None and j["cpu_baseline"] is None and j["secondary"] is None
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("n_keypoints", "mono_index", "sampled_frames", "keypoints", "descriptors")}
+    assert all(v.dtype == np.float32 for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+    pick = got["sampled_frames"].astype(int)
+    assert len(pick) == 64 and len(set(pick.tolist())) == 64 and got["n_keypoints"].shape == (96,)
+    frames = synth.frames("noise", 0, 96, 480, 640)
+    o = O.Oracle(1000, 1.2, 8, 20, 7)
+    for i in (0, 31, 63):
+        f = pick[i]
+        mono, k, d = o.extract(frames[f], (0, 1000))
+        n = len(k)
+        assert got["n_keypoints"][f] == n and got["mono_index"][f] == mono
+        want = np.stack([k[name].astype(np.float32) for name in k.dtype.names], -1)
+        assert np.array_equal(got["keypoints"][i, :n], want) and np.array_equal(got["descriptors"][i, :n], d.astype(np.float32))
+        assert not got["keypoints"][i, n:].any() and not got["descriptors"][i, n:].any()

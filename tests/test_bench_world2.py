@@ -11,12 +11,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(extra_env=None, extra_args=()):
+def run(extra_env=None, extra_args=(), full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests")] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--extractor-factory", "bench_stub:make_extractor", "--batch", "3", "--steps", "3",
-                        "--warmup", "1", *extra_args], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", *(["--full"] if full else []), *extra_args], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     return r, (json.loads(lines[0]) if len(lines) == 1 else None)
 
@@ -53,6 +53,30 @@ def test_no_gather_leaves_results_on_their_ranks():
     assert r.returncode == 0, r.stderr[-4000:]
     assert j["verified"]["ranks_checked"] == [0] and j["verified"]["bit_exact"] is True
     assert j["multi_gpu"]["gather_exposed_ms"] is None and len(j["multi_gpu"]["per_rank_ms_per_step"]) == 2
+
+
+def test_a_plain_run_times_only_and_dumps_what_the_last_timed_step_computed(tmp_path):
+    """Without --full the line carries the timed figure and nothing that takes runs of its own; --dump-outputs writes rank 0's slab of
+    the last timed step as float arrays - here the oracle's own results, which the stand-in wrote."""
+    import numpy as np
+    import oracle_lib as O
+    from extractorb_amd import synth
+    r, j = run(extra_args=("--dump-outputs", str(tmp_path)), full=False)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and max(j["multi_gpu"]["per_rank_ms_per_step"]) == j["ms_per_step"]
+    assert j["verified"] is None and j["secondary"] is None and j["multi_gpu"]["rank0_kernel_ms_per_step"] is None
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("n_keypoints", "mono_index", "sampled_frames", "keypoints", "descriptors")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["sampled_frames"].tolist() == [0, 1, 2] and got["keypoints"].shape[2] == 7 and got["descriptors"].shape[2] == 32
+    frames = synth.frames("noise", 0, 3, 480, 640)           # rank 0's frames of the stream
+    o = O.Oracle(1000, 1.2, 8, 20, 7)
+    for f in range(3):
+        mono, k, d = o.extract(frames[f], (0, 1000))
+        n = len(k)
+        assert got["n_keypoints"][f] == n and got["mono_index"][f] == mono
+        want = np.stack([k[name].astype(np.float32) for name in k.dtype.names], -1)
+        assert np.array_equal(got["keypoints"][f, :n], want) and np.array_equal(got["descriptors"][f, :n], d.astype(np.float32))
+        assert not got["keypoints"][f, n:].any() and not got["descriptors"][f, n:].any()
 
 
 def test_bench_py_names_the_oracle_only_in_its_checking_legs():

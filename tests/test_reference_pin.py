@@ -16,7 +16,7 @@ Its console pane reads
     ORB_SLAM3 has total 1420 keypoints
 
 The frame is pic/TUM/dataset-room4_512_16/mav0/cam0/data/1520531124150444163.png (16-bit PNG; imread(IMREAD_GRAYSCALE) keeps the high
-byte), committed as tests/golden/tum_room4_gray.png.  1420 is a number produced by the REAL reference on REAL OpenCV: it is the only
+byte), committed as tests/golden/tum_room4_gray.png (the 16-bit original as tests/golden/tum_room4_16bit.png).  1420 is a number produced by the REAL reference on REAL OpenCV: it is the only
 reference-held pin of the oracle.  What it pins and what it does not is measured below, one restated semantic at a time
 (`enum Mutation` in oracle/orb_oracle.cpp; table in DESIGN.md §2, printed by tools/pin_sensitivity.py)."""
 import numpy as np
@@ -89,11 +89,8 @@ def test_what_the_count_pins(mutation):
 def test_decode_of_the_16_bit_frame_is_only_weakly_pinned():
     """imread(IMREAD_GRAYSCALE) of a 16-bit PNG strips to the high byte.  A scaled conversion (v*255/65535, rounded) changes three
     levels' counts (125, 62, 64 instead of 127, 63, 61) whose sum happens to be the same 251: a sum is a weak hash and the file says so."""
-    from PIL import Image
-    import os
-    if not os.path.exists("/root/reference/pic/TUM"):
-        pytest.skip("needs the 16-bit original under /root/reference (build container only)")
-    a = np.array(Image.open("/root/reference/pic/TUM/dataset-room4_512_16/mav0/cam0/data/1520531124150444163.png")).astype(np.uint32)
+    a = load_gray("tum_room4_16bit.png").astype(np.uint32)      # the 16-bit original of the pinned frame, committed unchanged
+    assert a.max() > 255
     assert np.array_equal((a >> 8).astype(np.uint8), load_gray("tum_room4_gray.png"))
     scaled = ((a * 255 + 32767) // 65535).astype(np.uint8)
     counts = total_with(0, scaled)

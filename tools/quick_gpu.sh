@@ -10,7 +10,7 @@ else
 fi
 tail -2 gpurun_out/q_${TAG}_pytest.log
 : > gpurun_out/q_${TAG}_bench.jsonl
-for args in "--steps 30" "--steps 30 --workload hd1080" "--steps 300 --batch 1" "--steps 100 --batch 64"; do
+for args in "--full --steps 30" "--full --steps 30 --workload hd1080" "--full --steps 300 --batch 1" "--full --steps 100 --batch 64"; do
   timeout -k 10 200 python bench.py --no-cpu-baseline $args 2>/dev/null | tail -1 >> gpurun_out/q_${TAG}_bench.jsonl || exit 1
 done
 python - <<PY
