@@ -74,6 +74,13 @@ void launchProjectLast(hipStream_t, const Keypoint*, const Keypoint*, const int*
                        ProjQuery*, int);
 void launchSearchProj(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                       const int*, const float*, uint8_t*, const ProjSearchParams&, int*, int*, int);
+struct TwoEyesSearchParams {      // == k_project_two_eyes.hip
+    float minX, minY, wInv, hInv, nnRatio;
+    int capacity, queryCapacity, pairFirst, pairStep, descFirst, descStep, maxDist, forceWalk;
+};
+size_t twoEyesSearchLdsBytes(int capacity, int queryCapacity);
+void launchSearchProjTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
+                             const int*, const int*, const int*, uint8_t*, const TwoEyesSearchParams&, int*, int*, int);
 struct VocabDevice {
     const int* childOff; const int* childList; const uint32_t* desc; const double* weight; const uint32_t* wordId;
     int nNodes, k, L, scoring, weighting;
@@ -103,6 +110,7 @@ struct TestAids {
     int colsShape = -1;       // "pyr_cols_shape": pins the workgroup shape of k_pyr_cols (1, 4, 6) so that the parity tests reach every one
     long long sharedUploadBytes = -1;      // "shared_upload_bytes": input copies of at least this size go through the device's shared copy queue (-1: 16 MiB)
     int failAfterFast = 0;    // "fail_after_fast": the next handle's first call with leaf tables returns between k_fast and k_octree (one shot)
+    int twoEyesWalk = 0;      // "two_eyes_walk": 1 = the two-eye projection search settles every pair by its walk instead of the fixed point
 };
 extern TestAids g_aids;
 enum Slot { S_LEVEL0 = 0, S_RESIZE, S_BLUR, S_FAST, S_OCTREE, S_DESCRIBE, S_MISC, S_TOTAL, S_STEREO, S_FRAME };
@@ -211,6 +219,7 @@ struct orbx_handle {
     hipStream_t aux = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     long long sharedUploadBytes = -1;      // test aid "shared_upload_bytes" as orbx_create read it (-1: the default limit, uploadFrames)
+    bool twoEyesWalk = false;          // test aid "two_eyes_walk" as orbx_create read it
     hipEvent_t evUp[2] = {nullptr, nullptr};      // uploadFrames: the handle's stream -> the device's shared input-copy queue -> back
     hipStream_t aux2 = nullptr;        // the blur's side stream (pyramid -> {blur, FAST -> quad-tree} -> description), events per half-batch
     hipEvent_t evPyr[2] = {nullptr, nullptr}, evBlur[2] = {nullptr, nullptr};

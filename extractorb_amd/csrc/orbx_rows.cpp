@@ -291,6 +291,37 @@ int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first,
     return ORBX_OK;
 }
 
+int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int pair_first, int pair_step, const orbx_proj_query* d_queries,
+                                              const uint8_t* d_query_desc, int desc_first, int desc_step, const int* d_n_queries,
+                                              int query_capacity, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                                              int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4,
+                                              const int* d_left_to_right, const int* d_right_to_left, uint8_t* d_occupied, float nn_ratio,
+                                              int max_distance, int* d_matches, int* d_n_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_queries || !d_query_desc || !d_kps || !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_matches || !d_n_matches ||
+        capacity < 1 || query_capacity < 1 || n_pairs < 1 || pair_first < 0 || pair_step < 0 || desc_first < 0 || desc_step < 0 || max_distance < 0 ||
+        !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/query_capacity/n_pairs < 1, negative pair/descriptor index or step, "
+                                              "negative max_distance or empty bounds");
+    if (capacity > 32767 || query_capacity > (1 << 20) || twoEyesSearchLdsBytes(capacity, query_capacity) > 160 * 1024 - 512)
+        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity / query_capacity too large for the LDS-resident two-eye search (100 bytes per keypoint of "
+                                             "an eye, 8 per MapPoint, 12 KB of cell offsets: 160 KB per CU)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TwoEyesSearchParams p;
+    p.minX = bounds4[0]; p.minY = bounds4[2];
+    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    p.nnRatio = nn_ratio; p.capacity = capacity; p.queryCapacity = query_capacity; p.pairFirst = pair_first; p.pairStep = pair_step;
+    p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = max_distance < 255 ? max_distance : 255; p.forceWalk = h->twoEyesWalk ? 1 : 0;
+    {
+        Prof pr(h, S_FRAME);
+        launchSearchProjTwoEyes(h->stream, (const ProjQuery*)d_queries, d_query_desc, d_n_queries, (const Keypoint*)d_kps, d_desc, d_n_out,
+                                d_grid_off, d_grid_idx, d_left_to_right, d_right_to_left, d_occupied, p, d_matches, d_n_matches, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"
 
 struct orbx_vocabulary {

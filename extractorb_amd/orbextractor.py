@@ -154,6 +154,9 @@ def load_library():
                                                  C.c_float, C.c_float, C.c_float, C.c_int, vp]
     L.orbx_search_by_projection_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int,
                                                    vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp]
+    L.orbx_search_by_projection_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp,
+                                                            C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
+    L.orbx_debug_two_eyes_search_stats.argtypes = [ip]
     L.orbx_vocabulary_load_text.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int]
     L.orbx_vocabulary_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int]
     L.orbx_vocabulary_destroy.argtypes = [vp]
@@ -214,6 +217,7 @@ def debug_reset_options():
     debug_set_option("fail_after_fast", 0)
     debug_set_option("pyr_cols_shape", -1)
     debug_set_option("shared_upload_bytes", -1)
+    debug_set_option("two_eyes_walk", 0)
 
 
 # ---- handle-free host helpers (no GPU needed) -------------------------------------------------------------
@@ -488,6 +492,20 @@ class ORBextractor:
             self._h, n_pairs, cur[0], cur[1], dp(d_queries), dp(d_query_desc), desc_blocks[0], desc_blocks[1], dp(d_n_queries), query_capacity,
             dp(d_kps_un), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), dp(d_u_right), dp(d_occupied),
             int(ratio_mode), nnratio, max_distance, int(check_orientation), dp(d_matches), dp(d_n_matches)))
+
+    def search_by_projection_two_eyes_device(self, n_pairs, pairs, d_queries, d_query_desc, desc_blocks, d_n_queries, query_capacity, d_kps,
+                                             d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, d_left_to_right, d_right_to_left,
+                                             d_occupied, nnratio, d_matches, d_n_matches, max_distance=100):
+        """ORBmatcher::SearchByProjection(F, vpMapPoints, th, ...) for two-camera frames (reference src/ORBmatcher.cc:44-213, F.Nleft != -1);
+        pairs = (first, step): pair q's left eye is frame 2*(first + q*step), its right eye the next frame; desc_blocks = (first, step).
+        d_queries holds two requests per MapPoint (left, right); d_matches / d_occupied are [(2q + eye)*capacity + i]."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        bounds = np.ascontiguousarray(bounds, np.float32)
+        self._check(self._L.orbx_search_by_projection_two_eyes_device(
+            self._h, n_pairs, pairs[0], pairs[1], dp(d_queries), dp(d_query_desc), desc_blocks[0], desc_blocks[1], dp(d_n_queries), query_capacity,
+            dp(d_kps), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), dp(d_left_to_right), dp(d_right_to_left),
+            dp(d_occupied), nnratio, max_distance, dp(d_matches), dp(d_n_matches)))
 
     def compute_bow_device(self, vocab, n_frames, d_desc, d_n, capacity, d_word_ids, d_word_weights, d_n_words, d_feat_nodes, d_feat_idx,
                            d_n_feat, levels_up=4):

@@ -314,6 +314,40 @@ int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first,
                                      uint8_t* d_occupied, int ratio_mode, float nn_ratio, int max_distance, int check_orientation,
                                      int* d_matches, int* d_n_matches);
 
+/* ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) for TWO-CAMERA frames (src/ORBmatcher.cc:44-213 with
+ * F.Nleft != -1; caller Tracking::SearchLocalPoints, src/Tracking.cc:2986), on the grids of orbx_frame_finish_two_eyes_device.  For pair q
+ * the left eye is frame fL = 2*(pair_first + q*pair_step) (mvKeys, mGrid) and the right eye frame fL + 1 (mvKeysRight, mGridRight); each eye
+ * has its own keypoint count d_n_out[f].  MapPoint i of pair q (the caller's vpMapPoints order, after the skips of :53-60) has two requests:
+ *   d_queries[(q*query_capacity + i)*2 + 0]  left  (L, :62-140): u, v = mTrackProjX, mTrackProjY;
+ *            radius = RadiusByViewingCos(mTrackViewCos) (2.5 if > 0.998, else 4.0) * th (only when th != 1) * mvScaleFactors[mnTrackScaleLevel];
+ *            min_level, max_level = mnTrackScaleLevel - 1, mnTrackScaleLevel;  flags bit 0 = mbTrackInView
+ *   d_queries[(q*query_capacity + i)*2 + 1]  right (R, :145-207): u, v = mTrackProjXR, mTrackProjYR;
+ *            radius = RadiusByViewingCos(mTrackViewCosR) * mvScaleFactors[mnTrackScaleLevelR] - WITHOUT th (as the reference: :148);
+ *            min_level, max_level = mnTrackScaleLevelR - 1, mnTrackScaleLevelR;  flags bit 0 = mbTrackInViewR && mnTrackScaleLevelR != -1
+ *   flags bit 1 of both: Observations() > 0 (set it the same on both);  ur and angle are unused.
+ *   d_query_desc[((desc_first + q*desc_step)*query_capacity + i)*32] : MapPoint::GetDescriptor(), one per MapPoint;
+ *   d_n_queries[q] : MapPoints of pair q (NULL: query_capacity)
+ *   d_kps, d_desc, d_n_out : the extraction's RAW keypoints (mvKeys / mvKeysRight), descriptors and counts, [f*capacity + i]
+ *   d_grid_off, d_grid_idx, bounds4 : as written by / passed to orbx_frame_finish_two_eyes_device
+ *   d_left_to_right[fL*capacity + i], d_right_to_left[(fL + 1)*capacity + j] : mvLeftToRightMatch / mvRightToLeftMatch
+ *            (ComputeStereoFishEyeMatches), each read on its own branch as the reference does, not assumed inverse; NULL = all -1; an entry
+ *            outside [0, N of the other eye) is taken as -1 (the reference would index out of bounds)
+ *   d_occupied[(2q + eye)*capacity + i] : in/out or NULL (= all free): the keypoint holds a MapPoint with Observations() > 0
+ *   nn_ratio : mfNNratio;  max_distance : TH_HIGH = 100
+ *   d_matches[(2q + eye)*capacity + i] : out, the MapPoint the keypoint holds afterwards (the LAST one written to it), -1 = none written
+ *   d_n_matches[q] : the return value: every write, 1 or 2 per accepted sub-search (the pairing writes count)
+ * A pairing write writes what it is given (also onto a keypoint outside the grid, and without looking at what the keypoint holds: a
+ * MapPoint without observations so written opens a closed keypoint again).  Supported: the tables of a pair live in LDS,
+ *   100 * ((capacity + 3) & ~3) + 8 * query_capacity + 12 392 <= 163 328 bytes
+ * (2 x orbx_max_keypoints() = 1302 of a 1200-feature extractor with query_capacity up to 2048, or capacity 1344 at 2048 MapPoints); a larger
+ * call returns ORBX_ERR_UNSUPPORTED before anything is launched.  Asynchronous on the handle's stream. */
+int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int pair_first, int pair_step, const orbx_proj_query* d_queries,
+                                              const uint8_t* d_query_desc, int desc_first, int desc_step, const int* d_n_queries,
+                                              int query_capacity, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                                              int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4,
+                                              const int* d_left_to_right, const int* d_right_to_left, uint8_t* d_occupied, float nn_ratio,
+                                              int max_distance, int* d_matches, int* d_n_matches);
+
 /* ---- next row: Frame::ComputeBoW (src/Frame.cc:739-746) --------------------------------------------------
  * = DBoW2::TemplatedVocabulary<FORB>::transform(features, BowVector, FeatureVector, levelsup = 4)
  * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1196, 1218-1262; BowVector.cpp:34-83; FeatureVector.cpp:31-46).
@@ -378,6 +412,10 @@ int orbx_synchronize(orbx_handle* h);
 /* ---- introspection used by tests and bench.py (not part of the reference surface) ------------- */
 /* rounds the fixed-point projection search of the last launch needed for pair 0, and 100-MHz ticks of its staging / first scan / rounds */
 int orbx_debug_search_rounds(int* out4);
+/* the two-eye projection search (orbx_search_by_projection_two_eyes_device): out4[0] rounds the fixed point of the last launch's pair 0
+ * needed, [1] 1 if pair 0 was settled by the walk (forced, or a MapPoint without observations reopened a keypoint), [2] pairs settled by the
+ * walk since the last read (the read resets it), [3] 100-MHz ticks of pair 0's workgroup.  Returns 0, or a negative orbx_status. */
+int orbx_debug_two_eyes_search_stats(int* out4);
 
 /* Which launch forms the last call took (results never depend on them; the parity tests assert the form they mean to cover and the
  * published timings name theirs): pyramid_form 0 = k_pyr_cols (region-major, *pyramid_cut_px = side of its regions), 1 = k_pyr_first +
@@ -393,7 +431,8 @@ int orbx_debug_last_split_level(const orbx_handle* h);
  * filled with in front of every kernel; -1 = off), "fail_after_fast" (1: the next handle's first small-batch call returns ORBX_ERR_HIP
  * between the FAST and the quad-tree launch, once), "pyr_cols_shape" (1, 4 or 6: pins the workgroup shape of k_pyr_cols; -1 = by the grid
  * size), "shared_upload_bytes" (host-buffer batches whose input is at least this large copy it through the device's shared copy queue
- * and bring the results back by DMA, smaller ones use the handle's stream and a copy kernel; -1 = 16 MiB).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
+ * and bring the results back by DMA, smaller ones use the handle's stream and a copy kernel; -1 = 16 MiB), "two_eyes_walk" (1: the two-eye
+ * projection search settles every pair by its walk instead of the fixed point; 0 = by the decisions).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
 int orbx_debug_set_option(const char* name, int value);
 
 /* The launch-policy switches as orbx_create read them, "NAME=value" separated by blanks, "(env)" behind a value that came from an ORBX_<NAME>
