@@ -761,6 +761,7 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     h->blurSplit = envInt("ORBX_BLUR_SPLIT", -1);
     h->sharedUploadBytes = g_aids.sharedUploadBytes;
     h->twoEyesWalk = g_aids.twoEyesWalk == 1;
+    h->twoEyesBowStage = g_aids.twoEyesBowStage != 0;
     h->colsShape = g_aids.colsShape == 1 || g_aids.colsShape == 4 || g_aids.colsShape == 6 ? g_aids.colsShape : -1;
     h->colsCap = 0;
     for (int px : kColPx) h->colsCap += (size_t)((max_width + px / 2) / px + 1) * ((max_height + px / 2) / px + 1);

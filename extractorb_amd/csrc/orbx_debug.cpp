@@ -21,6 +21,7 @@ int orbx_debug_set_option(const char* name, int value) {
     else if (n == "pyr_cols_shape") g_aids.colsShape = value;
     else if (n == "shared_upload_bytes") g_aids.sharedUploadBytes = value;
     else if (n == "two_eyes_walk") g_aids.twoEyesWalk = value;
+    else if (n == "two_eyes_bow_stage") g_aids.twoEyesBowStage = value;
     else return ORBX_ERR_BAD_ARGUMENT;
     return ORBX_OK;
 }

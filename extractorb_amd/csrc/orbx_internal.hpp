@@ -27,6 +27,9 @@ void launchResize(hipStream_t, const LevelGeom&, const LevelGeom&, int, int, con
 struct BowMatchParams { float nnRatio; int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep, twoKeyFrames; };
 size_t bowMatchLdsBytes(int capacity, bool stageDesc);
 void launchSearchBow(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowMatchParams&, int*, int*, int);
+struct BowTwoEyesParams { float nnRatio; int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep; };      // == k_bow_match_two_eyes.hip
+size_t bowTwoEyesLdsBytes(int capacity, bool stage);
+void launchSearchBowTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowTwoEyesParams&, bool, int*, int*, int);
 void launchLdsPollute(hipStream_t, int, int, unsigned*);
 void launchPyrCols(hipStream_t, const uint8_t*, long long, long long, int, const PyrColumn*, int, const ColLevels*, int, const ResizeX*, int, uint8_t*, int, int, bool, int, int, int);
 void launchBlur(hipStream_t, const BlurItem*, const unsigned short*, int, int, const LevelGeom*, const uint8_t*, uint8_t*, int, int);
@@ -110,6 +113,7 @@ struct TestAids {
     int colsShape = -1;       // "pyr_cols_shape": pins the workgroup shape of k_pyr_cols (1, 4, 6) so that the parity tests reach every one
     long long sharedUploadBytes = -1;      // "shared_upload_bytes": input copies of at least this size go through the device's shared copy queue (-1: 16 MiB)
     int failAfterFast = 0;    // "fail_after_fast": the next handle's first call with leaf tables returns between k_fast and k_octree (one shot)
+    int twoEyesBowStage = -1; // "two_eyes_bow_stage": 0 = the two-eye BoW search reads the frame pair's descriptors from L2 whatever the capacity (the form of large capacities)
     int twoEyesWalk = 0;      // "two_eyes_walk": 1 = the two-eye projection search settles every pair by its walk instead of the fixed point
 };
 extern TestAids g_aids;
@@ -219,6 +223,7 @@ struct orbx_handle {
     hipStream_t aux = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr;
     long long sharedUploadBytes = -1;      // test aid "shared_upload_bytes" as orbx_create read it (-1: the default limit, uploadFrames)
+    bool twoEyesBowStage = true;       // test aid "two_eyes_bow_stage" as orbx_create read it
     bool twoEyesWalk = false;          // test aid "two_eyes_walk" as orbx_create read it
     hipEvent_t evUp[2] = {nullptr, nullptr};      // uploadFrames: the handle's stream -> the device's shared input-copy queue -> back
     hipStream_t aux2 = nullptr;        // the blur's side stream (pyramid -> {blur, FAST -> quad-tree} -> description), events per half-batch

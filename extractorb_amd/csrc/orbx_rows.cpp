@@ -504,4 +504,28 @@ int orbx_search_by_bow_keyframes_device(orbx_handle* h, int n_pairs, int kf1_fir
                        d_desc, d_n_out, capacity, nn_ratio, th_low, check_orientation, d_matches12, d_n_matches);
 }
 
+int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int cur_first, int cur_step,
+                                       const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat,
+                                       const uint8_t* d_kf_mp_flags, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                                       int capacity, float nn_ratio, int th_low, int check_orientation, int* d_matches, int* d_n_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_feat_nodes || !d_feat_idx || !d_n_feat || !d_kf_mp_flags || !d_kps || !d_desc || !d_n_out || !d_matches || !d_n_matches ||
+        capacity < 1 || n_pairs < 1 || kf_first < 0 || cur_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
+        cur_first + (long long)(n_pairs - 1) * cur_step < 0)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1 or a negative pair index");
+    if (bowTwoEyesLdsBytes(capacity, false) > 160 * 1024 - 512)
+        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident two-eye BoW search (40 bytes per slot of the capacity "
+                                             "rounded up to 16, + 64: 160 KB per CU)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    BowTwoEyesParams p{nn_ratio, th_low < 255 ? th_low : 255, check_orientation ? 1 : 0, capacity, kf_first, kf_step, cur_first, cur_step};
+    const bool stage = h->twoEyesBowStage && bowTwoEyesLdsBytes(capacity, true) <= 160 * 1024 - 512;
+    {
+        Prof pr(h, S_FRAME);
+        launchSearchBowTwoEyes(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, (const Keypoint*)d_kps, d_desc, d_n_out, p, stage,
+                               d_matches, d_n_matches, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"

@@ -167,6 +167,8 @@ def load_library():
                                             C.c_int, C.c_int, vp, vp]
     L.orbx_search_by_bow_keyframes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
                                                       C.c_float, C.c_int, C.c_int, vp, vp]
+    L.orbx_search_by_bow_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int,
+                                                     C.c_float, C.c_int, C.c_int, vp, vp]
     L.orbx_stereo_match_last.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, vp, C.c_int, vp]
     L.orbx_compute_image_bounds.argtypes = [vp, C.c_int, C.c_int, vp]
     L.orbx_frame_finish_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -218,6 +220,7 @@ def debug_reset_options():
     debug_set_option("pyr_cols_shape", -1)
     debug_set_option("shared_upload_bytes", -1)
     debug_set_option("two_eyes_walk", 0)
+    debug_set_option("two_eyes_bow_stage", -1)
 
 
 # ---- handle-free host helpers (no GPU needed) -------------------------------------------------------------
@@ -533,6 +536,18 @@ class ORBextractor:
                                                                 dp(d_n_feat), dp(d_kf1_mp_flags), dp(d_kf2_mp_flags), dp(d_kps), dp(d_desc), dp(d_n),
                                                                 capacity, C.c_float(nnratio), th_low, int(check_orientation), dp(d_matches12),
                                                                 dp(d_n_matches)))
+
+    def search_by_bow_two_eyes_device(self, n_pairs, kf, cur, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, d_kps, d_desc, d_n, capacity,
+                                      d_matches, d_n_matches, nnratio=0.7, th_low=50, check_orientation=True):
+        """ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) for two-camera frames (reference src/ORBmatcher.cc:269-471, F.Nleft != -1); kf and
+        cur = (first, step) in PAIRS: pair X is frame 2X (left eye) and 2X + 1 (right eye).  d_kf_mp_flags and d_matches are
+        [(2p + eye)*capacity + i]; a match names the keyframe feature by its concatenated index (left: i, right: Nleft of the keyframe + j)."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        self._check(self._L.orbx_search_by_bow_two_eyes_device(self._h, n_pairs, kf[0], kf[1], cur[0], cur[1], dp(d_feat_nodes), dp(d_feat_idx),
+                                                               dp(d_n_feat), dp(d_kf_mp_flags), dp(d_kps), dp(d_desc), dp(d_n), capacity,
+                                                               C.c_float(nnratio), th_low, int(check_orientation), dp(d_matches),
+                                                               dp(d_n_matches)))
 
     def stereo_from_rgbd_device(self, n_frames, d_kps, d_kps_un, d_n, capacity, d_depth, depth_is_u16, rows, cols, depth_map_factor, mbf,
                                 d_u_right, d_depth_out, depth_stride_bytes=None, depth_frame_stride_bytes=None):

@@ -402,6 +402,38 @@ int orbx_search_by_bow_keyframes_device(orbx_handle* h, int n_pairs, int kf1_fir
                                         const uint8_t* d_desc, const int* d_n_out, int capacity, float nn_ratio, int th_low,
                                         int check_orientation, int* d_matches12, int* d_n_matches);
 
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) for TWO-CAMERA frames (src/ORBmatcher.cc:269-471 with F.Nleft != -1:
+ * the else branch :340-367 and :373-433; the function reads descriptors, the two FeatureVectors, keypoint angles and F.Nleft, and the
+ * camera pair only as null tests).  Search p matches keyframe pair K = kf_first + p*kf_step against frame pair C = cur_first + p*cur_step;
+ * a pair X is batch frame 2X (left eye: mvKeys, the first Nleft rows of mDescriptors) and 2X + 1 (right eye: mvKeysRight, the other rows),
+ * Nleft = d_n_out[2X], Nright = d_n_out[2X + 1].  kf_step = 0 (one keyframe, many frames) and cur_step = 0 (relocalisation) are allowed.
+ *   d_feat_nodes, d_feat_idx, d_n_feat : what orbx_compute_bow_device wrote PER EYE (frames 2X and 2X + 1), same capacity.  The mFeatVec of
+ *                 the stacked descriptors is not needed: a node's list there is the left eye's list followed by the right eye's (+ Nleft),
+ *                 and the entry walks them so.  (The pair's mBowVec, which KeyFrameDatabase needs and this matcher does not, is what
+ *                 orbx_compute_bow_device gives for the two descriptor blocks packed back to back as one frame.)
+ *   d_kf_mp_flags[(2p + eye)*capacity + i] : bit 0 = keypoint i of that eye of the KEYFRAME holds a MapPoint that is not bad (:301-307)
+ *   d_kps[f*capacity + i] : the extraction's RAW keypoints of all frames; only .angle is read, of the eye the index falls in (:382-391,
+ *                 :408-417).  A one-camera keyframe is the case d_n_out[2K + 1] == 0 (mvKeysUn keeps the angle).
+ *   d_desc, d_n_out : descriptors and counts of all frames
+ *   nn_ratio = mfNNratio;  th_low = ORBmatcher::TH_LOW (50), a value above 255 is taken as 255;  check_orientation = mbCheckOrientation
+ *   d_matches[(2p + eye)*capacity + i] : out, for keypoint i of that eye of the FRAME the keyframe feature whose MapPoint it received, in
+ *                 the index space of pKF->GetMapPointMatches() (i_kf for a left feature, Nleft of the keyframe + j_kf for a right one),
+ *                 -1 = none; all capacity entries of both eyes are written
+ *   d_n_matches[p] : out, the return value (= the number of entries >= 0)
+ * As the reference: per keyframe feature the frame's open left and right candidates of the node are ranked separately; nothing happens
+ * unless the LEFT best is within th_low; then the left keypoint is written if it passes the ratio test and, whether or not it did, the
+ * right best if it is within th_low (its ratio test is disabled, :403).  One keyframe feature can so hand its MapPoint to two keypoints,
+ * and a node without an open left candidate never matches a right one.  The rotation histogram takes the pushes of both eyes.
+ * Supported: the tables of a search live in LDS,
+ *   40 * ((capacity + 15) & ~15) + 64 <= 163 328 bytes      (capacity <= 4080; orbx_max_keypoints() = 1302 of a 1200-feature extractor is inside)
+ * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched.  While 104 * ((capacity + 15) & ~15) + 64 <= 163 328
+ * (capacity <= 1568) the frame pair's descriptors are staged in LDS as well ("Two-eye BoW search": measured times); above, they
+ * are read from L2.  Asynchronous on the handle's stream. */
+int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int cur_first, int cur_step,
+                                       const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat,
+                                       const uint8_t* d_kf_mp_flags, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                                       int capacity, float nn_ratio, int th_low, int check_orientation, int* d_matches, int* d_n_matches);
+
 /* Stream control.  By default the handle owns a stream; orbx_set_stream adopts a caller stream
  * (hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream) so the caller's events
  * and graphs see the work. */
@@ -432,7 +464,8 @@ int orbx_debug_last_split_level(const orbx_handle* h);
  * between the FAST and the quad-tree launch, once), "pyr_cols_shape" (1, 4 or 6: pins the workgroup shape of k_pyr_cols; -1 = by the grid
  * size), "shared_upload_bytes" (host-buffer batches whose input is at least this large copy it through the device's shared copy queue
  * and bring the results back by DMA, smaller ones use the handle's stream and a copy kernel; -1 = 16 MiB), "two_eyes_walk" (1: the two-eye
- * projection search settles every pair by its walk instead of the fixed point; 0 = by the decisions).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
+ * projection search settles every pair by its walk instead of the fixed point; 0 = by the decisions), "two_eyes_bow_stage" (0: the two-eye
+ * BoW search reads the frame pair's descriptors from L2 whatever the capacity; -1 = staged in LDS where they fit).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
 int orbx_debug_set_option(const char* name, int value);
 
 /* The launch-policy switches as orbx_create read them, "NAME=value" separated by blanks, "(env)" behind a value that came from an ORBX_<NAME>
