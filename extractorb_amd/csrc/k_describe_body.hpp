@@ -5,7 +5,7 @@
 #include <stdint.h>
 
 #include "orbx_device.hpp"
-#include "k_blur_body.hpp"      // blurRun: the patch-blur form blurs a keypoint's 37 x 37 patch out of its raw 43 x 43 tile
+#include "k_blur_body.hpp"      // hsums4, satPack4: the patch-blur form blurs a keypoint's 37 x 37 patch out of its raw 43 x 43 tile
 
 namespace orbx {
 // ================================================================================================
@@ -104,11 +104,66 @@ constexpr int kPbLds = kPbRawBytes + kBlurRows * kBlurStride;               // 3
 // two-row blur loop; the box dealt as 10 groups x 3 runs of 13 was seven): entry = group | first row << 8 | rows << 16.  WHERE the runs of a group are cut
 // matters: the 32 lanes read tile rows (first row + i) x 11 dwords + group, and a first cut (runs of 10 / 12 rows from the top) had them collide in the LDS
 // banks 4.4-fold on average (SQ_LDS_BANK_CONFLICT: 514 cycles per wave, the old 10 x 3 layout: 2-fold) - which ate the instructions the disc saves.  The cuts
-// below come from a search (simulated annealing over the partitions; cost = sum over the loop's LDS instructions of the largest number of lanes on one
+// below came from a search (simulated annealing over the partitions; cost = sum over the loop's LDS instructions of the largest number of lanes on one
 // bank, loads of the raw tile and stores of the blurred one): 143 against 259 for the first cut and 66 for a conflict-free walk.
+// Round 7: a run of n rows read n + 6 tile rows and made the horizontal sums of all of them, so the six halo rows of a run were summed twice - by the
+// lane and by its neighbour in the group: 32 lanes x 18 = 576 row passes for the 370 (group, tile row) items the disc needs.  Now every item is summed by
+// ONE lane (32 x 12 = 384 passes) and the halo travels between lanes by DPP, no memory: the groups are laid end to end on two VIRTUAL columns of 192
+// rows, one per DPP row of 16 lanes (tools/pb_lane_search.py: groups 2 4 9 7 3 | 0 6 1 5 8).  Lane l of a DPP row sums virtual rows 12 l .. 12 l + 11 - six
+// row PAIRS, two u16 sums to a register -, takes the first three pairs of lane l + 1 (row_shl:1) and blurs output rows 12 l .. 12 l + 11 out of the
+// nine.  A group of n output rows takes n + 6 virtual rows (tile rows 18 - rmax .. 24 + rmax) from an even one on; the six outputs over its last rows
+// mix two groups and are not stored - they are the halo, so nothing is lost: 370 + 10 of the 384 rows are used.  The groups are ordered and padded so
+// that the rows a lane STORES lie in one group (c_pbRun keeps its format: one run per lane, what the lane stores) and a group lies in one DPP row, its
+// stored rows ending before the last lane's row 6.  c_pbSrc says what a lane READS: its rows i < split are tile bytes offA + 44 i (group A's tail),
+// the others (offB - 1024) + 44 i (the head of the group it stores to); split is even, so a row pair has one address.  Rows between two groups (padding:
+// at most tile row 43, which is not staged - the bytes behind the tile, inside the keypoint's own LDS) only reach outputs that are not stored.
+// entry = offA | offB << 11 | split << 23 | k0 << 27, k0 = the lane's output (0 .. 11) that is row 0 of its run.  tests/test_patch_blur_lanes.py replays
+// both tables.  The search takes the layout with the fewest bank collisions of those that fit (its cost: 144; worst: 192).
 static __constant__ unsigned c_pbRun[32] = {
-    0x0b0700, 0x0c1200, 0x080301, 0x0b0b01, 0x0c1601, 0x0c0102, 0x0c0d02, 0x0b1902, 0x050003, 0x0c0503, 0x091103, 0x0b1a03, 0x050004, 0x0c0504, 0x081104,
-    0x0c1904, 0x060005, 0x0c0605, 0x091205, 0x0a1b05, 0x050006, 0x0c0506, 0x0c1106, 0x081d06, 0x0b0207, 0x0b0d07, 0x0b1807, 0x0c0508, 0x0c1108, 0x031d08, 0x010c09, 0x0c0d09};
+    0x0c0102, 0x0c0d02, 0x0b1902, 0x060004, 0x0c0604, 0x0c1204, 0x071e04, 0x0a0c09, 0x031609, 0x0c0207, 0x0c0e07, 0x091a07, 0x080003, 0x0c0803, 0x0c1403,
+    0x052003, 0x0c0700, 0x0b1300, 0x060006, 0x0c0606, 0x0c1206, 0x071e06, 0x0a0301, 0x0c0d01, 0x091901, 0x080005, 0x0c0805, 0x0c1405, 0x052005, 0x0c0508,
+    0x0c1108, 0x031d08};
+static __constant__ unsigned c_pbSrc[32] = {
+    0x0621a034, 0x06322244, 0x0642a454, 0x33184664, 0x0628c118, 0x06394328, 0x0649c538, 0x112ee748, 0x063f63ec, 0x0623a074, 0x06342284, 0x0644a494,
+    0x221ae6a4, 0x062b616c, 0x063be37c, 0x064c658c, 0x0629a134, 0x063a2344, 0x33188554, 0x06290120, 0x06398330, 0x064a0540, 0x11218750, 0x06320240,
+    0x06428450, 0x221b2660, 0x062ba174, 0x063c2384, 0x064ca594, 0x0627e0fc, 0x0638630c, 0x0648e51c};
+
+// The patch blur of one lane (see c_pbSrc): horizontal sums of its own six row pairs (hsums4: the arithmetic of blurRun), the next lane's first three
+// by DPP, then the vertical pass of blurRun on the nine pairs W[0 .. 8] - output 2 t reads pairs t .. t + 2 and the low half of pair t + 3, output
+// 2 t + 1 the high half of pair t and pairs t + 1 .. t + 3: the same dot2 taps in the same order, the same integers.  Outputs kLo <= k < kHi are stored,
+// output k at dst + k * kBlurStride.  All indices are static (a run-time index into W would be scratch).  Every lane of the wave must be active.
+__device__ __forceinline__ void blurPatchLanes(const uint8_t* srcA, const uint8_t* srcB, int split, uint8_t* dst, int kLo, int kHi) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    auto dot2 = [](unsigned pair, unsigned short w0, unsigned short w1, unsigned acc) {
+        return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pair), u16x2{w0, w1}, acc, false);
+    };
+    unsigned W[9][4];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const unsigned* r0 = (const unsigned*)((2 * k < split ? srcA : srcB) + 2 * k * kPbStride);
+        const unsigned* r1 = r0 + kPbStride / 4;
+        unsigned he[4], ho[4];
+        hsums4(r0[0], r0[1], r0[2], he);
+        hsums4(r1[0], r1[1], r1[2], ho);
+#pragma unroll
+        for (int j = 0; j < 4; j++) W[k][j] = (ho[j] << 16) | he[j];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) W[6 + k][j] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)W[k][j], 0x101, 0xF, 0xF, true);      // row_shl:1: lane l + 1's
+#pragma unroll
+    for (int t = 0; t < 6; t++) {
+        unsigned e[4], o[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            e[j] = dot2(W[t + 3][j], 18, 0, dot2(W[t + 2][j], 49, 34, dot2(W[t + 1][j], 49, 55, dot2(W[t][j], 18, 34, 32768u))));
+            o[j] = dot2(W[t + 3][j], 34, 18, dot2(W[t + 2][j], 55, 49, dot2(W[t + 1][j], 34, 49, dot2(W[t][j], 0, 18, 32768u))));
+        }
+        if (2 * t >= kLo && 2 * t < kHi) *(unsigned*)(dst + 2 * t * kBlurStride) = satPack4(e);
+        if (2 * t + 1 >= kLo && 2 * t + 1 < kHi) *(unsigned*)(dst + (2 * t + 1) * kBlurStride) = satPack4(o);
+    }
+}
 
 // One half-wave (32 lanes) per kept keypoint; the two keypoints of a wave share a level (selOff is even):
 //   * both patches are staged in LDS with aligned dword loads that are all in flight at once: a half-wave covers
@@ -119,7 +174,7 @@ static __constant__ unsigned c_pbRun[32] = {
 //   * rBRIEF: lane = 8 of the 256 test pairs; a ballot per group of 32 pairs packs 4 descriptor bytes of each keypoint.
 #if defined(ORBX_DESC_STAMPS) && defined(ORBX_DESCRIBE_TU)      // (diagnostic builds stamp the kernel of k_describe.hip only)
 // diagnostic build (tools/desc_spans.py): stage stamps of every wave of frame 0, s_memrealtime ticks
-__device__ unsigned long long g_descStamps[6 * 1024];
+__device__ unsigned long long g_descStamps[6 * 1024];      // per wave: [0 .. 4] the stages in order, [5] (PB only) the end of the patch blur, between [3] and [4]
 extern "C" int orbx_debug_desc_stamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_descStamps), sizeof(g_descStamps)); }
 #define DSTAMP(i) do { const int dsW = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6); \
         if ((threadIdx.x & 63) == 0 && blockIdx.x == 0 && blockIdx.z == 0 && dsW < 1024) g_descStamps[6 * dsW + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -228,8 +283,8 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
     int m10 = 0, m01 = 0;
     uint8_t* blurT;
     int blurMis;
-    unsigned pbRun = 0;
-    if constexpr (PB) pbRun = c_pbRun[hl];      // (requested ahead of the tile's loads)
+    unsigned pbRun = 0, pbSrc = 0;
+    if constexpr (PB) { pbRun = c_pbRun[hl]; pbSrc = c_pbSrc[hl]; }      // (requested ahead of the tile's loads)
     if constexpr (PB) {
         // ---- stage the raw 43 x 44 tile, re-aligned: 8 lanes per tile row (6 load an 8-byte pair of source dwords - 4-byte aligned: one
         //      global_load_dwordx2 -, 11 re-aligned dwords stored), four rows per step: 11 load instructions per wave (dword loads: 22; the gather is bound
@@ -276,19 +331,15 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
             m10 = (int)s1 - 16 * (int)s0;     // sum u*I
             m01 = v * (int)s0;                // v * sum I
         }
-        // ---- the 7x7 blur of the part of the 37 x 37 patch the rotated pattern can reach (:1126-1127): lane = one (column group, run of rows) of
-        //      c_pbRun; output row o reads tile rows o .. o + 6 ----
+        // ---- the 7x7 blur of the part of the 37 x 37 patch the rotated pattern can reach (:1126-1127): the lane stores the (column group, run of
+        //      rows) of c_pbRun and sums the tile rows of c_pbSrc; output row o reads tile rows o .. o + 6 ----
         {
             const int g4 = (int)(pbRun & 0xff), o0 = (int)((pbRun >> 8) & 0xff), nOut = (int)(pbRun >> 16);
-            const uint8_t* src = rawT + o0 * kPbStride + 4 * g4;
-            uint8_t* dst = blurT + o0 * kBlurStride + 4 * g4;
-            blurRun(nOut,
-                    [&](int i, unsigned& d0, unsigned& d1, unsigned& d2) {
-                        const unsigned* row = (const unsigned*)(src + min(i, nOut + 5) * kPbStride);
-                        d0 = row[0]; d1 = row[1]; d2 = row[2];
-                    },
-                    [&](int rr, unsigned word) { *(unsigned*)(dst + rr * kBlurStride) = word; });
+            const int k0 = (int)(pbSrc >> 27), split = (int)((pbSrc >> 23) & 15);
+            blurPatchLanes(rawT + (pbSrc & 0x7ff), rawT + ((int)((pbSrc >> 11) & 0xfff) - 1024), split,
+                           blurT + (o0 - k0) * kBlurStride + 4 * g4, k0, k0 + nOut);
         }
+        DSTAMP(5);
         asm volatile("" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -375,18 +426,26 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
     const float factorPI = (float)(3.1415926535897932384626433832795 / 180.0);   // (float)(CV_PI/180.f)
     float a, b;
     sincosGlibc(__fmul_rn(angle, factorPI), &b, &a);
-    const uint8_t* bc = blurT + kBriefReach * kBlurStride + blurMis + kBriefReach;
+    // (int)rintf(v) is v_rndne_f32 + v_cvt_i32_f32.  One addition does both: v + 1.5 * 2^23 lies in [2^23, 2^24), where the spacing of binary32 is 1, so
+    // the addition itself rounds v to an integer, to nearest and ties to even as rintf does (|v| <= 18.4 here, any |v| <= 2^22 would do), and the bits
+    // of the sum are 0x4B400000 + rint(v).  v_mad_u32_u24 multiplies the low 24 bits of the row's sum, 0x400000 + r, by the tile's stride and adds the
+    // column's: 40 r + q + kRintOff, and the lane's base address carries - kRintOff (LDS addresses are 32 bits and wrap): four instructions per sample
+    // instead of six.  tests/test_rint_by_addition.py compares the two roundings over every float of the range.
+    constexpr float kRintMagic = 12582912.f;                                          // 1.5 * 2^23 = 0x4B400000
+    constexpr unsigned kRintOff = kBlurStride * 0x400000u + 0x4B400000u;
+    typedef __attribute__((address_space(3))) const uint8_t* LdsBytes;
+    const unsigned bc = (unsigned)(uintptr_t)(LdsBytes)(blurT + kBriefReach * kBlurStride + blurMis + kBriefReach) - kRintOff;
     unsigned myWord = 0;                   // lane hl < 8 ends up holding descriptor bytes 4*hl .. 4*hl+3 of its keypoint
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const int p = hl + 32 * j;        // test pair index; bit (p & 7) of descriptor byte (p >> 3)
         const float4 pt = ((const float4*)c_patternF)[p];
         const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
-        const int r0 = (int)rintf(__fadd_rn(__fmul_rn(x0, b), __fmul_rn(y0, a)));
-        const int q0 = (int)rintf(__fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b)));
-        const int r1 = (int)rintf(__fadd_rn(__fmul_rn(x1, b), __fmul_rn(y1, a)));
-        const int q1 = (int)rintf(__fsub_rn(__fmul_rn(x1, a), __fmul_rn(y1, b)));
-        const int t0 = bc[__mul24(r0, kBlurStride) + q0], t1 = bc[__mul24(r1, kBlurStride) + q1];
+        const unsigned r0 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(x0, b), __fmul_rn(y0, a)), kRintMagic));
+        const unsigned q0 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b)), kRintMagic));
+        const unsigned r1 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(x1, b), __fmul_rn(y1, a)), kRintMagic));
+        const unsigned q1 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(x1, a), __fmul_rn(y1, b)), kRintMagic));
+        const int t0 = *(LdsBytes)(uintptr_t)(bc + __umul24(r0, kBlurStride) + q0), t1 = *(LdsBytes)(uintptr_t)(bc + __umul24(r1, kBlurStride) + q1);
         const unsigned long long m = __ballot(t0 < t1);
         const unsigned mine = half ? (unsigned)(m >> 32) : (unsigned)m;
         myWord = hl == j ? mine : myWord;

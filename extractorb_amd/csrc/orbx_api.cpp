@@ -903,7 +903,10 @@ int orbx_extract_batch_begin(orbx_handle* h, int n_frames, const uint8_t* imgs, 
         // kernels are done (k_copy.hip; uploadFrames)
         const size_t bytes = want_levels ? lo.all : lo.noLevels;
         if (usesSharedUpload(h, B, rows, cols)) HIP_TRY(h, hipMemcpyAsync(h->h_out, h->d_out, bytes, hipMemcpyDeviceToHost, st));
-        else launchCopyOut(st, h->d_out, h->h_out, bytes, h->numCUs);
+        else {
+            launchCopyOut(st, h->d_out, h->h_out, bytes, h->numCUs);
+            HIP_TRY(h, hipGetLastError());      // (a launch reports nothing by itself: a refused one would leave the slab of the last batch)
+        }
     }
     h->pendingB = B;
     h->lastHostB = B;
