@@ -30,6 +30,12 @@ void launchSearchBow(hipStream_t, const uint32_t*, const uint32_t*, const int*, 
 struct BowTwoEyesParams { float nnRatio; int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep; };      // == k_bow_match_two_eyes.hip
 size_t bowTwoEyesLdsBytes(int capacity, bool stage);
 void launchSearchBowTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowTwoEyesParams&, bool, int*, int*, int);
+struct TriMatchParams {      // == k_triangulate_match.hip
+    float scale[kMaxLevels], sigma2[kMaxLevels];
+    int nlevels, thLow, checkOrientation, onlyStereo, coarse, capacity, kf1First, kf1Step, kf2First, kf2Step;
+};
+size_t triMatchLdsBytes(int capacity, bool stage);
+void launchSearchTriangulation(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const float*, const uint8_t*, const int*, const float*, const float*, const TriMatchParams&, bool, int*, int*, int*, int);
 void launchLdsPollute(hipStream_t, int, int, unsigned*);
 void launchPyrCols(hipStream_t, const uint8_t*, long long, long long, int, const PyrColumn*, int, const ColLevels*, int, const ResizeX*, int, uint8_t*, int, int, bool, int, int, int);
 void launchBlur(hipStream_t, const BlurItem*, const unsigned short*, int, int, const LevelGeom*, const uint8_t*, uint8_t*, int, int);

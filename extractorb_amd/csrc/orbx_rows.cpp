@@ -528,4 +528,34 @@ int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first
     return ORBX_OK;
 }
 
+int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
+                                         const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat,
+                                         const uint8_t* d_kf1_mp_flags, const uint8_t* d_kf2_mp_flags, const orbx_keypoint* d_kps_un,
+                                         const float* d_u_right, const uint8_t* d_desc, const int* d_n_out, int capacity, const float* d_f12,
+                                         const float* d_epipole, int only_stereo, int coarse, int th_low, int check_orientation,
+                                         int* d_matches12, int* d_pairs, int* d_n_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_feat_nodes || !d_feat_idx || !d_n_feat || !d_kf1_mp_flags || !d_kf2_mp_flags || !d_kps_un || !d_desc || !d_n_out || !d_f12 ||
+        !d_epipole || !d_matches12 || !d_pairs || !d_n_matches || capacity < 1 || n_pairs < 1 || kf1_first < 0 || kf2_first < 0 ||
+        kf1_first + (long long)(n_pairs - 1) * kf1_step < 0 || kf2_first + (long long)(n_pairs - 1) * kf2_step < 0)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1 or a negative frame index");
+    if (triMatchLdsBytes(capacity, false) > 160 * 1024 - 512)
+        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident triangulation search (28 bytes per slot of the capacity "
+                                             "rounded up to 16, + 64: 160 KB per CU)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TriMatchParams p{};
+    for (int i = 0; i < kMaxLevels; i++) { p.scale[i] = h->tabs.scale[i]; p.sigma2[i] = h->tabs.sigma2[i]; }
+    p.nlevels = std::max(1, std::min(h->nlevels, (int)kMaxLevels));
+    p.thLow = th_low; p.checkOrientation = check_orientation ? 1 : 0; p.onlyStereo = only_stereo ? 1 : 0; p.coarse = coarse ? 1 : 0;
+    p.capacity = capacity; p.kf1First = kf1_first; p.kf1Step = kf1_step; p.kf2First = kf2_first; p.kf2Step = kf2_step;
+    const bool stage = triMatchLdsBytes(capacity, true) <= 160 * 1024 - 512;
+    {
+        Prof pr(h, S_FRAME);
+        launchSearchTriangulation(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, (const Keypoint*)d_kps_un, d_u_right,
+                                  d_desc, d_n_out, d_f12, d_epipole, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"

@@ -169,6 +169,8 @@ def load_library():
                                                       C.c_float, C.c_int, C.c_int, vp, vp]
     L.orbx_search_by_bow_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int,
                                                      C.c_float, C.c_int, C.c_int, vp, vp]
+    L.orbx_search_for_triangulation_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                       C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.orbx_stereo_match_last.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, vp, C.c_int, vp]
     L.orbx_compute_image_bounds.argtypes = [vp, C.c_int, C.c_int, vp]
     L.orbx_frame_finish_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -548,6 +550,20 @@ class ORBextractor:
                                                                dp(d_n_feat), dp(d_kf_mp_flags), dp(d_kps), dp(d_desc), dp(d_n), capacity,
                                                                C.c_float(nnratio), th_low, int(check_orientation), dp(d_matches),
                                                                dp(d_n_matches)))
+
+    def search_for_triangulation_device(self, n_pairs, kf1, kf2, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, d_kps_un,
+                                        d_u_right, d_desc, d_n, capacity, d_f12, d_epipole, d_matches12, d_pairs, d_n_matches,
+                                        only_stereo=False, coarse=False, th_low=50, check_orientation=True):
+        """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) for one-camera keyframes with the Pinhole
+        model (reference src/ORBmatcher.cc:965-1206); kf1 and kf2 = (first, step), step 0 = one keyframe against many.  d_f12 [p*9] row-major
+        and d_epipole [p*2] are inputs; d_u_right may be None (no feature is stereo).  d_matches12 is [p*capacity + i], d_pairs
+        [(p*capacity + k)*2] holds d_n_matches[p] pairs (i, d_matches12[i]) in increasing i."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        self._check(self._L.orbx_search_for_triangulation_device(
+            self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], dp(d_feat_nodes), dp(d_feat_idx), dp(d_n_feat), dp(d_kf1_mp_flags),
+            dp(d_kf2_mp_flags), dp(d_kps_un), dp(d_u_right), dp(d_desc), dp(d_n), capacity, dp(d_f12), dp(d_epipole), int(only_stereo),
+            int(coarse), th_low, int(check_orientation), dp(d_matches12), dp(d_pairs), dp(d_n_matches)))
 
     def stereo_from_rgbd_device(self, n_frames, d_kps, d_kps_un, d_n, capacity, d_depth, depth_is_u16, rows, cols, depth_map_factor, mbf,
                                 d_u_right, d_depth_out, depth_stride_bytes=None, depth_frame_stride_bytes=None):

@@ -434,6 +434,50 @@ int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first
                                        const uint8_t* d_kf_mp_flags, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
                                        int capacity, float nn_ratio, int th_low, int check_orientation, int* d_matches, int* d_n_matches);
 
+/* ---- the mapping thread's matcher: ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) -----------
+ * (src/ORBmatcher.cc:965-1206; LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:456-463, once per neighbour keyframe; src/Tracking.cc:3702-3706)
+ * for keyframes with NLeft == -1 and no mpCamera2 on either side (monocular, rectified stereo, RGB-D) and the Pinhole model
+ * (Pinhole::epipolarConstrain, src/CameraModels/Pinhole.cpp:122-144).  NOT covered: the two-camera branches (:994-1004, :1099-1129;
+ * KannalaBrandt8) and the second overload (:1208-1397, matchAndtriangulate), which nothing in the reference calls.
+ * Pair p matches keyframe 1 = frame kf1_first + p*kf1_step against keyframe 2 = frame kf2_first + p*kf2_step of one device-resident batch;
+ * kf1_step = 0 is LocalMapping's shape (one new keyframe against its neighbours), kf2_step = 0 is allowed as well.
+ *   d_feat_nodes, d_feat_idx, d_n_feat : mFeatVec of all frames as written by orbx_compute_bow_device (same capacity)
+ *   d_kf1_mp_flags / d_kf2_mp_flags[p*capacity + i] : bit 0 = GetMapPoint(i) of keyframe 1 / 2 of pair p is not NULL (:1033-1039, :1064-1068:
+ *                 the pointer test alone, there is no isBad() here, unlike the SearchByBoW flags)
+ *   d_kps_un[f*capacity + i]  : mvKeysUn of all frames (orbx_frame_finish_device); .pt, .octave and .angle are read
+ *   d_u_right[f*capacity + i] : mvuRight of all frames (orbx_stereo_match_device / orbx_stereo_from_rgbd_device), >= 0 = stereo; NULL = no
+ *                 feature is stereo (monocular)
+ *   d_desc, d_n_out           : mDescriptors, N of all frames
+ *   d_f12[p*9]                : F12 of pair p, row-major binary32, = K1^-T [t12]x R12 K2^-1 as Pinhole.cpp:124-127 builds it (the reference
+ *                 ignores the F12 argument it is handed and rebuilds the matrix per candidate; its cv::Mat rounding is the caller's)
+ *   d_epipole[p*2]            : ep of pair p (:972-977: keyframe 1's camera centre projected into keyframe 2)
+ *   only_stereo = bOnlyStereo, coarse = bCoarse, th_low = ORBmatcher::TH_LOW (50), check_orientation = mbCheckOrientation
+ *   d_matches12[p*capacity + i] : out, vMatches12: the keypoint of keyframe 2 chosen for keypoint i of keyframe 1, -1 = none; all capacity
+ *                 entries are written
+ *   d_pairs[(p*capacity + k)*2 + {0, 1}] : out, vMatchedPairs: entry k < d_n_matches[p] is (i, d_matches12[i]) in increasing i; entries from
+ *                 d_n_matches[p] on are left as they were
+ *   d_n_matches[p]            : out, the return value
+ * As the reference: inside a node both FeatureVectors hold, every keyframe-1 feature without a MapPoint (and, under only_stereo, with
+ * mvuRight >= 0) scans keyframe 2's features of the node in list order; a candidate is dropped if it holds a MapPoint, by the stereo filter,
+ * if dist > th_low, if neither feature is stereo and it lies in the epipole's disc (distex^2 + distey^2 < 100 * mvScaleFactors[octave],
+ * :1089-1097), and if it fails dsqr < 3.84 * mvLevelSigma2[octave] (binary32 up to dsqr, every operation rounded on its own, the compare
+ * in double) unless coarse.  vbMatched2 is tested (:1067) but never set in this function, so a keyframe-1 feature never closes a candidate for
+ * another: SEVERAL keyframe-1 features may choose the same keyframe-2 keypoint.  bestDist starts AT th_low and an equal distance replaces
+ * the holder (:1057, :1080): of the passing candidates the smallest distance wins and of equal smallest distances the LAST in list order
+ * (the opposite of SearchByBoW).  Rotation histogram and ComputeThreeMaxima as there (:1147-1157, :1174-1193).
+ * The scale tables are the handle's (orbx_get_tables).  An octave outside [0, nlevels) is CLAMPED into the tables (the reference would
+ * index past them).  Supported: the tables of a pair live in LDS,
+ *   28 * ((capacity + 15) & ~15) + 64 <= 163 328 bytes      (capacity <= 5824)
+ * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched.  While 60 * ((capacity + 15) & ~15) + 64 <= 163 328
+ * (capacity <= 2720; orbx_max_keypoints() of a 2000-feature extractor is inside) keyframe 2's descriptors are staged in LDS as well; above,
+ * they are read from L2.  Asynchronous on the handle's stream. */
+int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
+                                         const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat,
+                                         const uint8_t* d_kf1_mp_flags, const uint8_t* d_kf2_mp_flags, const orbx_keypoint* d_kps_un,
+                                         const float* d_u_right, const uint8_t* d_desc, const int* d_n_out, int capacity, const float* d_f12,
+                                         const float* d_epipole, int only_stereo, int coarse, int th_low, int check_orientation,
+                                         int* d_matches12, int* d_pairs, int* d_n_matches);
+
 /* Stream control.  By default the handle owns a stream; orbx_set_stream adopts a caller stream
  * (hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream) so the caller's events
  * and graphs see the work. */

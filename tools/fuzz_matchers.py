@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Seeded soak of the matcher rows on the GPU box: the parity tests of tests/test_search_projection.py, tests/test_search_bow.py,
-tests/test_search_init.py and tests/test_stereo.py bodies re-run with seeds outside the committed parametrisation.
+tests/test_search_init.py, tests/test_stereo.py and tests/test_search_triangulation.py bodies re-run with seeds outside the committed parametrisation.
 usage: fuzz_matchers.py [n_seeds] [first_seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +13,7 @@ n, s0 = (int(sys.argv[1]) if len(sys.argv) > 1 else 20), (int(sys.argv[2]) if le
 import test_search_projection as P
 import test_search_bow as W
 import test_search_init as I
+import test_search_triangulation as T
 from extractorb_amd import synth
 t0 = time.time()
 done = 0
@@ -31,5 +32,8 @@ for k in range(n):
         frames = synth.frames(["textured", "noise", "sparse", "natural"][int(rng.integers(0, 4))], seed, 6, 480, 640)
         I.run_gpu_pairs(frames, ((0, 1), (1, 1), 5), I.PINHOLE, int(rng.choice([300, 1000, 2000, 5000])), int(rng.choice([30, 100, 300])),
                         float(rng.choice([0.6, 0.9, 1.3])), bool(rng.integers(0, 2)), rounds=int(rng.integers(1, 3)))
+    trng = np.random.default_rng(seed + 77)      # (a generator of its own: the draws of the cases above stay what they were)
+    T.check_gpu_on_seed(seed, only_stereo=bool(trng.random() < 0.2), coarse=bool(trng.integers(0, 2)), th_low=int(trng.choice([50, 100])),
+                        check_orientation=bool(trng.integers(0, 2)))
     done += 1
-print("matcher soak: %d seeds x 4 matcher parity bodies (+ SearchForInitialization every fifth seed) bit-exact, %.0f s" % (done, time.time() - t0))
+print("matcher soak: %d seeds x 5 matcher parity bodies (+ SearchForInitialization every fifth seed) bit-exact, %.0f s" % (done, time.time() - t0))
