@@ -10,6 +10,11 @@ namespace {
 // rows covered by one right keypoint's band [floor(y - 2s), ceil(y + 2s)], s = the coarsest level's scale
 int bandRows(const orbx_handle* h) { return 2 * (int)std::ceil(2.0 * h->tabs.scale[h->nlevels - 1]) + 2; }
 
+// k_stereo_filter holds one int per slot of the capacity in dynamic LDS (whole int4s) beside its static block; include/orbx.h documents the bound
+size_t stereoFilterLdsBytes(int capacity) { return 4 * (((size_t)capacity + 3) & ~(size_t)3) + ORBX_STEREO_FILTER_STATIC_LDS_BYTES; }
+bool stereoCapacityFits(int capacity) { return capacity <= 65535 && stereoFilterLdsBytes(capacity) <= 160 * 1024 - 512; }
+constexpr const char* kStereoCapacityMsg = "capacity too large for the LDS-resident median filter (4 bytes per slot of the capacity, 160 KB per CU)";
+
 int stereoEnsure(orbx_handle* h, int nPairs, int capacity, int rows) {
     if (nPairs <= h->stereoPairs && capacity <= h->stereoCap && rows <= h->stereoRows) return ORBX_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -34,7 +39,7 @@ int stereoEnqueue(orbx_handle* h, int n_pairs, const Keypoint* d_kps, const uint
     if (h->geom.nlevels == 0 || 2 * n_pairs > h->lastB || n_pairs < 1)
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "stereo matching needs the 2*n_pairs frames of the last extract batch on this handle");
     if (!(b > 0.f) || !(bf > 0.f)) return fail(h, ORBX_ERR_BAD_ARGUMENT, "bf and b must be positive");
-    if (capacity > 65535) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity above 65535 keypoints per eye");
+    if (!stereoCapacityFits(capacity)) return fail(h, ORBX_ERR_UNSUPPORTED, kStereoCapacityMsg);      // before any launch or allocation
     HIP_TRY(h, hipSetDevice(h->device));
     const int rows = h->geom.rows;
     int rc = stereoEnsure(h, n_pairs, capacity, rows);
@@ -71,6 +76,7 @@ int orbx_stereo_match_last(orbx_handle* h, int n_pairs, float bf, float b, float
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "orbx_stereo_match_last needs the 2*n_pairs frames of the last orbx_extract_batch call on this handle "
                                               "(after orbx_extract_batch_device use orbx_stereo_match_device)");
     const int cap = h->outCap;
+    if (!stereoCapacityFits(cap)) return fail(h, ORBX_ERR_UNSUPPORTED, kStereoCapacityMsg);
     for (int p = 0; p < n_pairs; p++) {     // counts of the left eyes, copied to the host by that call
         const int n = h->host.n[2 * p];
         if (n < 0 || n > cap) return fail(h, ORBX_ERR_HIP, "corrupt keypoint count in the handle's staging (internal)");

@@ -186,7 +186,12 @@ int orbx_fetch_pyramid(orbx_handle* h, int frame, const uint8_t** base, size_t* 
  *   n_matched[p] : matches that survive the median filter
  * orbx_stereo_match_device takes the device buffers an orbx_extract_batch_device call filled (and is asynchronous
  * on the handle's stream); orbx_stereo_match_last uses the results of the last orbx_extract_batch call, which the
- * handle keeps in HBM, and returns host arrays. */
+ * handle keeps in HBM, and returns host arrays.
+ * The median filter keeps one pair's SAD distances in the LDS of one CU: 4 * ((capacity + 3) & ~3) bytes beside
+ * ORBX_STEREO_FILTER_STATIC_LDS_BYTES of its own.  A capacity (for _last: the handle's orbx_max_keypoints()) with
+ *   4 * ((capacity + 3) & ~3) + ORBX_STEREO_FILTER_STATIC_LDS_BYTES > 160 * 1024 - 512      (capacity > 40568)
+ * is refused with ORBX_ERR_UNSUPPORTED before anything is launched or allocated. */
+#define ORBX_STEREO_FILTER_STATIC_LDS_BYTES 1056
 int orbx_stereo_match_device(orbx_handle* h, int n_pairs, const orbx_keypoint* d_kps, const uint8_t* d_desc,
                              const int* d_n_out, int capacity, float bf, float b, float* d_u_right, float* d_depth,
                              int* d_n_matched);
