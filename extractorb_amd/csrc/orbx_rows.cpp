@@ -224,9 +224,7 @@ int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame
         window_size < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, negative frame index/step/window or empty bounds");
     if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity above 32767 keypoints per frame");
-    const int slotCap = initMatchSlotCapacity(capacity);
-    if (slotCap < 64)
-        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident search (4 bytes per keypoint + 52 per level-0 keypoint of frame 2, 160 KB per CU)");
+    const int slotCap = initMatchSlotCapacity(capacity);      // >= capacity or 2456: any capacity up to 32767 has a table (include/orbx.h)
     HIP_TRY(h, hipSetDevice(h->device));
     InitMatchParams p;
     p.minX = bounds4[0]; p.minY = bounds4[2];

@@ -259,9 +259,12 @@ int orbx_frame_finish_two_eyes_device(orbx_handle* h, int n_pairs, const orbx_ke
  *                                      with F1.mvKeysUn[i].pt; matched entries become F2.mvKeysUn[match].pt, :815-817)
  *   d_matches12[p*capacity + i]      : vnMatches12, -1 = unmatched;  d_n_matches[p] : the return value
  * Frames of the initialisation extractor (ORBextractor(5 * nFeatures), src/Tracking.cc:774: capacity 5000 .. 10 000) are supported: only the
- * level-0 keypoints of F2 are candidates (:722-726) and only they are staged on chip (52 B each next to 4 B per keypoint of F1 in 160 KB of
- * LDS).  Should F2 hold more level-0 keypoints than fit (a one-level pyramid with thousands of features), the pair reports
- * d_n_matches[p] = -1 and an all -1 table.  Asynchronous on the handle's stream. */
+ * level-0 keypoints take part (:722-726: those of F1 ask, those of F2 inside the grid are candidates) and only they are kept on chip.  One
+ * workgroup's table has as many entries for F1 as for F2 and takes 66 B per entry pair (56 B per level-0 keypoint of F2: descriptor, position,
+ * cell, index, holder list; 10 B per level-0 keypoint of F1: index, two decision words) plus 608 B, in 160 KiB - 1 KiB of LDS:
+ * (capacity + 3) & ~3 entries while that fits (capacity <= 2457), 2456 entries for every larger capacity.  The number bounds the level-0
+ * keypoints of either frame: should F1 or F2 hold more (a one-level pyramid with thousands of features), the pair reports d_n_matches[p] = -1
+ * and an all -1 table and leaves d_prev_matched as it was; the other pairs of the call are not affected.  Asynchronous on the handle's stream. */
 int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame1_first, int frame1_step, int frame2_first,
                                           int frame2_step, const orbx_keypoint* d_kps_un, const uint8_t* d_desc,
                                           const int* d_n_out, int capacity, const int* d_grid_off, const int* d_grid_idx,

@@ -7,6 +7,7 @@ import pytest
 import oracle_lib as O
 import extractorb_amd as X
 from extractorb_amd import synth
+from search_init_statement import brute_force_search      # the independent walk (tests/search_init_statement.py)
 
 PINHOLE = dict(fx=500.0, fy=500.0, cx=320.0, cy=240.0)
 EUROC = dict(fx=458.654, fy=457.296, cx=367.215, cy=248.375, k1=-0.28340811, k2=0.07395907, p1=0.00019359, p2=1.76187114e-05)
@@ -49,64 +50,6 @@ def test_oracle_features_in_area_is_a_box_query_in_grid_order():
         # traversal order is ascending grid position (cells x-major, push_back order inside)
         assert sorted(got.tolist()) == want
         assert [pos_in_grid[int(i)] for i in got] == sorted(pos_in_grid[int(i)] for i in got)
-
-
-def brute_force_search(k1, d1, k2, d2, inside2, grid_pos2, prev, window, nnratio, check):
-    """Independent restatement on plain Python containers: candidates by brute-force box test over the keypoints
-    that are in the grid, visited in grid order."""
-    n1 = len(k1)
-    m12 = [-1] * n1; m21 = {}; mdist = {}
-    hist = [[] for _ in range(30)]
-    cand_all = sorted((i for i in range(len(k2)) if inside2[i] and k2["octave"][i] == 0), key=lambda i: grid_pos2[i])
-    pc = np.unpackbits(d2, axis=1)
-    nm = 0
-    for i1 in range(n1):
-        if k1["octave"][i1] > 0:
-            continue
-        x, y = np.float32(prev[i1][0]), np.float32(prev[i1][1])
-        best, best2, bi = 1 << 30, 1 << 30, -1
-        b1 = np.unpackbits(d1[i1])
-        for i2 in cand_all:
-            if not (abs(k2["x"][i2] - x) < window and abs(k2["y"][i2] - y) < window):
-                continue
-            dist = int((b1 != pc[i2]).sum())
-            if mdist.get(i2, 1 << 30) <= dist:
-                continue
-            if dist < best:
-                best2, best, bi = best, dist, i2
-            elif dist < best2:
-                best2 = dist
-        if best <= 50 and best < np.float32(best2 if best2 < (1 << 30) else 2 ** 31) * np.float32(nnratio):
-            if bi in m21:
-                m12[m21[bi]] = -1; nm -= 1
-            m12[i1] = bi; m21[bi] = i1; mdist[bi] = best; nm += 1
-            if check:
-                rot = np.float32(k1["angle"][i1]) - np.float32(k2["angle"][bi])
-                if rot < 0:
-                    rot = np.float32(rot + np.float32(360))
-                v = float(np.float32(rot * np.float32(1.0 / 30)))
-                b = int(np.floor(v + 0.5))
-                hist[0 if b == 30 else b].append(i1)
-    if check:
-        sizes = [len(h) for h in hist]
-        order = sorted(range(30), key=lambda i: (-sizes[i], i))
-        top = [order[0] if sizes[order[0]] > 0 else -1]
-        mx = sizes[order[0]]
-        for o in order[1:3]:
-            top.append(o if sizes[o] > 0 and not sizes[o] < np.float32(0.1) * np.float32(mx) else -1)
-        if top[1] == -1:
-            top[2] = -1
-        for b in range(30):
-            if b in top:
-                continue
-            for i1 in hist[b]:
-                if m12[i1] >= 0:
-                    m12[i1] = -1; nm -= 1
-    prev = np.array(prev, np.float32).copy()
-    for i1 in range(n1):
-        if m12[i1] >= 0:
-            prev[i1] = (k2["x"][m12[i1]], k2["y"][m12[i1]])
-    return nm, m12, prev
 
 
 def make_descriptor_pair(rng, k1, n2, flip_bits=12):
