@@ -36,6 +36,13 @@ struct TriMatchParams {      // == k_triangulate_match.hip
 };
 size_t triMatchLdsBytes(int capacity, bool stage);
 void launchSearchTriangulation(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const float*, const uint8_t*, const int*, const float*, const float*, const TriMatchParams&, bool, int*, int*, int*, int);
+struct FuseParams {      // == k_fuse.hip
+    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
+    float scale[kMaxLevels], invSigma2[kMaxLevels], breaks[kMaxLevels];
+    float mbf, th;
+    int nlevels, thLow, reprojCheck, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
+};
+void launchFuse(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const float*, const uint8_t*, const int*, const int*, const int*, const FuseParams&, int*, int*, uint8_t*, int*, int);
 void launchLdsPollute(hipStream_t, int, int, unsigned*);
 void launchPyrCols(hipStream_t, const uint8_t*, long long, long long, int, const PyrColumn*, int, const ColLevels*, int, const ResizeX*, int, uint8_t*, int, int, bool, int, int, int);
 void launchBlur(hipStream_t, const BlurItem*, const unsigned short*, int, int, const LevelGeom*, const uint8_t*, uint8_t*, int, int);
@@ -242,6 +249,9 @@ struct orbx_handle {
     size_t bowEntries = 0;
     uint32_t *d_bowWord = nullptr, *d_bowNode = nullptr;
     double* d_bowWeight = nullptr;
+    // MapPoint::PredictScale's breakpoints for (scaleFactor, nlevels) (orbx_fuse_device computes them on its first call)
+    float scaleBreaks[kMaxLevels] = {};
+    bool scaleBreaksReady = false;
     // stereo matching (allocated on first use)
     int stereoPairs = 0, stereoCap = 0, stereoRows = 0;
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;

@@ -562,4 +562,47 @@ int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_fi
     return ORBX_OK;
 }
 
+int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step, const float* d_mp_world,
+                     const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc, const int* d_n_mp, int mp_capacity,
+                     const uint8_t* d_mp_flags, const float* d_poses, const orbx_keypoint* d_kps_un, const float* d_u_right,
+                     const uint8_t* d_desc, const int* d_n_out, int capacity, const int* d_grid_off, const int* d_grid_idx,
+                     const float* bounds4, const orbx_camera* cam, int nlevels, float mbf, float th, int th_low, int reproj_check,
+                     int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !d_kps_un || !d_desc || !d_n_out || !d_grid_off ||
+        !d_grid_idx || !bounds4 || !cam || !d_best_idx || !d_best_dist || !d_n_fused || capacity < 1 || mp_capacity < 1 || n_pairs < 1 ||
+        n_pairs > 65535 || kf_first < 0 || mp_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
+        mp_first + (long long)(n_pairs - 1) * mp_step < 0 || th_low < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/mp_capacity/n_pairs < 1, more than 65535 pairs, a negative keyframe or list "
+                                              "index, negative th_low or empty bounds");
+    if (nlevels != h->nlevels)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
+    if (!h->scaleBreaksReady) {
+        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
+            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
+        h->scaleBreaksReady = true;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    FuseParams p{};
+    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
+    // KeyFrame's mnMinX .. mnMaxY are const int (inc/KeyFrame.h:484) initialised from Frame's floats (KeyFrame.cc:58): truncated toward zero.
+    // IsInImage (:816-819) and GetFeaturesInArea (:778-790) compare with and subtract the truncated values ...
+    p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
+    // ... but scale by Frame's inverses, made from the untruncated floats and copied as they are (Frame.cc:339-340, KeyFrame.cc:50)
+    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv
+    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv
+    for (int l = 0; l < h->nlevels; l++) { p.scale[l] = h->tabs.scale[l]; p.invSigma2[l] = h->tabs.invSigma2[l]; }
+    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    p.mbf = mbf; p.th = th; p.nlevels = h->nlevels; p.thLow = th_low < 255 ? th_low : 255; p.reprojCheck = reproj_check ? 1 : 0;
+    p.capacity = capacity; p.mpCapacity = mp_capacity; p.kfFirst = kf_first; p.kfStep = kf_step; p.mpFirst = mp_first; p.mpStep = mp_step;
+    {
+        Prof pr(h, S_FRAME);
+        HIP_TRY(h, hipMemsetAsync(d_n_fused, 0, sizeof(int) * (size_t)n_pairs, h->stream));
+        launchFuse(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps_un, d_u_right, d_desc,
+                   d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"

@@ -171,6 +171,10 @@ def load_library():
                                                      C.c_float, C.c_int, C.c_int, vp, vp]
     L.orbx_search_for_triangulation_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                        C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.orbx_fuse_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int,
+                                   vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.orbx_predict_scale.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int]
+    L.orbx_predict_scale_breakpoints.argtypes = [C.c_float, C.c_int, vp]
     L.orbx_stereo_match_last.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, vp, C.c_int, vp]
     L.orbx_compute_image_bounds.argtypes = [vp, C.c_int, C.c_int, vp]
     L.orbx_frame_finish_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -270,6 +274,23 @@ def pinned_empty(shape, dtype=np.uint8):
 
 def pinned_free(arr):
     load_library().orbx_host_free(C.c_void_p(arr.ctypes.data))
+
+
+def predict_scale(max_distance, dist, scale_factor=1.2, nlevels=8):
+    """MapPoint::PredictScale (reference src/MapPoint.cc:514-529) through the host libm.  Host only."""
+    rc = load_library().orbx_predict_scale(max_distance, dist, scale_factor, nlevels)
+    if rc < 0:
+        raise OrbxError(rc, "orbx_predict_scale")
+    return rc
+
+
+def predict_scale_breakpoints(scale_factor=1.2, nlevels=8):
+    """The nlevels - 1 ratios at which MapPoint::PredictScale steps: the level of a ratio is the number of breakpoints <= ratio.  Host only."""
+    b = np.zeros(max(nlevels - 1, 0), np.float32)
+    rc = load_library().orbx_predict_scale_breakpoints(scale_factor, nlevels, _ptr(b))
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_predict_scale_breakpoints")
+    return b
 
 
 def camera(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
@@ -564,6 +585,22 @@ class ORBextractor:
             self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], dp(d_feat_nodes), dp(d_feat_idx), dp(d_n_feat), dp(d_kf1_mp_flags),
             dp(d_kf2_mp_flags), dp(d_kps_un), dp(d_u_right), dp(d_desc), dp(d_n), capacity, dp(d_f12), dp(d_epipole), int(only_stereo),
             int(coarse), th_low, int(check_orientation), dp(d_matches12), dp(d_pairs), dp(d_n_matches)))
+
+    def fuse_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags, d_poses, d_kps_un,
+                    d_u_right, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, mbf, d_best_idx, d_best_dist, d_exit, d_n_fused,
+                    th=3.0, th_low=50, reproj_check=True, nlevels=None):
+        """The search half of ORBmatcher::Fuse (reference src/ORBmatcher.cc:1399-1609; reproj_check=False: the Sim3 overload, :1611-1733) for
+        one-camera keyframes with the Pinhole model; kf and mp = (first, step) of the keyframe / MapPoint list of pair p, mp step 0 = one list
+        into many keyframes.  d_n_mp, d_u_right and d_exit may be None.  The caller replays the map-changing tail on the host in list order."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
+        cam = None if cam is None else np.ascontiguousarray(cam, np.float32)
+        self._check(self._L.orbx_fuse_device(
+            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_n_mp), mp_capacity,
+            dp(d_mp_flags), dp(d_poses), dp(d_kps_un), dp(d_u_right), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds),
+            _ptr(cam), self.nlevels if nlevels is None else nlevels, mbf, th, th_low, int(reproj_check), dp(d_best_idx), dp(d_best_dist),
+            dp(d_exit), dp(d_n_fused)))
 
     def stereo_from_rgbd_device(self, n_frames, d_kps, d_kps_un, d_n, capacity, d_depth, depth_is_u16, rows, cols, depth_map_factor, mbf,
                                 d_u_right, d_depth_out, depth_stride_bytes=None, depth_frame_stride_bytes=None):

@@ -486,6 +486,92 @@ int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_fi
                                          const float* d_epipole, int only_stereo, int coarse, int th_low, int check_orientation,
                                          int* d_matches12, int* d_pairs, int* d_n_matches);
 
+/* ---- the mapping thread's second matcher: the search half of ORBmatcher::Fuse (LocalMapping::SearchInNeighbors, src/LocalMapping.cc:729-837) ----
+ * MapPoint::PredictScale(currentDist, pKF) (src/MapPoint.cc:514-529) on the host, through the host libm:
+ *   ratio = max_distance / dist;  ceil(log(ratio) / mfLogScaleFactor) clamped to [0, nlevels - 1]
+ * with log, / and ceil in binary32 (`using namespace std` is in scope there) and mfLogScaleFactor = log(scale_factor) in binary32
+ * (src/Frame.cc:99).  Where the reference is undefined (the int conversion of +inf / NaN): a ratio of +inf gives nlevels - 1, NaN (and a negative
+ * ratio) gives 0; a ratio of 0 gives 0.  Returns the level, or ORBX_ERR_BAD_ARGUMENT (nlevels < 1, scale_factor not a finite number above 1). */
+int orbx_predict_scale(float max_distance, float dist, float scale_factor, int nlevels);
+/* The same as a table: as a function of ratio the expression is a monotone step function with nlevels - 1 steps;
+ *   breakpoints[k - 1] (k = 1 .. nlevels - 1) = the smallest positive float r with ceil(logf(r) / logf(scale_factor)) >= k,
+ * found by bisection over float bit patterns with the expression itself (the steps sit a few ulp above scale_factor^k - 1.20000017,
+ * 1.44000018 for 1.2 - a table of powers would be wrong).  The predicted level of `ratio` is the number of breakpoints <= ratio (+inf: all,
+ * NaN: none).  Host-only, no GPU touched.  breakpoints may be NULL when nlevels == 1. */
+int orbx_predict_scale_breakpoints(float scale_factor, int nlevels, float* breakpoints /* nlevels - 1 */);
+
+/* Where a MapPoint left Fuse (d_exit of orbx_fuse_device): the reference's own count_* names at src/ORBmatcher.cc:1430 */
+enum orbx_fuse_exit {
+    ORBX_FUSE_FLAG = 0,           /* count_notMP / count_bad / count_isinKF: bit 0 of its flag is clear (or it lies beyond d_n_mp) */
+    ORBX_FUSE_NEG_DEPTH = 1,      /* count_negdepth (:1459) */
+    ORBX_FUSE_NOT_IN_IMAGE = 2,   /* count_notinim (:1473) */
+    ORBX_FUSE_DISTANCE = 3,       /* count_dist (:1487) */
+    ORBX_FUSE_NORMAL = 4,         /* count_normal (:1496) */
+    ORBX_FUSE_EMPTY_WINDOW = 5,   /* count_notidx (:1509): GetFeaturesInArea returned nothing */
+    ORBX_FUSE_ABOVE_TH_LOW = 6,   /* count_thcheck (:1594): no candidate passed, or the best distance is above th_low */
+    ORBX_FUSE_FUSED = 7           /* nFused++ (:1591) */
+};
+
+/* ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th, bRight = false) (src/ORBmatcher.cc:1399-1609; reproj_check = 1) and
+ * the loop-closing overload Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1611-1733; reproj_check = 0: the same search without the
+ * reprojection test of :1533-1557), for keyframes with NLeft == -1 and the Pinhole model (monocular, rectified stereo, RGB-D).  NOT covered:
+ * bRight = true and NLeft != -1 (:1404-1410, :1524-1526, :1559: mpCamera2, the KannalaBrandt8 pair).
+ * THE SEARCH HALF ONLY.  Everything up to bestIdx / bestDist (:1455-1570, :1643-1712) reads the MapPoint's position, normal, distance bounds and
+ * descriptor and the keyframe's pose, keypoints, grid, mvuRight and descriptors; only the tail (:1573-1592, :1715-1729: Replace /
+ * AddObservation / AddMapPoint) touches the map, and it closes no keypoint for later MapPoints.  So all MapPoints of all keyframes are searched
+ * in one launch, and the CALLER replays the tail on the host, keyframe by keyframe and in list order, re-testing isBad() and IsInKeyFrame(pKF)
+ * at replay time (an earlier Replace may have changed them): INTEGRATION.md, "SearchInNeighbors".
+ * WHERE THAT IS EXACT.  A call with ONE keyframe (n_pairs = 1: SearchInNeighbors' second half, LoopClosing's Fuse) plus the replay is the
+ * reference's Fuse: the MapPoint that survives a Replace is in pKF afterwards and is not searched there again.  A call with SEVERAL keyframes
+ * and one list (mp_step = 0) is exact for every list entry whose descriptor is still the uploaded one when the replay reaches the keyframe:
+ * MapPoint::Replace ends with ComputeDistinctiveDescriptors() on the survivor (src/MapPoint.cc:296-298, :330-403), which may rewrite
+ * mDescriptor, and the reference searches that entry in the LATER keyframes with the new descriptor (GetDescriptor(), :1517).  Position, normal
+ * and distances are not touched by Replace.  So before replaying keyframe p the caller compares GetDescriptor() of the list entries that
+ * survived a Replace in keyframes 0 .. p-1 with what it uploaded, and searches the changed ones again in keyframe p (one more call with
+ * n_pairs = 1 and bit 0 set for them alone); with that the sequence is the reference's.  INTEGRATION.md shows the loop, and
+ * tests/test_fuse.py holds it against the sequential Fuse on a map model with descriptors.
+ * Pair p fuses MapPoint list mp_first + p*mp_step into keyframe kf_first + p*kf_step of one device-resident batch: mp_step = 0 is
+ * SearchInNeighbors' first half (the current keyframe's MapPoints into every neighbour), n_pairs = 1 with a long list its second half;
+ * kf_step = 0 is allowed as well.
+ *   per MapPoint, in blocks of mp_capacity per list (m = list*mp_capacity + i):
+ *   d_mp_world[m*3], d_mp_normal[m*3] : GetWorldPos(), GetNormal()
+ *   d_mp_dist[m*3]             : GetMinDistanceInvariance(), GetMaxDistanceInvariance() (0.8f * mfMinDistance, 1.2f * mfMaxDistance: the bounds of
+ *                 :1487) and mfMaxDistance ITSELF, which PredictScale divides (src/MapPoint.cc:519; dividing the second by 1.2f is not bit-exact)
+ *   d_mp_desc[m*32]            : GetDescriptor() (16-byte aligned, as d_desc)
+ *   d_n_mp[list]               : MapPoints of the list, NULL = mp_capacity
+ *   d_mp_flags[p*mp_capacity + i] : per PAIR; bit 0 = pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF) (:1435-1452); for reproj_check = 0
+ *                 bit 0 = !pMP->isBad() && !spAlreadyFound.count(pMP) (:1639)
+ *   d_poses[f*12]              : rows 0..2 of the keyframe's Tcw (3x4, row-major: Rcw | tcw) of every frame, as orbx_project_last_frame_device
+ *                 takes them; for reproj_check = 0 the caller's sRcw/scw | tcw/scw (:1620-1623).  Ow = -Rcw.t()*tcw is computed here.
+ *   d_kps_un, d_desc, d_n_out, d_grid_off, d_grid_idx : mvKeysUn, mDescriptors, N, mGrid of all frames (orbx_frame_finish_device)
+ *   bounds4                    : Frame's FLOAT mnMinX, mnMaxX, mnMinY, mnMaxY (orbx_compute_image_bounds), the ones the grid was built with.  KeyFrame's
+ *                 own mnMinX .. mnMaxY are const int (inc/KeyFrame.h:484) initialised from them (src/KeyFrame.cc:58), so truncated toward zero,
+ *                 while its mfGridElementWidthInv / HeightInv are copies of Frame's, made from the floats (:50).  The entry does the same:
+ *                 IsInImage and the window subtract (float)(int)bounds4[i], the window scales by 64 / (bounds4[1] - bounds4[0]) and
+ *                 48 / (bounds4[3] - bounds4[2]).  With a distorted camera the bounds are no integers and the two differ near the edge.
+ *   d_u_right[f*capacity + i]  : mvuRight of all frames, NULL = monocular (all -1)
+ *   cam (fx, fy, cx, cy), mbf  : Pinhole::project, pKF->mbf;  th : 3.0 at both callers;  th_low : ORBmatcher::TH_LOW (50), above 255 taken as 255
+ *   nlevels                    : pKF->mnScaleLevels; must equal orbx_get_levels(h) - mvScaleFactors, mvInvLevelSigma2 and PredictScale's
+ *                 breakpoints are the handle's (orbx_get_tables, orbx_predict_scale_breakpoints); else ORBX_ERR_BAD_ARGUMENT
+ *   d_best_idx[p*mp_capacity + i]  : out, bestIdx, the keyframe's keypoint, if bestDist <= th_low; else -1
+ *   d_best_dist[p*mp_capacity + i] : out, bestDist; 256 where no candidate passed (in both modes; :1693 starts at INT_MAX)
+ *   d_exit[p*mp_capacity + i]      : out or NULL, an orbx_fuse_exit
+ *   d_n_fused[p]                   : out, the return value under the flags as passed (the number of ORBX_FUSE_FUSED)
+ * All mp_capacity entries of every pair are written.  Arithmetic as the reference's x86-64 build, every operation rounded on its own:
+ * p3Dc and Ow as cv::gemm (products and sums in double, one rounding to float), z < 0.0f rejected (z == 0 leaves by IsInImage), invz a FLOAT
+ * division (:1465), IsInImage with strict upper bounds on the truncated bounds (src/KeyFrame.cc:816-819), dist3D = (float)sqrt of squares summed in double, PO.dot(Pn) in
+ * double against 0.5 * (double)dist3D, KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:770-814: NOT Frame's - no level filter, four early
+ * returns, fabs(dx) < r && fabs(dy) < r, ix outer / iy inner / push order = the CSR order of d_grid_idx), kpLevel in [level - 1, level],
+ * (float)(e2 * invSigma2) promoted and compared with 7.8 (mvuRight >= 0) / 5.99, DescriptorDistance with strict <: of equal distances the
+ * FIRST in visit order wins.  A keypoint octave of -1 that passes the level filter (level 0) is CLAMPED into the table (the reference would
+ * index past it).  No table lives in LDS: there is no capacity bound and no ORBX_ERR_UNSUPPORTED case.  Asynchronous on the handle's stream. */
+int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step, const float* d_mp_world,
+                     const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc, const int* d_n_mp, int mp_capacity,
+                     const uint8_t* d_mp_flags, const float* d_poses, const orbx_keypoint* d_kps_un, const float* d_u_right,
+                     const uint8_t* d_desc, const int* d_n_out, int capacity, const int* d_grid_off, const int* d_grid_idx,
+                     const float* bounds4, const orbx_camera* cam, int nlevels, float mbf, float th, int th_low, int reproj_check,
+                     int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused);
+
 /* Stream control.  By default the handle owns a stream; orbx_set_stream adopts a caller stream
  * (hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream) so the caller's events
  * and graphs see the work. */
