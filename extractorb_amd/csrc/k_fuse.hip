@@ -20,12 +20,15 @@
 // PredictScale's ceil(log(ratio) / mfLogScaleFactor) is a monotone step function of ratio: the host finds the steps by bisection with the
 // same libm expression (orbx_predict_scale_breakpoints) and the level is the number of breakpoints <= ratio - no logarithm here.
 // Arithmetic: every operation rounded on its own (-ffp-contract=off and the __f*_rn / __d*_rn intrinsics), cv::Mat products as gemmRow.
+// The front end - pose, projection, IsInImage, distance and normal tests, PredictScale, the cell window (:1455-1509) - is projectIntoKeyFrame of
+// k_keyframe_project.hpp, shared with the Sim3 projection search (k_project_sim3.hip): one statement, two users.
 // This file is also compiled for the HOST by the CPU suite (tests/cpp/fuse_host_check.cpp includes it behind tests/cpp/host_shim/hip/
-// hip_runtime.h, a hand-written stand-in for the device vocabulary used here).  An intrinsic, builtin or vector type this kernel gains must
+// hip_runtime.h, a hand-written stand-in for the device vocabulary used here).  An intrinsic, builtin or vector type this kernel or that header gains must
 // get its stand-in there in the same change, or the CPU suite no longer builds; the wave-wide count into nFused is not emulated there.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_keyframe_project.hpp"
 #include "orbx_device.hpp"
 
 namespace orbx {
@@ -39,18 +42,8 @@ struct FuseParams {      // == orbx_internal.hpp
 };
 
 namespace {
-constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
+constexpr int kRows = kKfRows, kCells = kKfCells;
 enum { kExitFlag = 0, kExitNegDepth, kExitNotInImage, kExitDistance, kExitNormal, kExitEmptyWindow, kExitAboveThLow, kExitFused };      // == ORBX_FUSE_*
-
-// one row of cv::gemm on 3x3 * 3x1 float data: products and sums in double (each rounded), scaled, C added, rounded to float once
-__device__ __forceinline__ float gemmRow(float a0, float a1, float a2, const float (&b)[3], double alpha, float c, bool hasC) {
-    double s = __dmul_rn((double)a0, (double)b[0]);
-    s = __dadd_rn(s, __dmul_rn((double)a1, (double)b[1]));
-    s = __dadd_rn(s, __dmul_rn((double)a2, (double)b[2]));
-    s = __dmul_rn(s, alpha);
-    if (hasC) s = __dadd_rn(s, (double)c);
-    return (float)s;
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_fuse(const float* __restrict__ mpWorld, const float* __restrict__ mpNormal,
@@ -69,52 +62,17 @@ __global__ __launch_bounds__(256) void k_fuse(const float* __restrict__ mpWorld,
         const int NM = nMp ? min(max(nMp[list], 0), p.mpCapacity) : p.mpCapacity;
         do {
             if (i >= NM || !(mpFlags[o] & 1)) break;                                         // :1435-1452 / :1639
-            const float* T = poses + f * 12;
-            const float R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-            const float tcw[3] = {T[3], T[7], T[11]};
-            const float xw[3] = {mpWorld[3 * m], mpWorld[3 * m + 1], mpWorld[3 * m + 2]};
-            float xc[3];
-            for (int r = 0; r < 3; r++) xc[r] = gemmRow(R[3 * r], R[3 * r + 1], R[3 * r + 2], xw, 1.0, tcw[r], true);      // Rcw*p3Dw+tcw (:1456)
-            code = kExitNegDepth;
-            if (xc[2] < 0.0f) break;                                                         // :1459
-            const float invz = __fdiv_rn(1.0f, xc[2]);                                       // :1465, a float division
-            const float u = __fadd_rn(__fdiv_rn(__fmul_rn(p.fx, xc[0]), xc[2]), p.cx);       // Pinhole::project
-            const float v = __fadd_rn(__fdiv_rn(__fmul_rn(p.fy, xc[1]), xc[2]), p.cy);
-            code = kExitNotInImage;
-            if (!(u >= p.minX && u < p.maxX && v >= p.minY && v < p.maxY)) break;            // KeyFrame::IsInImage (z == 0: inf / NaN fail here)
-            const float ur = __fsub_rn(u, __fmul_rn(p.mbf, invz));                           // :1479
-            float Ow[3], PO[3];
-            for (int r = 0; r < 3; r++) Ow[r] = gemmRow(R[r], R[3 + r], R[6 + r], tcw, -1.0, 0.f, false);      // -Rcw.t()*tcw (KeyFrame.cc:118, :1624)
-            for (int r = 0; r < 3; r++) PO[r] = __fsub_rn(xw[r], Ow[r]);                     // :1483
-            // cv::norm of CV_32F: squares accumulated in double in element order, one square root, then float
-            const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)PO[0]), __dmul_rn((double)PO[1], (double)PO[1])),
-                                        __dmul_rn((double)PO[2], (double)PO[2]));
-            const float dist3D = (float)__dsqrt_rn(n2);
-            const float minDistance = mpDist[3 * m], maxDistance = mpDist[3 * m + 1];
-            code = kExitDistance;
-            if (dist3D < minDistance || dist3D > maxDistance) break;                         // :1487
-            const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)mpNormal[3 * m]), __dmul_rn((double)PO[1], (double)mpNormal[3 * m + 1])),
-                                         __dmul_rn((double)PO[2], (double)mpNormal[3 * m + 2]));
-            code = kExitNormal;
-            if (dot < __dmul_rn(0.5, (double)dist3D)) break;                                 // :1496
-            // MapPoint::PredictScale as a count of breakpoints (ascending; NaN is above none, +inf above all)
-            const float ratio = __fdiv_rn(mpDist[3 * m + 2], dist3D);                        // mfMaxDistance itself, not 1.2f * it (MapPoint.cc:519)
-            int level = 0;
-#pragma unroll
-            for (int k = 1; k < kMaxLevels; k++) level += k < p.nlevels && ratio >= p.breaks[k - 1] ? 1 : 0;
+            // the pose, the projection, IsInImage, the distance and normal tests, PredictScale and the cell window: k_keyframe_project.hpp,
+            // shared with the Sim3 projection search; its exits 1 .. 5 are kExitNegDepth .. kExitEmptyWindow
+            KfProjection q;
+            code = projectIntoKeyFrame(poses + f * 12, mpWorld + 3 * m, mpNormal + 3 * m, mpDist + 3 * m, p, kProjectPinhole, q);
+            if (code != kFrontPassed) break;
+            code = kExitEmptyWindow;
+            const float u = q.u, v = q.v, r = q.r;
+            const int level = q.level, minCX = q.minCX, maxCX = q.maxCX, minCY = q.minCY, maxCY = q.maxCY;
+            const float ur = __fsub_rn(u, __fmul_rn(p.mbf, q.invz));                         // :1479
             // a candidate's kpLevel is level or level - 1 (:1530): the two mvInvLevelSigma2 it can need
             const float invHi = p.invSigma2[level], invLo = p.invSigma2[max(level - 1, 0)];
-            const float r = __fmul_rn(p.th, p.scale[level]);                                 // :1505
-            // KeyFrame::GetFeaturesInArea's cell window with its four early returns (KeyFrame.cc:778-792)
-            code = kExitEmptyWindow;
-            const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, p.minX), r), p.wInv)));
-            if (minCX >= kCols) break;
-            const int maxCX = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, p.minX), r), p.wInv)));
-            if (maxCX < 0) break;
-            const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, p.minY), r), p.hInv)));
-            if (minCY >= kRows) break;
-            const int maxCY = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, p.minY), r), p.hInv)));
-            if (maxCY < 0) break;
             const int N = min(max(nOut[f], 0), p.capacity);
             const int* off = gridOff + f * (kCells + 1);
             const int* gi = gridIdx + f * p.capacity;

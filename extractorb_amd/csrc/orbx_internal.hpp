@@ -43,6 +43,15 @@ struct FuseParams {      // == k_fuse.hip
     int nlevels, thLow, reprojCheck, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
 };
 void launchFuse(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const float*, const uint8_t*, const int*, const int*, const int*, const FuseParams&, int*, int*, uint8_t*, int*, int);
+struct Sim3SearchParams {      // == k_project_sim3.hip
+    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
+    float scale[kMaxLevels], breaks[kMaxLevels];
+    float th;
+    int nlevels, maxDist, projection, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
+};
+size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
+size_t sim3RecordBytes();
+void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
 void launchLdsPollute(hipStream_t, int, int, unsigned*);
 void launchPyrCols(hipStream_t, const uint8_t*, long long, long long, int, const PyrColumn*, int, const ColLevels*, int, const ResizeX*, int, uint8_t*, int, int, bool, int, int, int);
 void launchBlur(hipStream_t, const BlurItem*, const unsigned short*, int, int, const LevelGeom*, const uint8_t*, uint8_t*, int, int);
@@ -252,6 +261,9 @@ struct orbx_handle {
     // MapPoint::PredictScale's breakpoints for (scaleFactor, nlevels) (orbx_fuse_device computes them on its first call)
     float scaleBreaks[kMaxLevels] = {};
     bool scaleBreaksReady = false;
+    // the Sim3 projection search's records (allocated on first use): the key list, the candidate count and the window of every (pair, MapPoint)
+    size_t sim3Entries = 0;
+    void* d_sim3Rec = nullptr;
     // stereo matching (allocated on first use)
     int stereoPairs = 0, stereoCap = 0, stereoRows = 0;
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;

@@ -605,4 +605,64 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
     return ORBX_OK;
 }
 
+int orbx_sim3_hamming_bound(int th_low, float ratio_hamming) {
+    const float product = (float)th_low * ratio_hamming;      // TH_LOW*ratioHamming (src/ORBmatcher.cc:577): int * float, a float
+    if (!(product >= 0.0f)) return -1;                        // negative or NaN: no int distance is <= it
+    return product >= 255.0f ? 255 : (int)floorf(product);    // the largest d with (float)d <= product, clamped to the largest distance
+}
+
+int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step,
+                                          const float* d_mp_world, const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc,
+                                          const int* d_n_mp, int mp_capacity, const uint8_t* d_mp_flags, const float* d_poses,
+                                          const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int* d_n_out, int capacity,
+                                          const int* d_grid_off, const int* d_grid_idx, const float* bounds4, const orbx_camera* cam, int nlevels,
+                                          int projection, float th, int th_low, float ratio_hamming, const uint8_t* d_occupied, int* d_matches,
+                                          int* d_match_idx, int* d_match_dist, uint8_t* d_exit, int* d_n_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !d_kps_un || !d_desc || !d_n_out || !d_grid_off ||
+        !d_grid_idx || !bounds4 || !cam || !d_matches || !d_match_idx || !d_match_dist || !d_n_matches || capacity < 1 || mp_capacity < 1 ||
+        n_pairs < 1 || n_pairs > 65535 || kf_first < 0 || mp_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
+        mp_first + (long long)(n_pairs - 1) * mp_step < 0 || th_low < 0 || (projection != 0 && projection != 1) || !(bounds4[1] > bounds4[0]) ||
+        !(bounds4[3] > bounds4[2]))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/mp_capacity/n_pairs < 1, more than 65535 pairs, a negative keyframe or list "
+                                              "index, negative th_low, a projection form other than 0 / 1 or empty bounds");
+    if (nlevels != h->nlevels)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
+    if (capacity > 65536 || sim3SettleLdsBytes(capacity, mp_capacity) > 160 * 1024 - 512)
+        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity / mp_capacity too large for the LDS-resident settling of the Sim3 projection search "
+                                             "(4 bytes per keypoint + 4 per MapPoint, + 64: 160 KB per CU; a key holds a 16-bit slot)");
+    if (!h->scaleBreaksReady) {
+        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
+            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
+        h->scaleBreaksReady = true;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t need = (size_t)n_pairs * mp_capacity;
+    if (need > h->sim3Entries) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_sim3Rec) (void)hipFree(h->d_sim3Rec);
+        h->d_sim3Rec = nullptr; h->sim3Entries = 0;
+        HIP_TRY(h, hipMalloc(&h->d_sim3Rec, need * sim3RecordBytes()));      // what k_sim3_window leaves for k_sim3_settle
+        h->sim3Entries = need;
+    }
+    Sim3SearchParams p{};
+    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
+    // KeyFrame's truncated bounds and Frame's untruncated inverses, as orbx_fuse_device
+    p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
+    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);
+    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);
+    for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
+    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    p.th = th; p.nlevels = h->nlevels; p.maxDist = orbx_sim3_hamming_bound(th_low, ratio_hamming); p.projection = projection;
+    p.capacity = capacity; p.mpCapacity = mp_capacity; p.kfFirst = kf_first; p.kfStep = kf_step; p.mpFirst = mp_first; p.mpStep = mp_step;
+    {
+        Prof pr(h, S_FRAME);
+        launchSim3Search(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps_un, d_desc,
+                         d_n_out, d_grid_off, d_grid_idx, d_occupied, p, h->d_sim3Rec, d_matches, d_match_idx, d_match_dist, d_exit,
+                         d_n_matches, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"

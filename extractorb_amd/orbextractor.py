@@ -173,6 +173,12 @@ def load_library():
                                                        C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.orbx_fuse_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int,
                                    vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
+                                                        vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
+                                                        vp, vp, vp, vp, vp]
+    L.orbx_sim3_hamming_bound.argtypes = [C.c_int, C.c_float]
+    L.orbx_debug_sim3_search_stats.argtypes = [ip]
+    L.orbx_debug_sim3_search_list_length.argtypes = []
     L.orbx_predict_scale.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int]
     L.orbx_predict_scale_breakpoints.argtypes = [C.c_float, C.c_int, vp]
     L.orbx_stereo_match_last.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, vp, C.c_int, vp]
@@ -291,6 +297,12 @@ def predict_scale_breakpoints(scale_factor=1.2, nlevels=8):
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbx_predict_scale_breakpoints")
     return b
+
+
+def sim3_hamming_bound(th_low=50, ratio_hamming=1.0):
+    """The largest descriptor distance the Sim3 projection search accepts: the largest d in [0, 255] with (float)d <= (float)th_low *
+    ratio_hamming, -1 if that product is negative or NaN.  Host only."""
+    return load_library().orbx_sim3_hamming_bound(int(th_low), C.c_float(ratio_hamming))
 
 
 def camera(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
@@ -601,6 +613,30 @@ class ORBextractor:
             dp(d_mp_flags), dp(d_poses), dp(d_kps_un), dp(d_u_right), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds),
             _ptr(cam), self.nlevels if nlevels is None else nlevels, mbf, th, th_low, int(reproj_check), dp(d_best_idx), dp(d_best_dist),
             dp(d_exit), dp(d_n_fused)))
+
+    def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
+                                         d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,
+                                         d_match_idx, d_match_dist, d_exit, d_n_matches, projection=0, th=3.0, th_low=50, ratio_hamming=1.0,
+                                         nlevels=None):
+        """The Sim3 overloads of ORBmatcher::SearchByProjection (reference src/ORBmatcher.cc:473-586, projection=0; :588-704, projection=1;
+        loop closing) for one-camera keyframes with the Pinhole model; kf and mp = (first, step) of the keyframe / MapPoint list of pair p,
+        kf step 0 = several candidates into one keyframe.  d_poses is [p*12], per pair.  d_n_mp, d_occupied and d_exit may be None.  A match
+        closes its keypoint for the later MapPoints of the list, as in the reference; d_matches [p*capacity + idx] names the list index."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
+        cam = None if cam is None else np.ascontiguousarray(cam, np.float32)
+        self._check(self._L.orbx_search_by_projection_sim3_device(
+            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_n_mp), mp_capacity,
+            dp(d_mp_flags), dp(d_poses), dp(d_kps_un), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), _ptr(cam),
+            self.nlevels if nlevels is None else nlevels, int(projection), th, th_low, ratio_hamming, dp(d_occupied), dp(d_matches),
+            dp(d_match_idx), dp(d_match_dist), dp(d_exit), dp(d_n_matches)))
+
+    def debug_sim3_search_stats(self):
+        """(rounds of pair 0, requests settled by a re-scan, 100-MHz ticks of pair 0's settling workgroup, 0) of the last Sim3 search"""
+        out = (C.c_int * 4)()
+        self._check(self._L.orbx_debug_sim3_search_stats(out))
+        return tuple(out)
 
     def stereo_from_rgbd_device(self, n_frames, d_kps, d_kps_un, d_n, capacity, d_depth, depth_is_u16, rows, cols, depth_map_factor, mbf,
                                 d_u_right, d_depth_out, depth_stride_bytes=None, depth_frame_stride_bytes=None):

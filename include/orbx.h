@@ -572,6 +572,72 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
                      const float* bounds4, const orbx_camera* cam, int nlevels, float mbf, float th, int th_low, int reproj_check,
                      int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused);
 
+/* ---- loop closing's matcher: the two Sim3 overloads of ORBmatcher::SearchByProjection ----------------------------------------------------
+ * Where a MapPoint left the search (d_exit of orbx_search_by_projection_sim3_device); 0 .. 5 are orbx_fuse_exit's */
+enum orbx_sim3_search_exit {
+    ORBX_SIM3_SEARCH_FLAG = 0,           /* bit 0 of its flag is clear (isBad() or in spAlreadyFound, :501 / :617), or it lies beyond d_n_mp */
+    ORBX_SIM3_SEARCH_NEG_DEPTH = 1,      /* :511 / :627 */
+    ORBX_SIM3_SEARCH_NOT_IN_IMAGE = 2,   /* :522 / :639 */
+    ORBX_SIM3_SEARCH_DISTANCE = 3,       /* :531 / :648 */
+    ORBX_SIM3_SEARCH_NORMAL = 4,         /* :537 / :654 */
+    ORBX_SIM3_SEARCH_EMPTY_WINDOW = 5,   /* vIndices.empty() (:547 / :664), tested before any keypoint state */
+    ORBX_SIM3_SEARCH_NO_MATCH = 6,       /* every candidate was closed, failed the level filter or was above the bound */
+    ORBX_SIM3_SEARCH_MATCHED = 7         /* nmatches++ (:580 / :697) */
+};
+
+/* The acceptance bestDist <= TH_LOW*ratioHamming (src/ORBmatcher.cc:577, :694) compares an int with a float product.  Host-only: the largest
+ * integer d in [0, 255] with (float)d <= (float)th_low * ratio_hamming; -1 if the product is negative or NaN (nothing matches).  A product
+ * of 256 or more gives 255: there the reference would accept bestDist = 256 of a MapPoint WITHOUT a candidate and write vpMatched[-1];
+ * the entry CLAMPS to 255 instead, so such a MapPoint never matches.  (50, 1.5) -> 75, (50, 1.0) -> 50, (50, 0.999) -> 49. */
+int orbx_sim3_hamming_bound(int th_low, float ratio_hamming);
+
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (src/ORBmatcher.cc:473-586; projection = 0; called at
+ * src/LoopClosing.cc:755 with th 5, ratio 1.0 and at :1008 with th 3, ratio 1.5) and SearchByProjection(pKF, Scw, vpPoints, vpPointsKFs,
+ * vpMatched, vpMatchedKF, th, ratioHamming) (:588-704; projection = 1; called at src/LoopClosing.cc:730 with th 8, ratio 1.5), for
+ * keyframes with NLeft == -1 and the Pinhole model.  NOT covered: the KannalaBrandt8 model.  (ORBmatcher::SearchBySim3, :1735-1959, has no
+ * caller in the reference and is not built.)
+ * Up to the window the search is the Sim3 overload of Fuse (orbx_fuse_device with reproj_check = 0) and shares its front end.  What is
+ * new: a match CLOSES its keypoint for every later MapPoint of the list (vpMatched[bestIdx] = pMP, :579 / :696, is read back at :558 /
+ * :675), so the MapPoints of a pair are a sequential chain.  The entry computes exactly what that chain computes - as a parallel fixed
+ * point ("Sim3 projection search") - including which of several MapPoints that want the same keypoint gets it (the first in
+ * list order) and what the others fall back to.
+ * Pair p searches MapPoint list mp_first + p*mp_step in keyframe kf_first + p*kf_step of one device-resident batch.  kf_step = 0 is the
+ * normal case: several loop candidates, each with its own Sim3 and point list, searched in the same current keyframe.
+ *   d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity : as orbx_fuse_device (d_mp_dist holds GetMinDistanceInvariance(),
+ *                 GetMaxDistanceInvariance() and mfMaxDistance ITSELF)
+ *   d_mp_flags[p*mp_capacity + i] : bit 0 = !pMP->isBad() && !spAlreadyFound.count(pMP) (:501, :617); static, the reference builds
+ *                 spAlreadyFound once before the loop (:490, :605)
+ *   d_poses[p*12]              : PER PAIR, not per frame: rows of sRcw/scw | tcw/scw as the caller's cv::Mat code computes them (:483-486,
+ *                 :598-601), the convention of orbx_fuse_device with reproj_check = 0.  Ow = -Rcw.t()*tcw (:487) is computed here.
+ *   d_kps_un, d_desc, d_n_out, capacity, d_grid_off, d_grid_idx, bounds4, cam, nlevels : as orbx_fuse_device (bounds4 truncated for
+ *                 IsInImage and the window, the grid inverses from the floats; nlevels must be the handle's)
+ *   projection                 : 0 = pKF->mpCamera->project (:519): u = fx*x/z + cx;  1 = the second overload's own lines (:631-636):
+ *                 invz = 1/z; x = X*invz; u = fx*x + cx.  Every operation is rounded on its own; the two differ in the last bit.
+ *   th                         : the reference's int th, multiplied as (float)th * mvScaleFactors[level] (:543, :660); 8, 5, 3 at the callers
+ *   th_low, ratio_hamming      : ORBmatcher::TH_LOW (50) and ratioHamming; the bound is orbx_sim3_hamming_bound(th_low, ratio_hamming)
+ *   d_occupied[p*capacity + idx] : vpMatched[idx] != NULL on entry, or NULL = all free
+ *   d_matches[p*capacity + idx]  : out, the list index i of the MapPoint the keypoint holds afterwards (vpMatched[idx] = vpPoints[i]), -1 =
+ *                 none; a keypoint occupied on entry stays -1 (the caller keeps its old entry).  vpMatchedKF[idx] of the second overload is
+ *                 vpPointsKFs[d_matches[idx]]: the caller derives it.
+ *   d_match_idx[p*mp_capacity + i]  : out, the keypoint MapPoint i received, -1 = none
+ *   d_match_dist[p*mp_capacity + i] : out, the accepted distance; 256 where nothing was accepted
+ *   d_exit[p*mp_capacity + i]       : out or NULL, an orbx_sim3_search_exit
+ *   d_n_matches[p]                  : out, the return value
+ * All entries of every pair are written (entries past d_n_mp as FLAG, -1, 256).  Arithmetic, IsInImage, PredictScale, GetFeaturesInArea
+ * and the tie rule (of equal distances the FIRST in visit order) as orbx_fuse_device.  Errors: ORBX_ERR_BAD_ARGUMENT as orbx_fuse_device
+ * (and for a projection other than 0 / 1).  Supported: the settling workgroup of a pair keeps one int per keypoint and one per MapPoint
+ * in LDS, and a key holds the keypoint's grid slot in 16 bits:
+ *   4 * (capacity + mp_capacity) + 64 <= 163 328 bytes  and  capacity <= 65 536      (capacity 2720 with mp_capacity 16384 is inside)
+ * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched or allocated.  The key lists (48 bytes per pair and MapPoint)
+ * are the handle's, allocated on first use.  Asynchronous on the handle's stream. */
+int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step,
+                                          const float* d_mp_world, const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc,
+                                          const int* d_n_mp, int mp_capacity, const uint8_t* d_mp_flags, const float* d_poses,
+                                          const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int* d_n_out, int capacity,
+                                          const int* d_grid_off, const int* d_grid_idx, const float* bounds4, const orbx_camera* cam, int nlevels,
+                                          int projection, float th, int th_low, float ratio_hamming, const uint8_t* d_occupied, int* d_matches,
+                                          int* d_match_idx, int* d_match_dist, uint8_t* d_exit, int* d_n_matches);
+
 /* Stream control.  By default the handle owns a stream; orbx_set_stream adopts a caller stream
  * (hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream) so the caller's events
  * and graphs see the work. */
@@ -586,6 +652,13 @@ int orbx_debug_search_rounds(int* out4);
  * needed, [1] 1 if pair 0 was settled by the walk (forced, or a MapPoint without observations reopened a keypoint), [2] pairs settled by the
  * walk since the last read (the read resets it), [3] 100-MHz ticks of pair 0's workgroup.  Returns 0, or a negative orbx_status. */
 int orbx_debug_two_eyes_search_stats(int* out4);
+
+/* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
+ * (the last one changes nothing), [1] requests of the last launch whose decision came from scanning the window again (every key of a
+ * truncated list was closed), [2] 100-MHz ticks of pair 0's settling workgroup, [3] 0.  Returns 0, or a negative orbx_status. */
+int orbx_debug_sim3_search_stats(int* out4);
+/* keys the window kernel of that search keeps per MapPoint (tests plant a window that holds more) */
+int orbx_debug_sim3_search_list_length(void);
 
 /* Which launch forms the last call took (results never depend on them; the parity tests assert the form they mean to cover and the
  * published timings name theirs): pyramid_form 0 = k_pyr_cols (region-major, *pyramid_cut_px = side of its regions), 1 = k_pyr_first +
