@@ -39,6 +39,16 @@ __device__ __forceinline__ float gemmRow(float a0, float a1, float a2, const flo
     return (float)s;
 }
 
+// MapPoint::PredictScale as a count of breakpoints (ascending; NaN is above none, +inf above all).  P: nlevels, breaks[].
+// Shared with the frustum test of k_frustum_point.hpp.
+template <class P>
+__device__ __forceinline__ int predictScaleLevel(float ratio, const P& p) {
+    int level = 0;
+#pragma unroll
+    for (int k = 1; k < kMaxLevels; k++) level += k < p.nlevels && ratio >= p.breaks[k - 1] ? 1 : 0;
+    return level;
+}
+
 // P: a parameter block with fx, fy, cx, cy, minX .. maxY (truncated), wInv, hInv (from the float bounds), scale[], breaks[], th, nlevels.
 // T: the 12 floats of the pose (Rcw | tcw rows); xw / nrm / dst: the MapPoint's position, normal and (min, max invariance, mfMaxDistance).
 // Returns the exit (kFrontNegDepth .. kFrontEmptyWindow) or kFrontPassed with `o` filled.
@@ -73,11 +83,8 @@ __device__ __forceinline__ int projectIntoKeyFrame(const float* __restrict__ T, 
     const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)nrm[0]), __dmul_rn((double)PO[1], (double)nrm[1])),
                                  __dmul_rn((double)PO[2], (double)nrm[2]));
     if (dot < __dmul_rn(0.5, (double)dist3D)) return kFrontNormal;                   // :1496, :537
-    // MapPoint::PredictScale as a count of breakpoints (ascending; NaN is above none, +inf above all)
     const float ratio = __fdiv_rn(dst[2], dist3D);                                   // mfMaxDistance itself, not 1.2f * it (MapPoint.cc:519)
-    int level = 0;
-#pragma unroll
-    for (int k = 1; k < kMaxLevels; k++) level += k < p.nlevels && ratio >= p.breaks[k - 1] ? 1 : 0;
+    const int level = predictScaleLevel(ratio, p);
     const float r = __fmul_rn(p.th, p.scale[level]);                                 // :1505, :543
     // KeyFrame::GetFeaturesInArea's cell window with its four early returns (KeyFrame.cc:778-792)
     const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, p.minX), r), p.wInv)));

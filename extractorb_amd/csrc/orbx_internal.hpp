@@ -99,6 +99,14 @@ void launchProjectLast(hipStream_t, const Keypoint*, const Keypoint*, const int*
                        ProjQuery*, int);
 void launchSearchProj(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                       const int*, const float*, uint8_t*, const ProjSearchParams&, int*, int*, int);
+struct TrackRecord { float projX, projY, projXR, depth, viewCos; int level, exit; };      // == orbx_track_record (k_frustum_point.hpp)
+struct FrustumParams {      // == k_frustum_point.hpp
+    float fx, fy, cx, cy, minX, maxX, minY, maxY;
+    float scale[kMaxLevels], breaks[kMaxLevels];
+    float mbf, viewCosLimit, th, thFarPoints;
+    int nlevels, mode, farPoints, mpCapacity, curFirst, curStep, mpFirst, mpStep;
+};
+void launchFrustum(hipStream_t, const float*, const float*, const float*, const uint8_t*, const float*, const int*, const uint8_t*, const float*, const FrustumParams&, ProjQuery*, uint8_t*, int*, int*, TrackRecord*, int*, int);
 struct TwoEyesSearchParams {      // == k_project_two_eyes.hip
     float minX, minY, wInv, hInv, nnRatio;
     int capacity, queryCapacity, pairFirst, pairStep, descFirst, descStep, maxDist, forceWalk;

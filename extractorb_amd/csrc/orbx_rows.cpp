@@ -665,4 +665,45 @@ int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_fi
     return ORBX_OK;
 }
 
+int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, int mp_first, int mp_step, const float* d_mp_world,
+                                 const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc, const float* d_mp_angle,
+                                 const int* d_n_mp, int mp_capacity, const uint8_t* d_mp_flags, const float* d_poses, const orbx_camera* cam,
+                                 const float* bounds4, int nlevels, int mode, float mbf, float view_cos_limit, float th, int far_points,
+                                 float th_far_points, orbx_proj_query* d_queries, uint8_t* d_query_desc, int* d_query_src, int* d_n_queries,
+                                 orbx_track_record* d_track, int* d_n_in_view) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (mode != ORBX_FRUSTUM_LOCAL_MAP && mode != ORBX_FRUSTUM_RELOCALIZATION)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "a mode other than ORBX_FRUSTUM_LOCAL_MAP / ORBX_FRUSTUM_RELOCALIZATION");
+    // the normals are read by the local-map mode alone, the keypoint angles by the relocalisation mode alone
+    if (!d_mp_world || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !cam || !bounds4 || !d_queries || !d_query_desc || !d_query_src ||
+        !d_n_queries || !d_track || !d_n_in_view || (mode == ORBX_FRUSTUM_LOCAL_MAP ? !d_mp_normal : !d_mp_angle) || mp_capacity < 1 ||
+        n_pairs < 1 || cur_first < 0 || mp_first < 0 || cur_first + (long long)(n_pairs - 1) * cur_step < 0 ||
+        mp_first + (long long)(n_pairs - 1) * mp_step < 0)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, mp_capacity/n_pairs < 1 or a negative frame or list index");
+    if (nlevels != h->nlevels)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
+    if (!h->scaleBreaksReady) {
+        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
+            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
+        h->scaleBreaksReady = true;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    FrustumParams p{};
+    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
+    // Frame's own float bounds, compared as they are (Frame.cc:520-523, ORBmatcher.cc:2209-2212): no truncation here, unlike orbx_fuse_device
+    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
+    for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
+    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    p.mbf = mbf; p.viewCosLimit = view_cos_limit; p.th = th; p.thFarPoints = th_far_points;
+    p.nlevels = h->nlevels; p.mode = mode; p.farPoints = far_points ? 1 : 0; p.mpCapacity = mp_capacity;
+    p.curFirst = cur_first; p.curStep = cur_step; p.mpFirst = mp_first; p.mpStep = mp_step;
+    {
+        Prof pr(h, S_FRAME);
+        launchFrustum(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_mp_angle, d_n_mp, d_mp_flags, d_poses, p, (ProjQuery*)d_queries,
+                      d_query_desc, d_query_src, d_n_queries, (TrackRecord*)d_track, d_n_in_view, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"

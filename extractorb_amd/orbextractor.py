@@ -19,6 +19,16 @@ _HEADER = os.path.join(_ROOT, "include", "orbx.h")
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 assert KEYPOINT_DTYPE.itemsize == 28
+# orbx_proj_query: one search request of orbx_search_by_projection_device (32 bytes)
+PROJ_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("radius", "<f4"), ("min_level", "<i4"), ("max_level", "<i4"),
+                             ("flags", "<i4"), ("angle", "<f4")])
+# orbx_track_record: what Frame::isInFrustum leaves in a MapPoint (28 bytes); mbTrackInView is exit >= FRUSTUM_FAR
+TRACK_RECORD_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"),
+                               ("level", "<i4"), ("exit", "<i4")])
+assert PROJ_QUERY_DTYPE.itemsize == 32 and TRACK_RECORD_DTYPE.itemsize == 28
+FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION = 0, 1      # orbx_frustum_mode
+(FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH, FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR,
+ FRUSTUM_REQUEST) = range(7)                           # orbx_frustum_exit
 
 ORBX_OK = 0
 ORBX_ERR_EMPTY_IMAGE = -1
@@ -176,6 +186,8 @@ def load_library():
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
+    L.orbx_frustum_requests_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp,
+                                               C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
     L.orbx_sim3_hamming_bound.argtypes = [C.c_int, C.c_float]
     L.orbx_debug_sim3_search_stats.argtypes = [ip]
     L.orbx_debug_sim3_search_list_length.argtypes = []
@@ -631,6 +643,26 @@ class ORBextractor:
             dp(d_mp_flags), dp(d_poses), dp(d_kps_un), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), _ptr(cam),
             self.nlevels if nlevels is None else nlevels, int(projection), th, th_low, ratio_hamming, dp(d_occupied), dp(d_matches),
             dp(d_match_idx), dp(d_match_dist), dp(d_exit), dp(d_n_matches)))
+
+    def frustum_requests_device(self, n_pairs, cur, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_mp_angle, d_n_mp, mp_capacity, d_mp_flags,
+                                d_poses, cam, bounds, d_queries, d_query_desc, d_query_src, d_n_queries, d_track, d_n_in_view,
+                                mode=FRUSTUM_LOCAL_MAP, mbf=0.0, view_cos_limit=0.5, th=1.0, far_points=False, th_far_points=0.0, nlevels=None):
+        """Frame::isInFrustum over a MapPoint list plus the prelude of ORBmatcher::SearchByProjection(F, vpMapPoints, ...) (reference
+        src/Frame.cc:493-570, src/Tracking.cc:2941-2959, src/ORBmatcher.cc:50-73; mode=FRUSTUM_LOCAL_MAP), or the projection of a keyframe's
+        MapPoints for Relocalization (src/ORBmatcher.cc:2183-2230; mode=FRUSTUM_RELOCALIZATION).  cur and mp = (first, step) of the frame /
+        MapPoint list of pair p.  Writes the requests of every pair compacted in list order (d_queries of PROJ_QUERY_DTYPE, d_query_desc,
+        d_query_src, d_n_queries: feed them to search_by_projection_device with query_capacity = mp_capacity and desc_blocks = (0, 1)), one
+        TRACK_RECORD_DTYPE per list entry and nToMatch per pair.  d_n_mp may be None; d_mp_angle in the local-map mode and d_mp_normal in
+        the relocalisation mode as well."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
+        cam = None if cam is None else np.ascontiguousarray(cam, np.float32)
+        self._check(self._L.orbx_frustum_requests_device(
+            self._h, n_pairs, cur[0], cur[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_mp_angle), dp(d_n_mp),
+            mp_capacity, dp(d_mp_flags), dp(d_poses), _ptr(cam), _ptr(bounds), self.nlevels if nlevels is None else nlevels, int(mode), mbf,
+            view_cos_limit, th, int(bool(far_points)), th_far_points, dp(d_queries), dp(d_query_desc), dp(d_query_src), dp(d_n_queries),
+            dp(d_track), dp(d_n_in_view)))
 
     def debug_sim3_search_stats(self):
         """(rounds of pair 0, requests settled by a re-scan, 100-MHz ticks of pair 0's settling workgroup, 0) of the last Sim3 search"""

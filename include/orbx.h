@@ -638,6 +638,91 @@ int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_fi
                                           int projection, float th, int th_low, float ratio_hamming, const uint8_t* d_occupied, int* d_matches,
                                           int* d_match_idx, int* d_match_dist, uint8_t* d_exit, int* d_n_matches);
 
+/* ---- the tracker's front half of the two map-to-frame projection searches: the frustum test and the request lists -------------------------
+ * Which statement orbx_frustum_requests_device applies to a MapPoint */
+enum orbx_frustum_mode {
+    ORBX_FRUSTUM_LOCAL_MAP = 0,       /* Frame::isInFrustum (src/Frame.cc:493-570) + the matcher's prelude (src/ORBmatcher.cc:50-73) */
+    ORBX_FRUSTUM_RELOCALIZATION = 1   /* the projection of pKF's MapPoints (src/ORBmatcher.cc:2183-2230) */
+};
+/* Where a MapPoint left it (orbx_track_record.exit) */
+enum orbx_frustum_exit {
+    ORBX_FRUSTUM_FLAG = 0,            /* bit 0 of its flag is clear (src/Tracking.cc:2945-2948 / src/ORBmatcher.cc:2199-2201), or it lies beyond d_n_mp */
+    ORBX_FRUSTUM_NEG_DEPTH = 1,       /* PcZ < 0.0f (src/Frame.cc:513); never in the relocalisation mode, which has no depth test */
+    ORBX_FRUSTUM_NOT_IN_IMAGE = 2,    /* src/Frame.cc:520-523 / src/ORBmatcher.cc:2209-2212 */
+    ORBX_FRUSTUM_DISTANCE = 3,        /* src/Frame.cc:535 / src/ORBmatcher.cc:2222 */
+    ORBX_FRUSTUM_VIEW_COS = 4,        /* viewCos < viewingCosLimit (src/Frame.cc:547); local map only */
+    ORBX_FRUSTUM_FAR = 5,             /* isInFrustum returned true, the matcher skips it: bFarPoints && mTrackDepth > thFarPoints (src/ORBmatcher.cc:56) */
+    ORBX_FRUSTUM_REQUEST = 6          /* it became a request */
+};
+/* What Frame::isInFrustum leaves in the MapPoint (src/Frame.cc:497-499, :526-527, :556-565), one per list entry.  mbTrackInView is
+ * exit >= ORBX_FRUSTUM_FAR.  proj_x / proj_y are -1 until the bounds test has passed and uv from there on (the reference assigns them at
+ * :526-527 even when it returns false later).  Fields the reference does not assign on the entry's path are 0 and level is -1 (proj_xr,
+ * depth, view_cos and level are assigned only when isInFrustum returns true), so every byte is defined; an entry that was not looked at
+ * (ORBX_FRUSTUM_FLAG) carries -1, -1, 0, 0, 0, -1, 0.  Relocalisation mode: proj_x / proj_y as above, level = nPredictedLevel of a request
+ * (src/ORBmatcher.cc:2225), proj_xr = depth = view_cos = 0. */
+typedef struct orbx_track_record {
+    float proj_x, proj_y;   /* mTrackProjX, mTrackProjY */
+    float proj_xr;          /* mTrackProjXR = uv.x - mbf*invz (:558) */
+    float depth;            /* mTrackDepth = Pc_dist = cv::norm(Pc) (:508, :560) */
+    float view_cos;         /* mTrackViewCos (:545, :565) */
+    int32_t level;          /* mnTrackScaleLevel (:551, :564) */
+    int32_t exit;           /* an orbx_frustum_exit */
+} orbx_track_record;
+
+/* Tracking::SearchLocalPoints' loop over the local map (src/Tracking.cc:2941-2959) and the front half of Relocalization's projection search,
+ * on the device: MapPoint lists and frame poses in, the request lists of orbx_search_by_projection_device out.  For frames with Nleft == -1 and
+ * the Pinhole model.  NOT covered: isInFrustum's Nleft != -1 branch (src/Frame.cc:571 on: isInFrustumChecks, mpCamera2 - the KannalaBrandt8 pair).
+ * Pair p projects MapPoint list mp_first + p*mp_step into frame cur_first + p*cur_step (mp_step = 0: one local map into several frames).
+ *   per MapPoint, in blocks of mp_capacity per list (m = list*mp_capacity + i), the conventions of orbx_fuse_device:
+ *   d_mp_world[m*3], d_mp_normal[m*3] : GetWorldPos(), GetNormal() (the normals are read in mode 0 only and may be NULL in mode 1)
+ *   d_mp_dist[m*3]             : GetMinDistanceInvariance(), GetMaxDistanceInvariance() and mfMaxDistance ITSELF (src/MapPoint.cc:519)
+ *   d_mp_desc[m*32]            : GetDescriptor() (16-byte aligned)
+ *   d_mp_angle[m]              : mode 1: pKF->mvKeysUn[i].angle of the keypoint that holds the MapPoint (src/ORBmatcher.cc:2264); NULL is allowed in mode 0
+ *   d_n_mp[list]               : MapPoints of the list, NULL = mp_capacity
+ *   d_mp_flags[p*mp_capacity + i] : per PAIR.  mode 0: bit 0 = pMP->mnLastFrameSeen != mCurrentFrame.mnId && !pMP->isBad()
+ *                 (src/Tracking.cc:2945-2948), bit 1 = Observations() > 0.  mode 1: bit 0 = pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)
+ *                 (src/ORBmatcher.cc:2199-2201)
+ *   d_poses[f*12]              : Frame::mTcw, rows 0..2 (3x4, row-major: Rcw | tcw) of every frame, as orbx_project_last_frame_device takes them
+ *   cam (fx, fy, cx, cy)       : Pinhole::project (src/CameraModels/Pinhole.cpp:30-33): u = fx*x/z + cx
+ *   bounds4                    : Frame's FLOAT mnMinX, mnMaxX, mnMinY, mnMaxY, compared as they are and NON-STRICTLY (uv.x < mnMinX || uv.x >
+ *                 mnMaxX leaves, src/Frame.cc:520-523): a projection exactly on a bound passes.  Not KeyFrame's truncated, strict bounds of orbx_fuse_device.
+ *   nlevels                    : must equal orbx_get_levels(h) (mvScaleFactors and PredictScale's breakpoints are the handle's); else ORBX_ERR_BAD_ARGUMENT
+ * mode = ORBX_FRUSTUM_LOCAL_MAP: Frame::isInFrustum(pMP, view_cos_limit) (src/Frame.cc:493-570; the caller passes 0.5, src/Tracking.cc:2950),
+ * every operation rounded on its own: Pc = mRcw*P + mtcw as cv::gemm (products and sums in double, one rounding to float); Pc_dist =
+ * cv::norm(Pc) (squares summed in double in element order, one square root, then float, :508); PcZ < 0.0f leaves (:513); invz = 1.0f/PcZ is a
+ * float division (:512) and z == 0 is NOT rejected: it goes on to Pinhole::project and +-inf leaves by the bounds (:520-523); mOw =
+ * -mRcw.t()*mtcw (src/Frame.cc:466-472); PO = P - mOw in float (:532); dist = cv::norm(PO) (:533); dist < min || dist > max leaves (:535: both
+ * ends pass); viewCos = (float)(PO.dot(Pn) / (double)dist) - Mat::dot accumulates a double in element order and the quotient is a double
+ * division stored to float (:545; NOT Fuse's dot < 0.5*dist: a quotient below 0.5 that rounds to 0.5f passes here); viewCos < view_cos_limit
+ * leaves (:547); PredictScale(dist, this) as the count of breakpoints at or below mfMaxDistance/dist (:551, src/MapPoint.cc:531-546);
+ * mTrackProjXR = uv.x - mbf*invz (:558); mTrackDepth = Pc_dist (:560).  Then the prelude of ORBmatcher::SearchByProjection(F, vpMapPoints, th,
+ * bFarPoints, thFarPoints) (src/ORBmatcher.cc:50-73): far_points && mTrackDepth > th_far_points leaves (:56); r = RadiusByViewingCos(viewCos)
+ * (:216-222: the float against the DOUBLE literal 0.998, which is viewCos >= 0.998f - a viewCos equal to 0.998f gets 2.5, not 4.0); th !=
+ * 1.0f multiplies it (:48, :69-70); the request is u, v = uv, ur = mTrackProjXR, radius = r*mvScaleFactors[level], min_level, max_level =
+ * level - 1, level (:73), flags = 1 | (bit 1 of the input flag), angle = 0.
+ * mode = ORBX_FRUSTUM_RELOCALIZATION: src/ORBmatcher.cc:2183-2230.  x3Dc = Rcw*x3Dw + tcw (:2205), project (:2207), the four bounds tests
+ * (:2209-2212) - there is NO depth test: a point behind the camera that projects inside the bounds becomes a request, as in the reference -,
+ * Ow (:2185), PO, dist3D (:2215-2216), the invariance test (:2222), PredictScale (:2225); the request is u, v = uv, ur = 0, radius =
+ * th*mvScaleFactors[level] (:2228), min_level, max_level = level - 1, level + 1 (:2230), flags = 3, angle = d_mp_angle[m].  d_mp_normal, mbf,
+ * view_cos_limit, far_points and th_far_points are unused.
+ *   d_queries[p*mp_capacity + k], d_query_desc[(p*mp_capacity + k)*32], d_query_src[p*mp_capacity + k], k < d_n_queries[p] : out, the requests
+ *                 of pair p COMPACTED IN LIST ORDER (the same order in every run: no atomic decides a position), their descriptors (16-byte
+ *                 aligned) and the list index i each came from.  They are what orbx_search_by_projection_device takes with query_capacity =
+ *                 mp_capacity, desc_first = 0, desc_step = 1 and d_n_queries as it is; vpMapPoints[d_query_src[d_matches[i2]]] is the match.
+ *                 (With n_pairs = 1 any query_capacity at or above d_n_queries[0] addresses the same slots, and the search's LDS grows with it.)
+ *                 Slots k >= d_n_queries[p] get an all-zero request and src = -1; their descriptor slots are left untouched.
+ *   d_track[p*mp_capacity + i] : out, an orbx_track_record per list entry; entries beyond d_n_mp carry ORBX_FRUSTUM_FLAG
+ *   d_n_in_view[p]             : out, nToMatch (src/Tracking.cc:2950-2954): the entries with exit >= ORBX_FRUSTUM_FAR, counted BEFORE the far test -
+ *                 the caller's IncreaseVisible() set and mmProjectPoints.  In mode 1 it equals d_n_queries[p].
+ * Errors: ORBX_ERR_BAD_ARGUMENT as orbx_fuse_device (null pointer, nlevels, a mode other than 0 / 1, negative sizes or indices).  Nothing lives in
+ * LDS tables: there is no capacity bound and no ORBX_ERR_UNSUPPORTED case.  Asynchronous on the handle's stream. */
+int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, int mp_first, int mp_step, const float* d_mp_world,
+                                 const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc, const float* d_mp_angle,
+                                 const int* d_n_mp, int mp_capacity, const uint8_t* d_mp_flags, const float* d_poses, const orbx_camera* cam,
+                                 const float* bounds4, int nlevels, int mode, float mbf, float view_cos_limit, float th, int far_points,
+                                 float th_far_points, orbx_proj_query* d_queries, uint8_t* d_query_desc, int* d_query_src, int* d_n_queries,
+                                 orbx_track_record* d_track, int* d_n_in_view);
+
 /* Stream control.  By default the handle owns a stream; orbx_set_stream adopts a caller stream
  * (hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream) so the caller's events
  * and graphs see the work. */
