@@ -13,34 +13,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wave_min.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
-
-struct VocabDevice {            // plain arrays of the tree (TemplatedVocabulary::m_nodes)
-    const int* childOff;        // [nNodes + 1] children of node n: childList[childOff[n] .. childOff[n + 1])  (in m_nodes[n].children order)
-    const int* childList;
-    const uint32_t* desc;       // [nNodes][8]  node descriptors
-    const double* weight;       // [nNodes]
-    const uint32_t* wordId;     // [nNodes]     valid for leaves
-    int nNodes, k, L, scoring, weighting;
-};
-
-namespace {
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ unsigned dppMinU(unsigned v) {
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWMASK, 0xF, false);
-    return o < v ? o : v;
-}
-// minimum over each row of 16 lanes, returned in every lane of the row
-__device__ __forceinline__ unsigned rowMin16(unsigned v) {
-    v = dppMinU<0xB1, 0xF>(v);     // quad_perm [1,0,3,2]
-    v = dppMinU<0x4E, 0xF>(v);     // quad_perm [2,3,0,1]
-    v = dppMinU<0x141, 0xF>(v);    // row_half_mirror
-    v = dppMinU<0x140, 0xF>(v);    // row_mirror
-    return v;
-}
-}  // namespace
 
 // grid (ceil(capacity / 16), n_frames); 256 threads = 16 features x 16 lanes.
 __global__ __launch_bounds__(256) void k_bow_words(VocabDevice V, const uint8_t* __restrict__ desc, const int* __restrict__ nOut,

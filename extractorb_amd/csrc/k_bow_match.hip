@@ -16,34 +16,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
+#include "k_wave_min.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct BowMatchParams {
-    float nnRatio;
-    int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep;
-    int twoKeyFrames;      // SearchByBoW(pKF1, pKF2, vpMatches12): candidates must hold a MapPoint, strict threshold, result indexed by pKF1's keypoints
-};
-
 namespace {
-constexpr int kHistoLength = 30;                          // ORBmatcher.cc:38
 constexpr unsigned kNoneKey = (256u << 16) | 0xFFFFu;     // bestDist = 256, no position
 constexpr int kThreads = 1024;     // 64 rows of 16 lanes: ~100 node segments of a frame are two sequential segments per row
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dppMinU(unsigned v) {
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-    return o < v ? o : v;
-}
-// minimum over each row of 16 lanes, returned in every lane of the row
-__device__ __forceinline__ unsigned rowMin16(unsigned v) {
-    v = dppMinU<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dppMinU<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dppMinU<0x141>(v);     // row_half_mirror
-    v = dppMinU<0x140>(v);     // row_mirror
-    return v;
-}
 }  // namespace
 
 size_t bowMatchLdsBytes(int capacity, bool stageDesc) { return (size_t)((capacity + 15) & ~15) * (4 + 4 + 4 + 4 + 1 + 2 + 2 + 1 + (stageDesc ? 64 : 0)) + 64; }
@@ -103,7 +85,6 @@ __global__ __launch_bounds__(kThreads) void k_search_bow(const uint32_t* __restr
         if (i == 0 || nodeK[i] != nodeK[i - 1]) segList[atomicAdd(&sSeg, 1)] = i;      // (any order: nodes are independent)
     __syncthreads();
     const int nSeg = sSeg;
-    const float factor = 1.0f / kHistoLength;
     for (int s = row; s < nSeg; s += kThreads / 16) {
         const int k0 = segList[s];
         const uint32_t node = nodeK[k0];
@@ -125,8 +106,7 @@ __global__ __launch_bounds__(kThreads) void k_search_bow(const uint32_t* __restr
                 if (takenBy[realIdxF] != -1) continue;                                      // :318-319 (:884-888)
                 uint4 x, y;
                 loadC(realIdxF, x, y);
-                const int dist = __popc(a.x ^ x.x) + __popc(a.y ^ x.y) + __popc(a.z ^ x.z) + __popc(a.w ^ x.w) + __popc(b.x ^ y.x) +
-                                 __popc(b.y ^ y.y) + __popc(b.z ^ y.z) + __popc(b.w ^ y.w);
+                const int dist = hamming256(a, b, x, y);
                 const unsigned kk = ((unsigned)dist << 16) | (unsigned)(c - c0);            // positions ascend per lane: a later equal distance never displaces (:325, :331)
                 if (kk < key) { second = key; key = kk; }
                 else if (kk < second) second = kk;
@@ -139,10 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_search_bow(const uint32_t* __restr
                 if (sub == 0) {
                     takenBy[bestIdxF] = realIdxKF;                                          // vpMapPointMatches[bestIdxF] = pMP
                     if (p.checkOrientation) {                                               // :384-401
-                        float rot = __fsub_rn(kpK[realIdxKF].angle, kpC[bestIdxF].angle);
-                        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                        int bin = (int)roundf(__fmul_rn(rot, factor));
-                        if (bin == kHistoLength) bin = 0;
+                        const int bin = rotationBin(kpK[realIdxKF].angle, kpC[bestIdxF].angle);
                         binOf[bestIdxF] = (uint8_t)bin;
                         atomicAdd(&sHist[bin], 1);
                     }
@@ -154,17 +131,9 @@ __global__ __launch_bounds__(kThreads) void k_search_bow(const uint32_t* __restr
     __syncthreads();
     unsigned dropBins = 0u;
     if (p.checkOrientation) {                                                               // ComputeThreeMaxima (:2303-2344), then :452-468
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = sHist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top3 = computeThreeMaxima(sHist);
         for (int i = 0; i < kHistoLength; i++)
-            if (i != ind1 && i != ind2 && i != ind3) dropBins |= 1u << i;
+            if (i != top3.ind1 && i != top3.ind2 && i != top3.ind3) dropBins |= 1u << i;
     }
     int mine = 0;
     int* out = matches + (long long)pair * cap;

@@ -19,39 +19,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
+#include "k_wave_min.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct BowTwoEyesParams {      // == orbx_internal.hpp
-    float nnRatio;
-    int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep;
-};
-
 namespace {
-constexpr int kHistoLength = 30;                          // ORBmatcher.cc:38
 constexpr unsigned kNoneKey = (256u << 16) | 0xFFFFu;     // bestDist = 256, no position
 constexpr int kThreads = 1024;                            // 64 rows of 16 lanes
 // the match table is read by 16 lanes and written by one: volatile, and typed as LDS so that no access becomes a FLAT one
 typedef __attribute__((address_space(3))) volatile int LdsVolatileInt;
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dppMinU(unsigned v) {
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-    return o < v ? o : v;
-}
-// minimum over each row of 16 lanes, returned in every lane of the row
-__device__ __forceinline__ unsigned rowMin16(unsigned v) {
-    v = dppMinU<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dppMinU<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dppMinU<0x141>(v);     // row_half_mirror
-    v = dppMinU<0x140>(v);     // row_mirror
-    return v;
-}
-__device__ __forceinline__ int hamming(const uint4& a, const uint4& b, const uint4& x, const uint4& y) {      // DescriptorDistance (:2349-2365)
-    return __popc(a.x ^ x.x) + __popc(a.y ^ x.y) + __popc(a.z ^ x.z) + __popc(a.w ^ x.w) + __popc(b.x ^ y.x) + __popc(b.y ^ y.y) +
-           __popc(b.z ^ y.z) + __popc(b.w ^ y.w);
-}
 // [lo, hi) of `node` in a sorted node column of n entries (the maps' lower_bound walk, :432-439, meets exactly the common keys)
 __device__ __forceinline__ void segmentOf(const uint32_t* col, int n, uint32_t node, int& s0, int& s1) {
     int lo = 0, hi = n;
@@ -121,7 +100,6 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
         if (i == 0 || nodeCL[i] != nodeCL[i - 1]) segList[atomicAdd(&sSeg, 1)] = i;      // (any order: nodes are independent)
     __syncthreads();
     const int nSeg = sSeg;
-    const float factor = 1.0f / kHistoLength;
     for (int s = row; s < nSeg; s += kThreads / 16) {
         const int cl0 = segList[s];
         const uint32_t node = nodeCL[cl0];
@@ -153,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
                 uint4 x, y;
                 if constexpr (STAGE) { x = sDesc[2 * f]; y = sDesc[2 * f + 1]; }
                 else { x = descC[2 * f]; y = descC[2 * f + 1]; }
-                const unsigned kk = ((unsigned)hamming(da, db, x, y) << 16) | (unsigned)(c - cl0);   // positions ascend per lane: a later equal distance never displaces
+                const unsigned kk = ((unsigned)hamming256(da, db, x, y) << 16) | (unsigned)(c - cl0);   // positions ascend per lane: a later equal distance never displaces
                 if (kk < key) { second = key; key = kk; }
                 else if (kk < second) second = kk;
             }
@@ -163,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
                 uint4 x, y;
                 if constexpr (STAGE) { x = sDesc[2 * (capA + f)]; y = sDesc[2 * (capA + f) + 1]; }
                 else { x = descC[2 * ((long long)cap + f)]; y = descC[2 * ((long long)cap + f) + 1]; }
-                const unsigned kk = ((unsigned)hamming(da, db, x, y) << 16) | (unsigned)(c - cr0);
+                const unsigned kk = ((unsigned)hamming256(da, db, x, y) << 16) | (unsigned)(c - cr0);
                 if (kk < keyR) keyR = kk;
             }
             const unsigned best = rowMin16(key);
@@ -181,10 +159,7 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
                     const int f = e ? (int)idxCR[cr0 + (int)(bestR & 0xFFFFu)] : (int)idxCL[cl0 + (int)(best & 0xFFFFu)];
                     takenBy[e * capA + f] = from;                                               // vpMapPointMatches[bestIdxF / bestIdxFR] = pMP
                     if (p.checkOrientation) {                                                   // :384-401, :411-428
-                        float rot = __fsub_rn(angleK, kpC[(long long)e * cap + f].angle);
-                        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                        int bin = (int)roundf(__fmul_rn(rot, factor));
-                        if (bin == kHistoLength) bin = 0;
+                        int bin = rotationBin(angleK, kpC[(long long)e * cap + f].angle);
                         bin = min(max(bin, 0), kHistoLength - 1);                               // (the reference asserts it; an angle outside [0, 360) must not index past the table)
                         binOf[e * capA + f] = (uint8_t)bin;
                         atomicAdd(&sHist[bin], 1);
@@ -197,17 +172,9 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
     __syncthreads();
     unsigned dropBins = 0u;
     if (p.checkOrientation) {                                                                   // ComputeThreeMaxima (:2303-2344), then :446-468
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = sHist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top3 = computeThreeMaxima(sHist);
         for (int i = 0; i < kHistoLength; i++)
-            if (i != ind1 && i != ind2 && i != ind3) dropBins |= 1u << i;
+            if (i != top3.ind1 && i != top3.ind2 && i != top3.ind3) dropBins |= 1u << i;
     }
     int mine = 0;
 #pragma unroll

@@ -11,18 +11,9 @@
 #include <stdint.h>
 
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
-
-struct CameraParams { float fx, fy, cx, cy, k1, k2, p1, p2, k3; };
-struct FrameFinishParams {
-    CameraParams cam;
-    float minX, minY, wInv, hInv;   // mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv
-    int capacity;
-    int rawGrid;                    // the Nleft != -1 branch of AssignFeaturesToGrid (:404-414): the cells come from mvKeys / mvKeysRight, not from mvKeysUn
-};
-
-constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;   // FRAME_GRID_COLS/ROWS, inc/Frame.h:39-40
 
 __device__ __forceinline__ void undistortPoint(const CameraParams& c, float xin, float yin, float* xo, float* yo) {
     const double fx = c.fx, fy = c.fy, cx = c.cx, cy = c.cy;
@@ -122,11 +113,6 @@ __global__ __launch_bounds__(1024) void k_frame_finish(const Keypoint* __restric
 // Frame::ComputeStereoFromRGBD (reference src/Frame.cc:994-1015) with the depth conversion Tracking::GrabImageRGBD applies
 // first (imDepth.convertTo(CV_32F, mDepthMapFactor), src/Tracking.cc:1003-1004): d = depth(int(v), int(u)) [* factor];
 // d > 0: mvDepth = d, mvuRight = kpUn.x - mbf / d; else both -1.  One thread per keypoint slot.
-struct RgbdParams {
-    int capacity, rows, cols, isU16, scale;     // scale: convertTo runs (a 16-bit map always, a float map when factor != 1)
-    long long stride, frame;                    // bytes
-    float factor, mbf;
-};
 __global__ __launch_bounds__(256) void k_stereo_from_rgbd(const Keypoint* __restrict__ kps, const Keypoint* __restrict__ kpsUn,
                                                            const int* __restrict__ nOut, const uint8_t* __restrict__ depth,
                                                            RgbdParams p, float* __restrict__ uRight, float* __restrict__ depthOut) {

@@ -17,6 +17,7 @@
 
 #include "k_frustum_point.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 

@@ -7,7 +7,7 @@
 // It is a statement of its own and NOT projectIntoKeyFrame of k_keyframe_project.hpp: the bounds are Frame's FLOAT mnMinX .. mnMaxY with
 // NON-STRICT tests (uv.x < mnMinX || uv.x > mnMaxX, src/Frame.cc:520-523, src/ORBmatcher.cc:2209-2212), not KeyFrame's truncated, strict
 // ones; there is no cell window; the viewing-angle test has another form (below); the relocalisation path has no depth test at all.  What
-// is shared with that header: gemmRow (cv::gemm) and predictScaleLevel (MapPoint::PredictScale as a count of breakpoints).
+// is shared: gemmRow (cv::gemm, k_match_helpers.hpp) and predictScaleLevel (MapPoint::PredictScale as a count of breakpoints, that header).
 // The arithmetic is the reference's x86-64 build, every operation rounded on its own (-ffp-contract=off and the __f*_rn / __d*_rn
 // intrinsics).  Where the forms matter:
 //   * Pc_dist, dist = cv::norm of CV_32F: squares summed in double in element order, one square root, then float;
@@ -25,24 +25,12 @@
 
 #include "k_keyframe_project.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct ProjQuery { float u, v, ur, radius; int minLevel, maxLevel, flags; float angle; };      // == orbx_proj_query (k_project.hip)
-static_assert(sizeof(ProjQuery) == 32, "orbx_proj_query layout");
-struct TrackRecord { float projX, projY, projXR, depth, viewCos; int level, exit; };             // == orbx_track_record
-static_assert(sizeof(TrackRecord) == 28, "orbx_track_record layout");
-
 enum { kFrustumLocalMap = 0, kFrustumRelocalization = 1 };                                        // == ORBX_FRUSTUM_LOCAL_MAP / _RELOCALIZATION
 enum { kFrustumFlag = 0, kFrustumNegDepth, kFrustumNotInImage, kFrustumDistance, kFrustumViewCos, kFrustumFar, kFrustumRequest };      // == orbx_frustum_exit
-
-struct FrustumParams {      // == orbx_internal.hpp
-    float fx, fy, cx, cy, minX, maxX, minY, maxY;      // Frame's float bounds, as they are
-    float scale[kMaxLevels];                           // mvScaleFactors of the handle
-    float breaks[kMaxLevels];                          // [k - 1]: smallest ratio whose predicted level is >= k (k = 1 .. nlevels - 1)
-    float mbf, viewCosLimit, th, thFarPoints;
-    int nlevels, mode, farPoints, mpCapacity, curFirst, curStep, mpFirst, mpStep;
-};
 
 // what a MapPoint that is not looked at carries (bit 0 of its flag clear, or beyond the list): every byte defined
 __device__ __forceinline__ TrackRecord frustumUntouched() { return TrackRecord{-1.0f, -1.0f, 0.0f, 0.0f, 0.0f, -1, kFrustumFlag}; }

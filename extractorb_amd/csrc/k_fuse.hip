@@ -29,20 +29,13 @@
 #include <stdint.h>
 
 #include "k_keyframe_project.hpp"
+#include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct FuseParams {      // == orbx_internal.hpp
-    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
-    float scale[kMaxLevels], invSigma2[kMaxLevels];      // mvScaleFactors, mvInvLevelSigma2 of the handle
-    float breaks[kMaxLevels];                            // [k - 1]: smallest ratio whose predicted level is >= k (k = 1 .. nlevels - 1)
-    float mbf, th;
-    int nlevels, thLow, reprojCheck, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
-};
-
 namespace {
-constexpr int kRows = kKfRows, kCells = kKfCells;
 enum { kExitFlag = 0, kExitNegDepth, kExitNotInImage, kExitDistance, kExitNormal, kExitEmptyWindow, kExitAboveThLow, kExitFused };      // == ORBX_FUSE_*
 }  // namespace
 
@@ -74,18 +67,18 @@ __global__ __launch_bounds__(256) void k_fuse(const float* __restrict__ mpWorld,
             // a candidate's kpLevel is level or level - 1 (:1530): the two mvInvLevelSigma2 it can need
             const float invHi = p.invSigma2[level], invLo = p.invSigma2[max(level - 1, 0)];
             const int N = min(max(nOut[f], 0), p.capacity);
-            const int* off = gridOff + f * (kCells + 1);
+            const int* off = gridOff + f * (kGridCells + 1);
             const int* gi = gridIdx + f * p.capacity;
             const Keypoint* K = kpsUn + f * p.capacity;
             const float* UR = uRight ? uRight + f * p.capacity : nullptr;
             const uint4* D = (const uint4*)(desc + f * p.capacity * 32);
-            const int nIn = min(max(off[kCells], 0), N);                                     // (clamped: a corrupt grid must not index past the frame)
+            const int nIn = min(max(off[kGridCells], 0), N);                                     // (clamped: a corrupt grid must not index past the frame)
             const uint4 dlo = *(const uint4*)(mpDesc + m * 32), dhi = *(const uint4*)(mpDesc + m * 32 + 16);
             bool any = false;
             for (int cx = minCX; cx <= maxCX; cx++) {
                 if (minCY > maxCY) break;
-                const int sEnd = min(max(off[cx * kRows + maxCY + 1], 0), nIn);
-                for (int s = min(max(off[cx * kRows + minCY], 0), nIn); s < sEnd; s++) {
+                const int sEnd = min(max(off[cx * kGridRows + maxCY + 1], 0), nIn);
+                for (int s = min(max(off[cx * kGridRows + minCY], 0), nIn); s < sEnd; s++) {
                     const int idx = min(max(gi[s], 0), p.capacity - 1);
                     const float kx = K[idx].x, ky = K[idx].y;
                     if (!(fabsf(__fsub_rn(kx, u)) < r && fabsf(__fsub_rn(ky, v)) < r)) continue;      // KeyFrame.cc:804-808
@@ -103,8 +96,7 @@ __global__ __launch_bounds__(256) void k_fuse(const float* __restrict__ mpWorld,
                         } else if ((double)__fmul_rn(e2m, inv) > 5.99) continue;             // :1547-1557
                     }
                     const uint4 e = D[2 * idx], g = D[2 * idx + 1];
-                    const int dist = __popc(dlo.x ^ e.x) + __popc(dlo.y ^ e.y) + __popc(dlo.z ^ e.z) + __popc(dlo.w ^ e.w) + __popc(dhi.x ^ g.x) +
-                                     __popc(dhi.y ^ g.y) + __popc(dhi.z ^ g.z) + __popc(dhi.w ^ g.w);
+                    const int dist = hamming256(dlo, dhi, e, g);
                     if (dist < bestDist) { bestDist = dist; bestIdx = idx; }                 // :1565, strict: the first of equals stays
                 }
             }

@@ -10,15 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_params.hpp"
+
 namespace orbx {
 
 constexpr size_t kPolluteBytes = 158 * 1024;      // one workgroup per CU (160 KB of LDS each)
-
-
-struct GrayParams {
-    int rows, cols, channels, redFirst, aligned;
-    long long srcStride, srcFrame, dstStride, dstFrame;
-};
 
 __device__ __forceinline__ unsigned grayOf(unsigned c0, unsigned c1, unsigned c2, bool redFirst) {
     const unsigned r = redFirst ? c0 : c2, b = redFirst ? c2 : c0;

@@ -14,11 +14,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
 
 namespace orbx {
 
-constexpr int kKfCols = 64, kKfRows = 48, kKfCells = kKfCols * kKfRows;
 enum { kProjectPinhole = 0, kProjectInvZ = 1 };
 // where the front end leaves a MapPoint: == ORBX_FUSE_* / ORBX_SIM3_SEARCH_* 1 .. 5; kFrontPassed = it reached the window scan
 enum { kFrontNegDepth = 1, kFrontNotInImage = 2, kFrontDistance = 3, kFrontNormal = 4, kFrontEmptyWindow = 5, kFrontPassed = 6 };
@@ -28,16 +28,6 @@ struct KfProjection {
     int level;                // MapPoint::PredictScale
     int minCX, maxCX, minCY, maxCY;
 };
-
-// one row of cv::gemm on 3x3 * 3x1 float data: products and sums in double (each rounded), scaled, C added, rounded to float once
-__device__ __forceinline__ float gemmRow(float a0, float a1, float a2, const float (&b)[3], double alpha, float c, bool hasC) {
-    double s = __dmul_rn((double)a0, (double)b[0]);
-    s = __dadd_rn(s, __dmul_rn((double)a1, (double)b[1]));
-    s = __dadd_rn(s, __dmul_rn((double)a2, (double)b[2]));
-    s = __dmul_rn(s, alpha);
-    if (hasC) s = __dadd_rn(s, (double)c);
-    return (float)s;
-}
 
 // MapPoint::PredictScale as a count of breakpoints (ascending; NaN is above none, +inf above all).  P: nlevels, breaks[].
 // Shared with the frustum test of k_frustum_point.hpp.
@@ -87,13 +77,13 @@ __device__ __forceinline__ int projectIntoKeyFrame(const float* __restrict__ T, 
     const int level = predictScaleLevel(ratio, p);
     const float r = __fmul_rn(p.th, p.scale[level]);                                 // :1505, :543
     // KeyFrame::GetFeaturesInArea's cell window with its four early returns (KeyFrame.cc:778-792)
-    const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, p.minX), r), p.wInv)));
-    if (minCX >= kKfCols) return kFrontEmptyWindow;
-    const int maxCX = min(kKfCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, p.minX), r), p.wInv)));
+    const int minCX = cellWindowMin(u, p.minX, r, p.wInv);
+    if (minCX >= kGridCols) return kFrontEmptyWindow;
+    const int maxCX = cellWindowMax(u, p.minX, r, p.wInv, kGridCols);
     if (maxCX < 0) return kFrontEmptyWindow;
-    const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, p.minY), r), p.hInv)));
-    if (minCY >= kKfRows) return kFrontEmptyWindow;
-    const int maxCY = min(kKfRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, p.minY), r), p.hInv)));
+    const int minCY = cellWindowMin(v, p.minY, r, p.hInv);
+    if (minCY >= kGridRows) return kFrontEmptyWindow;
+    const int maxCY = cellWindowMax(v, p.minY, r, p.hInv, kGridRows);
     if (maxCY < 0) return kFrontEmptyWindow;
     o.u = u; o.v = v; o.invz = invz; o.r = r; o.level = level;
     o.minCX = minCX; o.maxCX = maxCX; o.minCY = minCY; o.maxCY = maxCY;

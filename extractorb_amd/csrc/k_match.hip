@@ -21,41 +21,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct InitMatchParams {
-    float minX, minY, wInv, hInv;   // mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv of frame 2
-    float r, nnRatio;               // windowSize as float (Frame.cc:660-661), mfNNratio
-    int checkOrientation, capacity;
-    int slotCapacity;               // level-0 keypoints of frame 2 the LDS tables hold (a multiple of 4)
-    int f1First, f1Step, f2First, f2Step;
-};
-
 namespace {
-constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
-constexpr int kThLow = 50, kHistoLength = 30;           // ORBmatcher.cc:37-38
+constexpr int kThLow = 50;                               // ORBmatcher.cc:37
 constexpr int kNone = 0x7FFF;                            // "INT_MAX" of the 16-bit distance fields
 constexpr int kThreads = 1024, kWaves = kThreads / 64;
 constexpr int kAcc = 2;                                  // holders of a slot kept per round (more: answered by a scan of the decisions)
 constexpr unsigned kNoDec = 0xFFFFFFFFu;
-
-__device__ __forceinline__ int bcast(int v, int srcLane) { return __builtin_amdgcn_readlane(v, srcLane); }
-__device__ __forceinline__ float bcastf(float v, int srcLane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srcLane)); }
-
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int dppMin(int v) { return min(v, __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xF, false)); }
-// minimum over the 64 lanes, returned wave-uniform
-__device__ __forceinline__ int waveMin(int v) {
-    v = dppMin<0xB1, 0xF>(v);     // quad_perm [1,0,3,2]
-    v = dppMin<0x4E, 0xF>(v);     // quad_perm [2,3,0,1]
-    v = dppMin<0x141, 0xF>(v);    // row_half_mirror
-    v = dppMin<0x140, 0xF>(v);    // row_mirror: every lane of a row holds the row's minimum
-    v = dppMin<0x142, 0xA>(v);    // row_bcast:15 into rows 1 and 3
-    v = dppMin<0x143, 0xC>(v);    // row_bcast:31 into rows 2 and 3
-    return __builtin_amdgcn_readlane(v, 63);
-}
 }  // namespace
 
 // LDS: per staged (level-0) keypoint of frame 2 its descriptor, position, cell, index and the holder list (32 + 8 + 2 + 2 + 4 + 8 = 56 B);
@@ -65,11 +42,11 @@ __device__ __forceinline__ int waveMin(int v) {
 size_t initMatchLdsBytes(int capacity, int slotCapacity) {
     (void)capacity;
     const size_t sc = (size_t)((slotCapacity + 3) & ~3);
-    return sc * (32 + 8 + 2 + 2 + 4 + 4 * kAcc + 2 + 4 + 4) + (kCols + 2 + kHistoLength + 8) * sizeof(int) + 2 * kWaves * sizeof(int) + 64;
+    return sc * (32 + 8 + 2 + 2 + 4 + 4 * kAcc + 2 + 4 + 4) + (kGridCols + 2 + kHistoLength + 8) * sizeof(int) + 2 * kWaves * sizeof(int) + 64;
 }
 // the largest table (slots = requests) that fits a workgroup's LDS
 int initMatchSlotCapacity(int capacity) {
-    const long long room = 160LL * 1024 - 1024 - (long long)((kCols + 2 + kHistoLength + 8) * sizeof(int) + 2 * kWaves * sizeof(int) + 64);
+    const long long room = 160LL * 1024 - 1024 - (long long)((kGridCols + 2 + kHistoLength + 8) * sizeof(int) + 2 * kWaves * sizeof(int) + 64);
     const long long sc = room / (32 + 8 + 2 + 2 + 4 + 4 * kAcc + 2 + 4 + 4);
     return (int)(sc < capacity ? sc & ~3LL : (capacity + 3) & ~3);
 }
@@ -89,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
     unsigned* decA = (unsigned*)(accCnt + capA);           // [capA] decision of request r: distance << 16 | slot, or kNoDec
     unsigned* decB = decA + capA;                          // [capA] (the other buffer: decisions are read by others while new ones are written)
     int* colStart = (int*)(decB + capA);                   // [66] first slot of cell column c (c = 64, 65: n2)
-    int* hist = colStart + kCols + 2;                      // [30] rotHist sizes
+    int* hist = colStart + kGridCols + 2;                  // [30] rotHist sizes
     int* flags = hist + kHistoLength;                      // [8] changed (two alternating), matches, dropped, requests
     int* wcnt = flags + 8;                                 // [2][kWaves] compaction counts
     unsigned short* cell2 = (unsigned short*)(wcnt + 2 * kWaves);  // [capA] ix << 8 | iy
@@ -103,11 +80,11 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
     const Keypoint* K2 = kpsUn + (long long)f2 * cap;
     const uint32_t* D1 = (const uint32_t*)(desc + (long long)f1 * cap * 32);
     const uint32_t* D2 = (const uint32_t*)(desc + (long long)f2 * cap * 32);
-    const int* off2 = gridOff + (long long)f2 * (kCells + 1);
+    const int* off2 = gridOff + (long long)f2 * (kGridCells + 1);
     const int* gi2 = gridIdx + (long long)f2 * cap;
     float* prev = prevMatched + (long long)pair * cap * 2;
     int* out = matches12 + (long long)pair * cap;
-    const int nIn2 = min(off2[kCells], N2);
+    const int nIn2 = min(off2[kGridCells], N2);
     if (tid < kHistoLength) hist[tid] = 0;
     if (tid < 8) flags[tid] = 0;
 
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
     }
     for (int i = tid; i < capA; i += kThreads) { accCnt[i] = 0; decA[i] = kNoDec; decB[i] = kNoDec; }
     __syncthreads();
-    if (tid < kCols + 2) {      // first slot whose cell column is >= tid (slots are sorted by column)
+    if (tid < kGridCols + 2) {      // first slot whose cell column is >= tid (slots are sorted by column)
         int lo = 0, hi = n2;
         while (lo < hi) { const int mid = (lo + hi) >> 1; if ((cell2[mid] >> 8) < tid) lo = mid + 1; else hi = mid; }
         colStart[tid] = lo;
@@ -181,12 +158,8 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
     auto decide = [&](int r) -> unsigned {
         const int i1 = req[r];
         const float px = prev[2 * i1], py = prev[2 * i1 + 1];
-        // GetFeaturesInArea's cell window (Frame.cc:666-688); an empty window is "no candidates"
-        const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(px, p.minX), p.r), p.wInv)));
-        const int maxCX = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(px, p.minX), p.r), p.wInv)));
-        const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(py, p.minY), p.r), p.hInv)));
-        const int maxCY = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(py, p.minY), p.r), p.hInv)));
-        if (minCX >= kCols || maxCX < 0 || minCY >= kRows || maxCY < 0 || minCX > maxCX || minCY > maxCY) return kNoDec;
+        int minCX, maxCX, minCY, maxCY;
+        if (!frameCellWindow(px, py, p.r, p, minCX, maxCX, minCY, maxCY)) return kNoDec;      // Frame.cc:666-688; an empty window is "no candidates"
         const uint4 a = *(const uint4*)(D1 + (long long)i1 * 8), b = *(const uint4*)(D1 + (long long)i1 * 8 + 4);
         int bestDist = kNone, bestDist2 = kNone, bs = 0;
         const int sEnd = colStart[maxCX + 1];
@@ -195,8 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
             const float2 q = xy2[s];
             if (cy < minCY || cy > maxCY || !(fabsf(__fsub_rn(q.x, px)) < p.r) || !(fabsf(__fsub_rn(q.y, py)) < p.r)) continue;      // Frame.cc:717
             const uint4 e = d2[2 * s], g = d2[2 * s + 1];
-            const int dist = __popc(a.x ^ e.x) + __popc(a.y ^ e.y) + __popc(a.z ^ e.z) + __popc(a.w ^ e.w) + __popc(b.x ^ g.x) +
-                             __popc(b.y ^ g.y) + __popc(b.z ^ g.z) + __popc(b.w ^ g.w);
+            const int dist = hamming256(a, b, e, g);
             if (mdBefore(s, r) <= dist) continue;                                                                // :744-745
             if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bs = s; }                              // :747-752
             else if (dist < bestDist2) bestDist2 = dist;                                                         // :753-756
@@ -234,7 +206,6 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
     int* own = accCnt;
     for (int s = tid; s < n2; s += kThreads) own[s] = -1;
     __syncthreads();
-    const float factor = 1.0f / kHistoLength;
     for (int r = tid; r < R; r += kThreads) {
         const unsigned d = decCur[r];
         decNew[r] = 0xFFu;                                  // (now: the request's rotHist bin, 255 = none)
@@ -242,27 +213,14 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
         const int s = (int)(d & 0xFFFFu);
         atomicMax(&own[s], r);
         if (p.checkOrientation) {                                                                                // :773-783
-            float rot = __fsub_rn(K1[req[r]].angle, K2[idx2[s]].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, factor));
-            if (bin == kHistoLength) bin = 0;
+            const int bin = rotationBin(K1[req[r]].angle, K2[idx2[s]].angle);
             decNew[r] = (unsigned)bin;
             atomicAdd(&hist[bin], 1);
         }
     }
     __syncthreads();
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    if (p.checkOrientation) {                                                                                  // ComputeThreeMaxima
-        int max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-    }
+    ThreeMaxima top{-1, -1, -1};
+    if (p.checkOrientation) top = computeThreeMaxima(hist);
     int kept = 0;
     for (int r = tid; r < R; r += kThreads) {
         const unsigned d = decCur[r];
@@ -270,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
         const int s = (int)(d & 0xFFFFu), i1 = req[r];
         if (own[s] != r) continue;                                                         // stolen later (:763-767): stays -1
         const int b = (int)decNew[r];
-        if (p.checkOrientation && b != ind1 && b != ind2 && b != ind3) continue;           // :797-808
+        if (p.checkOrientation && b != top.ind1 && b != top.ind2 && b != top.ind3) continue;           // :797-808
         const int m = idx2[s];
         out[i1] = m;
         const Keypoint k = K2[m];

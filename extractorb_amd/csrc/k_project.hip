@@ -25,57 +25,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct ProjQuery { float u, v, ur, radius; int minLevel, maxLevel, flags; float angle; };   // == orbx_proj_query
-static_assert(sizeof(ProjQuery) == 32, "orbx_proj_query layout");
-
-struct ProjectParams {
-    float fx, fy, cx, cy, minX, maxX, minY, maxY;
-    float scale[kMaxLevels];
-    float mbf, mb, th;
-    int mono, capacity, lastFirst, lastStep, curFirst, curStep;
-};
-
-struct ProjSearchParams {
-    float minX, minY, wInv, hInv, nnRatio;
-    int ratioMode, checkOrientation, capacity, queryCapacity, curFirst, curStep, descFirst, descStep, maxDist;
-};
-
 namespace {
-constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
-constexpr int kHistoLength = 30;                          // ORBmatcher.cc:38 (the distance bound, TH_HIGH = 100 or the caller's ORBdist, is a parameter)
 constexpr int kNoneKey = (256 << 16) | 0xFFFF;            // bestDist = 256, no position
 constexpr int kTop = 4;                                   // best keys a request remembers between rounds
 constexpr unsigned kNoDecision = 0xFFFFFFFFu;             // the request is inactive, finds nothing or is rejected
 constexpr int kThreads = 1024;     // one request per thread per round at ~1000 requests; 16 waves hide the LDS latency of the window scans (256 threads: 111 us for the first scan)
-
-__device__ __forceinline__ int bcast(int v, int srcLane) { return __builtin_amdgcn_readlane(v, srcLane); }
-__device__ __forceinline__ float bcastf(float v, int srcLane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srcLane)); }
-
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int dppMin(int v) { return min(v, __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xF, false)); }
-__device__ __forceinline__ int waveMin(int v) {          // minimum over the 64 lanes, wave-uniform
-    v = dppMin<0xB1, 0xF>(v);
-    v = dppMin<0x4E, 0xF>(v);
-    v = dppMin<0x141, 0xF>(v);
-    v = dppMin<0x140, 0xF>(v);
-    v = dppMin<0x142, 0xA>(v);
-    v = dppMin<0x143, 0xC>(v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// one row of cv::gemm on 3x3 * 3x1 float data: products and sums in double (each rounded), scaled, C added, rounded to float once
-__device__ __forceinline__ float gemmRow(float a0, float a1, float a2, const float (&b)[3], double alpha, float c, bool hasC) {
-    double s = __dmul_rn((double)a0, (double)b[0]);
-    s = __dadd_rn(s, __dmul_rn((double)a1, (double)b[1]));
-    s = __dadd_rn(s, __dmul_rn((double)a2, (double)b[2]));
-    s = __dmul_rn(s, alpha);
-    if (hasC) s = __dadd_rn(s, (double)c);
-    return (float)s;
-}
+// (the distance bound, TH_HIGH = 100 or the caller's ORBdist, is a parameter)
 }  // namespace
 
 // grid (ceil(capacity / 256), n_pairs).  Tcw: one 3x4 row-major pose per FRAME.
@@ -121,7 +82,7 @@ __global__ __launch_bounds__(256) void k_project_last(const Keypoint* __restrict
 
 size_t projSearchLdsBytes(int capacity, int queryCapacity, bool topList) {
     const size_t c = (size_t)((capacity + 3) & ~3);
-    return c * (32 + 16 + 4 + 4 + 2 + 1 + 1 + 2) + (kHistoLength + 4) * sizeof(int) + (kCells + 2) * sizeof(unsigned short) +
+    return c * (32 + 16 + 4 + 4 + 2 + 1 + 1 + 2) + (kHistoLength + 4) * sizeof(int) + (kGridCells + 2) * sizeof(unsigned short) +
            (size_t)queryCapacity * (4 + 1 + (topList ? 4 * kTop : 0)) + 64;
 }
 __device__ int g_searchRounds[4];      // diagnostics: rounds the last launch's pair 0 needed (projection search, initialisation search)
@@ -147,8 +108,8 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
     unsigned* dec = (unsigned*)(top + (TOPLIST ? (long long)p.queryCapacity * kTop : 0));      // [queryCapacity] decision of every request: slot | closes << 16, or kNoDecision
     int* hist = (int*)(dec + p.queryCapacity);             // [30] rotHist sizes
     int* flags = hist + kHistoLength;                      // [3] "a decision changed" (two alternating slots), number of accepted requests
-    unsigned short* cellOff = (unsigned short*)(flags + 4);      // [kCells + 2] slot range of every grid cell (mGrid's CSR offsets)
-    unsigned short* idx2 = cellOff + kCells + 2;           // keypoint index in the frame
+    unsigned short* cellOff = (unsigned short*)(flags + 4);      // [kGridCells + 2] slot range of every grid cell (mGrid's CSR offsets)
+    unsigned short* idx2 = cellOff + kGridCells + 2;           // keypoint index in the frame
     uint8_t* oct2 = (uint8_t*)(idx2 + capA);               // octave
     uint8_t* occ = oct2 + capA;                            // holds a MapPoint with Observations() > 0
     uint8_t* qflag = occ + capA;                           // [queryCapacity] orbx_proj_query::flags
@@ -158,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
     const int N2 = min(nOut[f2], cap);
     const Keypoint* K2 = kpsUn + (long long)f2 * cap;
     const uint32_t* D2 = (const uint32_t*)(desc + (long long)f2 * cap * 32);
-    const int* off2 = gridOff + (long long)f2 * (kCells + 1);
+    const int* off2 = gridOff + (long long)f2 * (kGridCells + 1);
     const int* gi2 = gridIdx + (long long)f2 * cap;
     const float* UR = uRight ? uRight + (long long)f2 * cap : nullptr;
     uint8_t* occIO = occupied ? occupied + (long long)pair * cap : nullptr;
@@ -166,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
     const uint32_t* QD = (const uint32_t*)(qdesc + (long long)(p.descFirst + pair * p.descStep) * p.queryCapacity * 32);
     const int NQ = nQueries ? min(nQueries[pair], p.queryCapacity) : p.queryCapacity;
     int* out = matches + (long long)pair * cap;
-    const int nIn2 = min(off2[kCells], N2);
+    const int nIn2 = min(off2[kGridCells], N2);
 
     // ---- stage the frame's keypoints in grid order (every octave: the level window differs per request) ----
     const unsigned long long tStart = __builtin_amdgcn_s_memrealtime();
@@ -184,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
         d2[2 * slot] = lo; d2[2 * slot + 1] = hi;
     }
     for (int i = tid; i < cap; i += kThreads) out[i] = -1;     // keypoints outside the grid can never match
-    for (int c = tid; c <= kCells; c += kThreads) cellOff[c] = (unsigned short)min(off2[c], n2);      // mGrid's CSR offsets: slot range of every cell
+    for (int c = tid; c <= kGridCells; c += kThreads) cellOff[c] = (unsigned short)min(off2[c], n2);      // mGrid's CSR offsets: slot range of every cell
     for (int i = tid; i < NQ; i += kThreads) dec[i] = kNoDecision;
     if (tid < kHistoLength) hist[tid] = 0;
     if (tid == 0) { flags[0] = 0; flags[1] = 0; flags[2] = 0; }
@@ -200,7 +161,6 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
     //      depends only on decisions of requests < i), so the fixed point IS the sequential result; real frames settle in 3-6 rounds
     //      instead of a thousand dependent steps. ----
     const unsigned long long tStaged = __builtin_amdgcn_s_memrealtime();
-    const float factor = 1.0f / kHistoLength;
     // the kTop smallest keys (distance << 16 | slot) of a request's window, ascending, among the keypoints that pass the static tests
     // (cell window, level, box, stereo column, not closed on entry) and - if `live` - are not closed for this request right now
     auto scan = [&](int iq, bool live, int (&keys)[kTop]) -> int {
@@ -209,19 +169,15 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
         const ProjQuery q = Q[iq];
         if (!(q.flags & 1)) return 0;
         const float r = q.radius;
-        // GetFeaturesInArea's cell window (Frame.cc:666-688); an empty window is "no candidates"
-        const int minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(q.u, p.minX), r), p.wInv)));
-        const int maxCX = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(q.u, p.minX), r), p.wInv)));
-        const int minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(q.v, p.minY), r), p.hInv)));
-        const int maxCY = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(q.v, p.minY), r), p.hInv)));
-        if (minCX >= kCols || maxCX < 0 || minCY >= kRows || maxCY < 0 || minCX > maxCX || minCY > maxCY) return q.flags;
+        int minCX, maxCX, minCY, maxCY;
+        if (!frameCellWindow(q.u, q.v, r, p, minCX, maxCX, minCY, maxCY)) return q.flags;      // Frame.cc:666-688; an empty window is "no candidates"
         // level filter of GetFeaturesInArea (:690, :705-712) as an inclusive range; without bCheckLevels everything passes
         const bool checkLevels = q.minLevel > 0 || q.maxLevel >= 0;
         const int loLv = checkLevels ? max(q.minLevel, 0) : 0, hiLv = checkLevels && q.maxLevel >= 0 ? min(q.maxLevel, 255) : 255;
         const uint4 dlo = *(const uint4*)(QD + (long long)iq * 8), dhi = *(const uint4*)(QD + (long long)iq * 8 + 4);
         for (int cx = minCX; cx <= maxCX; cx++) {          // ascending cells, push_back order inside a cell = ascending slots (Frame.cc:690-720)
-            const int sEnd = cellOff[cx * kRows + maxCY + 1];
-            for (int s = cellOff[cx * kRows + minCY]; s < sEnd; s++) {
+            const int sEnd = cellOff[cx * kGridRows + maxCY + 1];
+            for (int s = cellOff[cx * kGridRows + minCY]; s < sEnd; s++) {
                 const float4 rc = rec[s];
                 const int lv = __float_as_int(rc.w);
                 const float distx = __fsub_rn(rc.x, q.u), disty = __fsub_rn(rc.y, q.v), us = rc.z;
@@ -231,11 +187,11 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
                                 (int)(live ? !(cb < iq) : cb != -1) & (int)!stereoOut;                                 // Frame.cc:717; :64-66
                 if (in) {
                     const uint4 e = d2[2 * s], f = d2[2 * s + 1];
-                    const int dist = __popc(dlo.x ^ e.x) + __popc(dlo.y ^ e.y) + __popc(dlo.z ^ e.z) + __popc(dlo.w ^ e.w) + __popc(dhi.x ^ f.x) +
-                                     __popc(dhi.y ^ f.y) + __popc(dhi.z ^ f.z) + __popc(dhi.w ^ f.w);
-                    int k = (dist << 16) | s;              // slots ascend: a later equal distance never displaces
+                    int k = (hamming256(dlo, dhi, e, f) << 16) | s;      // slots ascend: a later equal distance never displaces
+                    // sortedInsert(keys, k) written out: as a call this loop kept six more register copies per candidate and the search
+                    // measured 3 % slower at 256 pairs (profiles/r12_shared_helpers_ab.md)
 #pragma unroll
-                    for (int t = 0; t < kTop; t++) { const int lo = min(keys[t], k); k = max(keys[t], k); keys[t] = lo; }      // sorted insert
+                    for (int t = 0; t < kTop; t++) { const int lo = min(keys[t], k); k = max(keys[t], k); keys[t] = lo; }
                 }
             }
         }
@@ -318,10 +274,7 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
         atomicMax(&m2q[bs], iq);
         nm++;
         if (!p.ratioMode && p.checkOrientation) {                                                                  // :2064-2080
-            float rot = __fsub_rn(Q[iq].angle, a2[bs]);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, factor));
-            if (bin == kHistoLength) bin = 0;
+            const int bin = rotationBin(Q[iq].angle, a2[bs]);
             atomicOr(&binMask[bs], 1u << bin);
             atomicAdd(&hist[bin], 1);
         }
@@ -332,17 +285,9 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
     unsigned dropBins = 0u;
     int droppedCount = 0;
     if (!p.ratioMode && p.checkOrientation) {                                                                  // ComputeThreeMaxima
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top3 = computeThreeMaxima(hist);
         for (int i = 0; i < kHistoLength; i++)
-            if (i != ind1 && i != ind2 && i != ind3) { dropBins |= 1u << i; droppedCount += hist[i]; }             // :2166-2170: one nmatches-- per entry
+            if (i != top3.ind1 && i != top3.ind2 && i != top3.ind3) { dropBins |= 1u << i; droppedCount += hist[i]; }             // :2166-2170: one nmatches-- per entry
     }
     for (int s = tid; s < n2; s += kThreads) {
         const bool dropped = (binMask[s] & dropBins) != 0u;

@@ -28,17 +28,11 @@
 
 #include "k_keyframe_project.hpp"
 #include "k_sim3_decide.hpp"
+#include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
-
-struct Sim3SearchParams {      // == orbx_internal.hpp
-    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
-    float scale[kMaxLevels];       // mvScaleFactors of the handle
-    float breaks[kMaxLevels];      // PredictScale's breakpoints
-    float th;
-    int nlevels, maxDist, projection, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
-};
 
 namespace {
 enum { kSim3Flag = 0, kSim3NoMatch = 6, kSim3Matched = 7 };      // == ORBX_SIM3_SEARCH_*; 1 .. 5 are the front end's
@@ -62,11 +56,11 @@ struct Sim3KeyFrame {
 __device__ __forceinline__ Sim3KeyFrame sim3KeyFrame(long long f, int pair, const Keypoint* kpsUn, const uint8_t* desc, const int* nOut,
                                                      const int* gridOff, const int* gridIdx, const uint8_t* occupied, int capacity) {
     Sim3KeyFrame k;
-    k.off = gridOff + f * (kKfCells + 1); k.gi = gridIdx + f * capacity; k.K = kpsUn + f * capacity;
+    k.off = gridOff + f * (kGridCells + 1); k.gi = gridIdx + f * capacity; k.K = kpsUn + f * capacity;
     k.D = (const uint4*)(desc + f * capacity * 32);
     k.occ = occupied ? occupied + (long long)pair * capacity : nullptr;
     const int N = min(max(nOut[f], 0), capacity);
-    k.nIn = min(max(k.off[kKfCells], 0), N);      // (clamped: a corrupt grid must not index past the frame - or past closedBy)
+    k.nIn = min(max(k.off[kGridCells], 0), N);      // (clamped: a corrupt grid must not index past the frame - or past closedBy)
     k.capacity = capacity;
     return k;
 }
@@ -81,8 +75,8 @@ __device__ __forceinline__ int sim3Scan(const KfProjection& q, const Sim3KeyFram
     any = false;
     for (int cx = q.minCX; cx <= q.maxCX; cx++) {
         if (q.minCY > q.maxCY) break;
-        const int sEnd = min(max(kf.off[cx * kKfRows + q.maxCY + 1], 0), kf.nIn);
-        for (int s = min(max(kf.off[cx * kKfRows + q.minCY], 0), kf.nIn); s < sEnd; s++) {
+        const int sEnd = min(max(kf.off[cx * kGridRows + q.maxCY + 1], 0), kf.nIn);
+        for (int s = min(max(kf.off[cx * kGridRows + q.minCY], 0), kf.nIn); s < sEnd; s++) {
             const int idx = min(max(kf.gi[s], 0), kf.capacity - 1);
             const float kx = kf.K[idx].x, ky = kf.K[idx].y;
             if (!(fabsf(__fsub_rn(kx, q.u)) < q.r && fabsf(__fsub_rn(ky, q.v)) < q.r)) continue;      // KeyFrame.cc:804-808
@@ -92,13 +86,10 @@ __device__ __forceinline__ int sim3Scan(const KfProjection& q, const Sim3KeyFram
             const int lv = kf.K[idx].octave;
             if (lv < q.level - 1 || lv > q.level) continue;                          // :563, :680
             const uint4 e = kf.D[2 * idx], g = kf.D[2 * idx + 1];
-            const int dist = __popc(dlo.x ^ e.x) + __popc(dlo.y ^ e.y) + __popc(dlo.z ^ e.z) + __popc(dlo.w ^ e.w) + __popc(dhi.x ^ g.x) +
-                             __popc(dhi.y ^ g.y) + __popc(dhi.z ^ g.z) + __popc(dhi.w ^ g.w);
+            const int dist = hamming256(dlo, dhi, e, g);
             if (dist > maxDist) continue;                                            // :577, :694 (header: applied before the minimum, same result)
             count++;
-            int k = (dist << 16) | s;                    // slots are distinct, so keys are: the sorted insert keeps the first of equal distances
-#pragma unroll
-            for (int t = 0; t < kSim3Top; t++) { const int lo = min(keys[t], k); k = max(keys[t], k); keys[t] = lo; }
+            sortedInsert(keys, (dist << 16) | s);        // slots are distinct, so keys are: the sorted insert keeps the first of equal distances
         }
     }
     return count;
@@ -204,7 +195,7 @@ __global__ __launch_bounds__(kSettleThreads) void k_sim3_settle(const uint8_t* _
     const long long f = p.kfFirst + (long long)pair * p.kfStep;
     const int* gi = gridIdx + f * p.capacity;
     const int N = min(max(nOut[f], 0), p.capacity);
-    const int nIn = min(max(gridOff[f * (kKfCells + 1) + kKfCells], 0), N);      // as sim3KeyFrame: every slot of a key is below it
+    const int nIn = min(max(gridOff[f * (kGridCells + 1) + kGridCells], 0), N);      // as sim3KeyFrame: every slot of a key is below it
     int* out = matches + (long long)pair * p.capacity;
     for (int s = tid; s < p.capacity; s += kSettleThreads) { closedBy[s] = 0x7fffffff; out[s] = -1; }
     for (int i = tid; i < p.mpCapacity; i += kSettleThreads) dec[i] = kSim3NoKey;

@@ -26,43 +26,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
+#include "k_wave_min.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct ProjQuery { float u, v, ur, radius; int minLevel, maxLevel, flags; float angle; };   // == orbx_proj_query
-static_assert(sizeof(ProjQuery) == 32, "orbx_proj_query layout");
-
-struct TwoEyesSearchParams {      // == orbx_internal.hpp
-    float minX, minY, wInv, hInv, nnRatio;
-    int capacity, queryCapacity, pairFirst, pairStep, descFirst, descStep, maxDist, forceWalk;
-};
-
 namespace {
-constexpr int kCols = 64, kRows = 48, kCells = kCols * kRows;
-constexpr int kCellTab = kCells + 2;                      // cell offsets per eye (kCells + 1 used)
+constexpr int kCellTab = kGridCells + 2;                  // cell offsets per eye (kGridCells + 1 used)
 constexpr int kNoneKey = (256 << 16) | 0xFFFF;            // bestDist = 256, no slot
 constexpr unsigned kNoDecision = 0xFFFFFFFFu;             // inactive, no candidate or best above the bound (the MapPoint's R still runs)
 constexpr unsigned kRatioReject = 0xFFFFFFFEu;            // rejected by the ratio test (:127 / :191): an L so rejected suppresses its R
 constexpr unsigned short kNoSlot = 0xFFFF;
 constexpr int kOpen = 0x7fffffff;
 constexpr int kThreads = 1024;
-
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int dppMin(int v) { return min(v, __builtin_amdgcn_update_dpp(v, v, CTRL, ROWMASK, 0xF, false)); }
-__device__ __forceinline__ int waveMin(int v) {          // minimum over the 64 lanes, wave-uniform
-    v = dppMin<0xB1, 0xF>(v);
-    v = dppMin<0x4E, 0xF>(v);
-    v = dppMin<0x141, 0xF>(v);
-    v = dppMin<0x140, 0xF>(v);
-    v = dppMin<0x142, 0xA>(v);
-    v = dppMin<0x143, 0xC>(v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ int hamming(const uint4& a, const uint4& b, const uint4& c, const uint4& d) {
-    return __popc(a.x ^ c.x) + __popc(a.y ^ c.y) + __popc(a.z ^ c.z) + __popc(a.w ^ c.w) + __popc(b.x ^ d.x) + __popc(b.y ^ d.y) +
-           __popc(b.z ^ d.z) + __popc(b.w ^ d.w);
-}
 }  // namespace
 
 size_t twoEyesSearchLdsBytes(int capacity, int queryCapacity) {
@@ -104,8 +82,8 @@ __global__ __launch_bounds__(kThreads) void k_search_proj_two_eyes(const ProjQue
     const int pair = blockIdx.x, tid = threadIdx.x;
     const int fL = 2 * (p.pairFirst + pair * p.pairStep), fR = fL + 1;
     const int NL = min(max(nOut[fL], 0), cap), NR = min(max(nOut[fR], 0), cap);
-    const int nInL = min(max(gridOff[(long long)fL * (kCells + 1) + kCells], 0), NL);
-    const int nInR = min(max(gridOff[(long long)fR * (kCells + 1) + kCells], 0), NR);
+    const int nInL = min(max(gridOff[(long long)fL * (kGridCells + 1) + kGridCells], 0), NL);
+    const int nInR = min(max(gridOff[(long long)fR * (kGridCells + 1) + kGridCells], 0), NR);
     const ProjQuery* Q = queries + (long long)pair * p.queryCapacity * 2;
     const uint32_t* QD = (const uint32_t*)(qdesc + (long long)(p.descFirst + pair * p.descStep) * p.queryCapacity * 32);
     const int NQ = nQueries ? min(max(nQueries[pair], 0), p.queryCapacity) : p.queryCapacity;
@@ -129,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void k_search_proj_two_eyes(const ProjQue
     }
     for (int c = tid; c < 2 * kCellTab; c += kThreads) {
         const int e = c >= kCellTab, cc = c - e * kCellTab, nIn = e ? nInR : nInL;
-        const int o = cc <= kCells ? gridOff[(long long)(fL + e) * (kCells + 1) + cc] : nIn;
+        const int o = cc <= kGridCells ? gridOff[(long long)(fL + e) * (kGridCells + 1) + cc] : nIn;
         cellOff[c] = (unsigned short)(e * capA + min(max(o, 0), nIn));
     }
     for (int j = tid; j < 2 * NQ; j += kThreads) dec[j] = kNoDecision;
@@ -157,15 +135,6 @@ __global__ __launch_bounds__(kThreads) void k_search_proj_two_eyes(const ProjQue
     }
     __syncthreads();
 
-    // GetFeaturesInArea's cell window (Frame.cc:666-688); false: empty, no candidates
-    auto window = [&](const ProjQuery& q, int& minCX, int& maxCX, int& minCY, int& maxCY) -> bool {
-        const float r = q.radius;
-        minCX = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(q.u, p.minX), r), p.wInv)));
-        maxCX = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(q.u, p.minX), r), p.wInv)));
-        minCY = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(q.v, p.minY), r), p.hInv)));
-        maxCY = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(q.v, p.minY), r), p.hInv)));
-        return !(minCX >= kCols || maxCX < 0 || minCY >= kRows || maxCY < 0 || minCX > maxCX || minCY > maxCY);
-    };
     // does slot s pass GetFeaturesInArea's level filter (:690, :705-712) and box test (:717)?
     auto inArea = [&](const ProjQuery& q, int s) -> bool {
         const bool checkLevels = q.minLevel > 0 || q.maxLevel >= 0;
@@ -188,14 +157,14 @@ __global__ __launch_bounds__(kThreads) void k_search_proj_two_eyes(const ProjQue
     auto decide = [&](int j, const ProjQuery& q, const uint4& dlo, const uint4& dhi, int alsoClosed) -> unsigned {
         if (!(q.flags & 1)) return kNoDecision;
         int minCX, maxCX, minCY, maxCY;
-        if (!window(q, minCX, maxCX, minCY, maxCY)) return kNoDecision;
+        if (!frameCellWindow(q.u, q.v, q.radius, p, minCX, maxCX, minCY, maxCY)) return kNoDecision;
         const int cb = (j & 1) * kCellTab;
         int key = kNoneKey, second = kNoneKey;
         for (int cx = minCX; cx <= maxCX; cx++) {          // ascending cells, push_back order inside a cell = ascending slots
-            const int sEnd = cellOff[cb + cx * kRows + maxCY + 1];
-            for (int s = cellOff[cb + cx * kRows + minCY]; s < sEnd; s++) {
+            const int sEnd = cellOff[cb + cx * kGridRows + maxCY + 1];
+            for (int s = cellOff[cb + cx * kGridRows + minCY]; s < sEnd; s++) {
                 if (closedBy[s] < j || s == alsoClosed || !inArea(q, s)) continue;      // :89-91 / :158-160
-                const int k = (hamming(dlo, dhi, d2[2 * s], d2[2 * s + 1]) << 16) | s;
+                const int k = (hamming256(dlo, dhi, d2[2 * s], d2[2 * s + 1]) << 16) | s;
                 if (k < key) { second = key; key = k; } else if (k < second) second = k;
             }
         }
@@ -260,15 +229,15 @@ __global__ __launch_bounds__(kThreads) void k_search_proj_two_eyes(const ProjQue
                 const ProjQuery q = Q[j];
                 int minCX, maxCX, minCY, maxCY;
                 unsigned d = kNoDecision;
-                if ((q.flags & 1) && window(q, minCX, maxCX, minCY, maxCY)) {
+                if ((q.flags & 1) && frameCellWindow(q.u, q.v, q.radius, p, minCX, maxCX, minCY, maxCY)) {
                     const uint4 dlo = *(const uint4*)(QD + (long long)(j >> 1) * 8), dhi = *(const uint4*)(QD + (long long)(j >> 1) * 8 + 4);
                     const int cb = (j & 1) * kCellTab;
                     int key = kNoneKey, second = kNoneKey;
                     for (int cx = minCX; cx <= maxCX; cx++) {
-                        const int sEnd = cellOff[cb + cx * kRows + maxCY + 1];
-                        for (int s = cellOff[cb + cx * kRows + minCY] + lane; s < sEnd; s += 64) {
+                        const int sEnd = cellOff[cb + cx * kGridRows + maxCY + 1];
+                        for (int s = cellOff[cb + cx * kGridRows + minCY] + lane; s < sEnd; s += 64) {
                             if ((closedBy[s] & 1) || !inArea(q, s)) continue;
-                            const int k = (hamming(dlo, dhi, d2[2 * s], d2[2 * s + 1]) << 16) | s;
+                            const int k = (hamming256(dlo, dhi, d2[2 * s], d2[2 * s + 1]) << 16) | s;
                             if (k < key) { second = key; key = k; } else if (k < second) second = k;
                         }
                     }

@@ -22,17 +22,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_match_helpers.hpp"
+#include "k_wave_min.hpp"
 #include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
-struct TriMatchParams {      // == orbx_internal.hpp
-    float scale[kMaxLevels], sigma2[kMaxLevels];      // mvScaleFactors, mvLevelSigma2 of the handle
-    int nlevels, thLow, checkOrientation, onlyStereo, coarse, capacity, kf1First, kf1Step, kf2First, kf2Step;
-};
-
 namespace {
-constexpr int kHistoLength = 30;                          // ORBmatcher.cc:38
 constexpr unsigned kNoneKey = 0xFFFFFFFFu;                // no candidate passed
 constexpr int kThreads = 1024;                            // 64 rows of 16 lanes
 constexpr int kWaves = kThreads / 64;
@@ -44,24 +41,6 @@ typedef __attribute__((address_space(3))) uint32_t LdsU32;
 typedef __attribute__((address_space(3))) int LdsInt;
 typedef __attribute__((address_space(3))) unsigned short LdsU16;
 typedef __attribute__((address_space(3))) uint8_t LdsU8;
-
-template <int CTRL>
-__device__ __forceinline__ unsigned dppMinU(unsigned v) {
-    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-    return o < v ? o : v;
-}
-// minimum over each row of 16 lanes, returned in every lane of the row
-__device__ __forceinline__ unsigned rowMin16(unsigned v) {
-    v = dppMinU<0xB1>(v);      // quad_perm [1,0,3,2]
-    v = dppMinU<0x4E>(v);      // quad_perm [2,3,0,1]
-    v = dppMinU<0x141>(v);     // row_half_mirror
-    v = dppMinU<0x140>(v);     // row_mirror
-    return v;
-}
-__device__ __forceinline__ int hamming(const U4 a, const U4 b, const U4 x, const U4 y) {      // DescriptorDistance (:2349-2365)
-    return __popc(a.x ^ x.x) + __popc(a.y ^ x.y) + __popc(a.z ^ x.z) + __popc(a.w ^ x.w) + __popc(b.x ^ y.x) + __popc(b.y ^ y.y) +
-           __popc(b.z ^ y.z) + __popc(b.w ^ y.w);
-}
 }  // namespace
 
 // per slot of the capacity rounded up to 16: keyframe 2's positions (8), two node columns (8; keyframe 1's becomes the segment ranges), the
@@ -135,7 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_search_triangulation(const uint32_
         segK[i] = (uint32_t)c0 | ((uint32_t)lo << 16);
     }
     __syncthreads();
-    const float factor = 1.0f / kHistoLength;
     for (int k = row; k < M1; k += kThreads / 16) {
         const int idx1 = (int)idxK[k];
         const unsigned fl1 = flag1[idx1], range = segK[k];
@@ -160,7 +138,7 @@ __global__ __launch_bounds__(kThreads) void k_search_triangulation(const uint32_
             U4 x, y;
             if constexpr (STAGE) { x = sDesc2[2 * idx2]; y = sDesc2[2 * idx2 + 1]; }
             else { x = desc2[2 * idx2]; y = desc2[2 * idx2 + 1]; }
-            const int dist = hamming(da, db, x, y);
+            const int dist = hamming256(da, db, x, y);
             if (dist > p.thLow) continue;                                                       // :1080 (dist > bestDist is the minimum below)
             const F2 pt = sPos2[idx2];
             const int o = oct2[idx2];
@@ -182,10 +160,7 @@ __global__ __launch_bounds__(kThreads) void k_search_triangulation(const uint32_
         const int bestIdx2 = (int)idxC[c0 + (int)(0xFFFFu - (best & 0xFFFFu))];
         m12[idx1] = bestIdx2;                                                                   // :1144
         if (p.checkOrientation) {                                                               // :1147-1157
-            float rot = __fsub_rn(kp1[idx1].angle, kp2[bestIdx2].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, factor));
-            if (bin == kHistoLength) bin = 0;
+            int bin = rotationBin(kp1[idx1].angle, kp2[bestIdx2].angle);
             bin = min(max(bin, 0), kHistoLength - 1);                                           // (the reference asserts it; an angle outside [0, 360) must not index past the table)
             binOf[idx1] = (uint8_t)bin;
             atomicAdd(&sHist[bin], 1);
@@ -194,17 +169,9 @@ __global__ __launch_bounds__(kThreads) void k_search_triangulation(const uint32_
     __syncthreads();
     unsigned dropBins = 0u;
     if (p.checkOrientation) {                                                                   // ComputeThreeMaxima (:2303-2344), then :1174-1193
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < kHistoLength; i++) {
-            const int s = sHist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top3 = computeThreeMaxima(sHist);
         for (int i = 0; i < kHistoLength; i++)
-            if (i != ind1 && i != ind2 && i != ind3) dropBins |= 1u << i;
+            if (i != top3.ind1 && i != top3.ind2 && i != top3.ind3) dropBins |= 1u << i;
     }
     // vMatches12 and vMatchedPairs in increasing keypoint index (:1195-1203): a ballot inside the wave, the waves' counts through LDS
     int* out = matches12 + (long long)pair * cap;

@@ -12,6 +12,8 @@ constexpr int kPatch = 31;       // PATCH_SIZE, ORBextractor.cc:70
 constexpr int kMaxLevels = 16;
 constexpr int kCellW = 30;       // W, ORBextractor.cc:777
 constexpr int kMinBorder = kEdge - 3;   // minBorderX/Y, ORBextractor.cc:781-782
+// FRAME_GRID_COLS / ROWS (inc/Frame.h:39-40): Frame's mGrid and KeyFrame's, as CSR with cell = x * kGridRows + y
+constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;
 
 
 struct Keypoint {             // == orbx_keypoint == cv::KeyPoint (28 bytes)

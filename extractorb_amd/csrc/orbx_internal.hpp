@@ -17,38 +17,21 @@
 
 #include "orbx.h"
 #include "orbx_geometry.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
-// launch wrappers, defined in the k_*.hip files
+// launch wrappers and LDS sizes, defined in the k_*.hip files (the parameter blocks they take: orbx_params.hpp)
 void launchPyrFirst(hipStream_t, const uint8_t*, long long, long long, const LevelGeom&, const LevelGeom*, int, int, int, int,
                     const ResizeX*, const QuadRec*, const ResizeX*, const TileFoot*, uint8_t*, int, int, bool, int, int);
 void launchResize(hipStream_t, const LevelGeom&, const LevelGeom&, int, int, const ResizeX*, const QuadRec*, const ResizeX*, const TileFoot*,
                   uint8_t*, int, int, bool, int, int);
-struct BowMatchParams { float nnRatio; int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep, twoKeyFrames; };
 size_t bowMatchLdsBytes(int capacity, bool stageDesc);
 void launchSearchBow(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowMatchParams&, int*, int*, int);
-struct BowTwoEyesParams { float nnRatio; int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep; };      // == k_bow_match_two_eyes.hip
 size_t bowTwoEyesLdsBytes(int capacity, bool stage);
 void launchSearchBowTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowTwoEyesParams&, bool, int*, int*, int);
-struct TriMatchParams {      // == k_triangulate_match.hip
-    float scale[kMaxLevels], sigma2[kMaxLevels];
-    int nlevels, thLow, checkOrientation, onlyStereo, coarse, capacity, kf1First, kf1Step, kf2First, kf2Step;
-};
 size_t triMatchLdsBytes(int capacity, bool stage);
 void launchSearchTriangulation(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const float*, const uint8_t*, const int*, const float*, const float*, const TriMatchParams&, bool, int*, int*, int*, int);
-struct FuseParams {      // == k_fuse.hip
-    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
-    float scale[kMaxLevels], invSigma2[kMaxLevels], breaks[kMaxLevels];
-    float mbf, th;
-    int nlevels, thLow, reprojCheck, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
-};
 void launchFuse(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const float*, const uint8_t*, const int*, const int*, const int*, const FuseParams&, int*, int*, uint8_t*, int*, int);
-struct Sim3SearchParams {      // == k_project_sim3.hip
-    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
-    float scale[kMaxLevels], breaks[kMaxLevels];
-    float th;
-    int nlevels, maxDist, projection, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
-};
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
@@ -65,64 +48,25 @@ void launchDescribe(hipStream_t, const LevelGeom*, int, const uint8_t*, const ui
                     const int*, Keypoint*, uint8_t*, int, int*, int*, Keypoint*, int*, bool, int, int, int, int, int, int);
 bool checkUmax(const int* umax16);
 hipError_t runPackedSelfTest(hipStream_t, unsigned*, unsigned*);
-struct StereoParams {
-    float scale[kMaxLevels], invScale[kMaxLevels];
-    float bf, b;
-    int nlevels, capacity, rowCap;
-};
-struct CameraParams { float fx, fy, cx, cy, k1, k2, p1, p2, k3; };
-struct FrameFinishParams { CameraParams cam; float minX, minY, wInv, hInv; int capacity, rawGrid; };      // (k_frame.hip holds the same layout)
 void launchFrameFinish(hipStream_t, const Keypoint*, const int*, const FrameFinishParams&, Keypoint*, int*, int*, int*, int);
 void launchStereo(hipStream_t, const LevelGeom*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const StereoParams&,
                   int, int*, unsigned short*, float*, float*, int*, int*, int);
-struct InitMatchParams {
-    float minX, minY, wInv, hInv, r, nnRatio;
-    int checkOrientation, capacity, slotCapacity, f1First, f1Step, f2First, f2Step;
-};
 size_t initMatchLdsBytes(int capacity, int slotCapacity);
 int initMatchSlotCapacity(int capacity);
 void launchSearchInit(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const InitMatchParams&,
                       float*, int*, int*, int);
-struct ProjQuery { float u, v, ur, radius; int minLevel, maxLevel, flags; float angle; };
-struct ProjectParams {
-    float fx, fy, cx, cy, minX, maxX, minY, maxY;
-    float scale[kMaxLevels];
-    float mbf, mb, th;
-    int mono, capacity, lastFirst, lastStep, curFirst, curStep;
-};
-struct ProjSearchParams {
-    float minX, minY, wInv, hInv, nnRatio;
-    int ratioMode, checkOrientation, capacity, queryCapacity, curFirst, curStep, descFirst, descStep, maxDist;
-};
 size_t projSearchLdsBytes(int capacity, int queryCapacity, bool topList);
 void launchProjectLast(hipStream_t, const Keypoint*, const Keypoint*, const int*, const uint8_t*, const float*, const float*, const ProjectParams&,
                        ProjQuery*, int);
 void launchSearchProj(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                       const int*, const float*, uint8_t*, const ProjSearchParams&, int*, int*, int);
-struct TrackRecord { float projX, projY, projXR, depth, viewCos; int level, exit; };      // == orbx_track_record (k_frustum_point.hpp)
-struct FrustumParams {      // == k_frustum_point.hpp
-    float fx, fy, cx, cy, minX, maxX, minY, maxY;
-    float scale[kMaxLevels], breaks[kMaxLevels];
-    float mbf, viewCosLimit, th, thFarPoints;
-    int nlevels, mode, farPoints, mpCapacity, curFirst, curStep, mpFirst, mpStep;
-};
 void launchFrustum(hipStream_t, const float*, const float*, const float*, const uint8_t*, const float*, const int*, const uint8_t*, const float*, const FrustumParams&, ProjQuery*, uint8_t*, int*, int*, TrackRecord*, int*, int);
-struct TwoEyesSearchParams {      // == k_project_two_eyes.hip
-    float minX, minY, wInv, hInv, nnRatio;
-    int capacity, queryCapacity, pairFirst, pairStep, descFirst, descStep, maxDist, forceWalk;
-};
 size_t twoEyesSearchLdsBytes(int capacity, int queryCapacity);
 void launchSearchProjTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                              const int*, const int*, const int*, uint8_t*, const TwoEyesSearchParams&, int*, int*, int);
-struct VocabDevice {
-    const int* childOff; const int* childList; const uint32_t* desc; const double* weight; const uint32_t* wordId;
-    int nNodes, k, L, scoring, weighting;
-};
 void launchBow(hipStream_t, const VocabDevice&, const uint8_t*, const int*, int, int, uint32_t*, double*, uint32_t*, uint32_t*, double*, int*,
                uint32_t*, uint32_t*, int*, int);
-struct RgbdParams { int capacity, rows, cols, isU16, scale; long long stride, frame; float factor, mbf; };
 void launchStereoFromRgbd(hipStream_t, const Keypoint*, const Keypoint*, const int*, const uint8_t*, const RgbdParams&, float*, float*, int);
-struct GrayParams { int rows, cols, channels, redFirst, aligned; long long srcStride, srcFrame, dstStride, dstFrame; };
 void launchGray(hipStream_t, const uint8_t*, uint8_t*, const GrayParams&, int);
 void launchClockProbe(hipStream_t, unsigned long long*, int, int, unsigned);
 void launchCopyOut(hipStream_t, const void*, void*, size_t, int);

@@ -1,0 +1,118 @@
+// orbx_params.hpp - the parameter blocks the kernels take BY VALUE and the records host and device exchange: the one definition of each.  The
+// host files fill them (through orbx_internal.hpp), the k_* files read them; a field added here reaches both sides or neither.  Plain data only:
+// compiles for the host (the CPU suite's builds behind tests/cpp/host_shim included) and the device.  A new entry adds its block here.
+#pragma once
+#include <stdint.h>
+
+#include "orbx_device.hpp"
+
+namespace orbx {
+
+// ---- records mirrored by include/orbx.h ------------------------------------------------------------------------------------------
+struct ProjQuery { float u, v, ur, radius; int minLevel, maxLevel, flags; float angle; };      // == orbx_proj_query
+static_assert(sizeof(ProjQuery) == 32, "orbx_proj_query layout");
+struct TrackRecord { float projX, projY, projXR, depth, viewCos; int level, exit; };             // == orbx_track_record
+static_assert(sizeof(TrackRecord) == 28, "orbx_track_record layout");
+
+// ---- in front of and behind the extractor ----------------------------------------------------------------------------------------
+struct GrayParams {              // k_gray.hip
+    int rows, cols, channels, redFirst, aligned;
+    long long srcStride, srcFrame, dstStride, dstFrame;
+};
+
+struct StereoParams {            // k_stereo.hip
+    float scale[kMaxLevels], invScale[kMaxLevels];
+    float bf, b;
+    int nlevels, capacity, rowCap;   // rowCap: entries of one pair's row-list arena
+};
+
+struct CameraParams { float fx, fy, cx, cy, k1, k2, p1, p2, k3; };
+struct FrameFinishParams {       // k_frame.hip
+    CameraParams cam;
+    float minX, minY, wInv, hInv;   // mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv
+    int capacity;
+    int rawGrid;                    // the Nleft != -1 branch of AssignFeaturesToGrid (:404-414): the cells come from mvKeys / mvKeysRight, not from mvKeysUn
+};
+
+struct RgbdParams {              // k_frame.hip (k_stereo_from_rgbd)
+    int capacity, rows, cols, isU16, scale;     // scale: convertTo runs (a 16-bit map always, a float map when factor != 1)
+    long long stride, frame;                    // bytes
+    float factor, mbf;
+};
+
+struct VocabDevice {            // k_bow.hip: plain arrays of the tree (TemplatedVocabulary::m_nodes)
+    const int* childOff;        // [nNodes + 1] children of node n: childList[childOff[n] .. childOff[n + 1])  (in m_nodes[n].children order)
+    const int* childList;
+    const uint32_t* desc;       // [nNodes][8]  node descriptors
+    const double* weight;       // [nNodes]
+    const uint32_t* wordId;     // [nNodes]     valid for leaves
+    int nNodes, k, L, scoring, weighting;
+};
+
+// ---- the matchers ----------------------------------------------------------------------------------------------------------------
+struct InitMatchParams {         // k_match.hip
+    float minX, minY, wInv, hInv;   // mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv of frame 2
+    float r, nnRatio;               // windowSize as float (Frame.cc:660-661), mfNNratio
+    int checkOrientation, capacity;
+    int slotCapacity;               // level-0 keypoints of frame 2 the LDS tables hold (a multiple of 4)
+    int f1First, f1Step, f2First, f2Step;
+};
+
+struct ProjectParams {           // k_project.hip (k_project_last)
+    float fx, fy, cx, cy, minX, maxX, minY, maxY;
+    float scale[kMaxLevels];
+    float mbf, mb, th;
+    int mono, capacity, lastFirst, lastStep, curFirst, curStep;
+};
+
+struct ProjSearchParams {        // k_project.hip (k_search_proj)
+    float minX, minY, wInv, hInv, nnRatio;
+    int ratioMode, checkOrientation, capacity, queryCapacity, curFirst, curStep, descFirst, descStep, maxDist;
+};
+
+struct TwoEyesSearchParams {     // k_project_two_eyes.hip
+    float minX, minY, wInv, hInv, nnRatio;
+    int capacity, queryCapacity, pairFirst, pairStep, descFirst, descStep, maxDist, forceWalk;
+};
+
+struct BowMatchParams {          // k_bow_match.hip
+    float nnRatio;
+    int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep;
+    int twoKeyFrames;      // SearchByBoW(pKF1, pKF2, vpMatches12): candidates must hold a MapPoint, strict threshold, result indexed by pKF1's keypoints
+};
+
+struct BowTwoEyesParams {        // k_bow_match_two_eyes.hip
+    float nnRatio;
+    int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep;
+};
+
+struct TriMatchParams {          // k_triangulate_match.hip
+    float scale[kMaxLevels], sigma2[kMaxLevels];      // mvScaleFactors, mvLevelSigma2 of the handle
+    int nlevels, thLow, checkOrientation, onlyStereo, coarse, capacity, kf1First, kf1Step, kf2First, kf2Step;
+};
+
+struct FuseParams {              // k_fuse.hip
+    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
+    float scale[kMaxLevels], invSigma2[kMaxLevels];      // mvScaleFactors, mvInvLevelSigma2 of the handle
+    float breaks[kMaxLevels];                            // [k - 1]: smallest ratio whose predicted level is >= k (k = 1 .. nlevels - 1)
+    float mbf, th;
+    int nlevels, thLow, reprojCheck, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
+};
+
+struct Sim3SearchParams {        // k_project_sim3.hip
+    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
+    float scale[kMaxLevels];       // mvScaleFactors of the handle
+    float breaks[kMaxLevels];      // PredictScale's breakpoints
+    float th;
+    int nlevels, maxDist, projection, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
+};
+
+struct FrustumParams {           // k_frustum.hip / k_frustum_point.hpp
+    float fx, fy, cx, cy, minX, maxX, minY, maxY;      // Frame's float bounds, as they are
+    float scale[kMaxLevels];                           // mvScaleFactors of the handle
+    float breaks[kMaxLevels];                          // [k - 1]: smallest ratio whose predicted level is >= k (k = 1 .. nlevels - 1)
+    float mbf, viewCosLimit, th, thFarPoints;
+    int nlevels, mode, farPoints, mpCapacity, curFirst, curStep, mpFirst, mpStep;
+};
+
+}  // namespace orbx

@@ -201,8 +201,8 @@ static int frameFinish(orbx_handle* h, int n_frames, const orbx_keypoint* d_kps,
     FrameFinishParams p;
     p.cam = CameraParams{cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2, cam->k3};
     p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
     p.capacity = capacity;
     p.rawGrid = rawGrid;
     {
@@ -228,8 +228,8 @@ int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame
     HIP_TRY(h, hipSetDevice(h->device));
     InitMatchParams p;
     p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
     p.r = (float)window_size; p.nnRatio = nn_ratio; p.checkOrientation = check_orientation != 0; p.capacity = capacity; p.slotCapacity = slotCap;
     p.f1First = frame1_first; p.f1Step = frame1_step; p.f2First = frame2_first; p.f2Step = frame2_step;
     {
@@ -281,8 +281,8 @@ int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first,
     HIP_TRY(h, hipSetDevice(h->device));
     ProjSearchParams p;
     p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
     p.nnRatio = nn_ratio; p.ratioMode = ratio_mode != 0; p.checkOrientation = check_orientation != 0;
     p.capacity = capacity; p.queryCapacity = query_capacity; p.curFirst = cur_first; p.curStep = cur_step;
     p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = max_distance < 255 ? max_distance : 255;
@@ -313,8 +313,8 @@ int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int p
     HIP_TRY(h, hipSetDevice(h->device));
     TwoEyesSearchParams p;
     p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
     p.nnRatio = nn_ratio; p.capacity = capacity; p.queryCapacity = query_capacity; p.pairFirst = pair_first; p.pairStep = pair_step;
     p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = max_distance < 255 ? max_distance : 255; p.forceWalk = h->twoEyesWalk ? 1 : 0;
     {
@@ -589,8 +589,8 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
     // IsInImage (:816-819) and GetFeaturesInArea (:778-790) compare with and subtract the truncated values ...
     p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
     // ... but scale by Frame's inverses, made from the untruncated floats and copied as they are (Frame.cc:339-340, KeyFrame.cc:50)
-    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv
-    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv
     for (int l = 0; l < h->nlevels; l++) { p.scale[l] = h->tabs.scale[l]; p.invSigma2[l] = h->tabs.invSigma2[l]; }
     for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
     p.mbf = mbf; p.th = th; p.nlevels = h->nlevels; p.thLow = th_low < 255 ? th_low : 255; p.reprojCheck = reproj_check ? 1 : 0;
@@ -649,8 +649,8 @@ int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_fi
     p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
     // KeyFrame's truncated bounds and Frame's untruncated inverses, as orbx_fuse_device
     p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
-    p.wInv = 64.0f / (bounds4[1] - bounds4[0]);
-    p.hInv = 48.0f / (bounds4[3] - bounds4[2]);
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);
     for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
     for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
     p.th = th; p.nlevels = h->nlevels; p.maxDist = orbx_sim3_hamming_bound(th_low, ratio_hamming); p.projection = projection;

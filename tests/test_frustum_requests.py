@@ -193,7 +193,7 @@ HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "test
 HOST_SOURCES = [os.path.join(ROOT, "tests", "cpp", "frustum_host_check.cpp"), os.path.join(ROOT, "extractorb_amd", "csrc", "orbx_predict_scale.cpp")]
 
 
-class HostParams(C.Structure):      # == FrustumParams of extractorb_amd/csrc/k_frustum_point.hpp
+class HostParams(C.Structure):      # == FrustumParams of extractorb_amd/csrc/orbx_params.hpp
     _fields_ = ([(n, C.c_float) for n in "fx fy cx cy minX maxX minY maxY".split()] + [("scale", C.c_float * 16), ("breaks", C.c_float * 16)] +
                 [(n, C.c_float) for n in "mbf viewCosLimit th thFarPoints".split()] +
                 [(n, C.c_int) for n in "nlevels mode farPoints mpCapacity curFirst curStep mpFirst mpStep".split()])

@@ -496,7 +496,12 @@ def test_synchronous_rounds_settle_on_the_walk_within_requests_plus_one_rounds(n
 
 def test_slot_limit_is_derived_from_the_kernel_and_documented():
     src = open(os.path.join(os.path.dirname(X.orbextractor.__file__), "csrc", "k_match.hip")).read()
-    assert "160LL * 1024 - 1024" in src and "(kCols + 2 + kHistoLength + 8) * sizeof(int) + 2 * kWaves * sizeof(int) + 64" in src
+    assert "160LL * 1024 - 1024" in src and "(kGridCols + 2 + kHistoLength + 8) * sizeof(int) + 2 * kWaves * sizeof(int) + 64" in src
+    # the two shared constants of that expression, where the kernels take them from
+    csrc = os.path.dirname(os.path.join(os.path.dirname(X.orbextractor.__file__), "csrc", "k_match.hip"))
+    assert "constexpr int kGridCols = 64, kGridRows = 48," in open(os.path.join(csrc, "orbx_device.hpp")).read()
+    assert "constexpr int kHistoLength = 30;" in open(os.path.join(csrc, "k_match_helpers.hpp")).read()
+    assert "constexpr int kThreads = 1024, kWaves = kThreads / 64;" in src
     per_slot = re.search(r"const long long sc = room / \(([0-9+* kAc]+)\);", src).group(1)
     assert "constexpr int kAcc = 2;" in src
     assert sum(int(np.prod([2 if f.strip() == "kAcc" else int(f) for f in term.split("*")])) for term in per_slot.split("+")) == SLOT_BYTES == 66

@@ -433,7 +433,7 @@ HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "test
 HOST_SOURCES = [os.path.join(ROOT, "tests", "cpp", "sim3_host_check.cpp"), os.path.join(ROOT, "extractorb_amd", "csrc", "orbx_predict_scale.cpp")]
 
 
-class HostParams(C.Structure):      # == Sim3SearchParams of extractorb_amd/csrc/k_project_sim3.hip
+class HostParams(C.Structure):      # == Sim3SearchParams of extractorb_amd/csrc/orbx_params.hpp
     _fields_ = ([(n, C.c_float) for n in "fx fy cx cy minX maxX minY maxY wInv hInv".split()] +
                 [("scale", C.c_float * 16), ("breaks", C.c_float * 16), ("th", C.c_float)] +
                 [(n, C.c_int) for n in "nlevels maxDist projection capacity mpCapacity kfFirst kfStep mpFirst mpStep".split()])
