@@ -64,6 +64,12 @@ void launchFrustum(hipStream_t, const float*, const float*, const float*, const 
 size_t twoEyesSearchLdsBytes(int capacity, int queryCapacity);
 void launchSearchProjTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                              const int*, const int*, const int*, uint8_t*, const TwoEyesSearchParams&, int*, int*, int);
+size_t lastTwoEyesLdsBytes(int capacity);
+void launchKb8Project(hipStream_t, const float*, const float*, int, float*);
+void launchProjectLastTwoEyes(hipStream_t, const Keypoint*, const int*, const uint8_t*, const float*, const float*, const ProjectTwoEyesParams&,
+                              ProjQuery*, int);
+void launchSearchLastTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const int*, const int*,
+                             uint8_t*, const LastTwoEyesSearchParams&, int*, int*, int);
 void launchBow(hipStream_t, const VocabDevice&, const uint8_t*, const int*, int, int, uint32_t*, double*, uint32_t*, uint32_t*, double*, int*,
                uint32_t*, uint32_t*, int*, int);
 void launchStereoFromRgbd(hipStream_t, const Keypoint*, const Keypoint*, const int*, const uint8_t*, const RgbdParams&, float*, float*, int);

@@ -75,6 +75,20 @@ struct TwoEyesSearchParams {     // k_project_two_eyes.hip
     int capacity, queryCapacity, pairFirst, pairStep, descFirst, descStep, maxDist, forceWalk;
 };
 
+struct ProjectTwoEyesParams {    // k_last_frame_two_eyes.hip (k_project_last_two_eyes) / k_project_last_two_eyes_point.hpp
+    float cam[8];                   // KannalaBrandt8::mvParameters: fx, fy, cx, cy, k1, k2, k3, k4
+    float minX, maxX, minY, maxY;
+    float scale[kMaxLevels];        // CurrentFrame.mvScaleFactors
+    float trl[12];                  // CurrentFrame.mTrl, 3x4 row-major
+    float mb, th;
+    int mono, capacity, lastFirst, lastStep, curFirst, curStep;      // first / step: RIG frames (device frames 2r, 2r + 1)
+};
+
+struct LastTwoEyesSearchParams { // k_last_frame_two_eyes.hip (k_search_last_two_eyes)
+    float minX, minY, wInv, hInv;
+    int checkOrientation, capacity, curFirst, curStep, maxDist;
+};
+
 struct BowMatchParams {          // k_bow_match.hip
     float nnRatio;
     int thLow, checkOrientation, capacity, kfFirst, kfStep, curFirst, curStep;

@@ -326,6 +326,72 @@ int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int p
     return ORBX_OK;
 }
 
+int orbx_kb8_project_device(orbx_handle* h, int n, const float* d_xyz, const orbx_camera_kb8* cam, float* d_uv) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_xyz || !cam || !d_uv || n < 1) return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer or n < 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const float k[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->k3, cam->k4};
+    {
+        Prof pr(h, S_FRAME);
+        launchKb8Project(h->stream, d_xyz, k, n, d_uv);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
+int orbx_project_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int last_first, int last_step, int cur_first, int cur_step,
+                                            const orbx_keypoint* d_kps, const int* d_n_out, int capacity, const uint8_t* d_mp_flags,
+                                            const float* d_world, const float* d_poses, const float* trl12, const orbx_camera_kb8* cam,
+                                            const float* bounds4, float mb, float th, int mono, orbx_proj_query* d_queries) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_kps || !d_n_out || !d_mp_flags || !d_world || !d_poses || !trl12 || !cam || !bounds4 || !d_queries || capacity < 1 || n_pairs < 1 ||
+        n_pairs > 65535 || capacity > (1 << 24) || last_first < 0 || cur_first < 0 || last_step < 0 || cur_step < 0 || !(bounds4[1] > bounds4[0]) ||
+        !(bounds4[3] > bounds4[2]))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, more than 65535 pairs, negative rig index/step or empty bounds");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ProjectTwoEyesParams p;
+    const float k[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->k3, cam->k4};
+    for (int i = 0; i < 8; i++) p.cam[i] = k[i];
+    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
+    for (int l = 0; l < kMaxLevels; l++) p.scale[l] = l < h->nlevels ? h->tabs.scale[l] : h->tabs.scale[h->nlevels - 1];   // CurrentFrame.mvScaleFactors
+    for (int i = 0; i < 12; i++) p.trl[i] = trl12[i];
+    p.mb = mb; p.th = th; p.mono = mono != 0; p.capacity = capacity;
+    p.lastFirst = last_first; p.lastStep = last_step; p.curFirst = cur_first; p.curStep = cur_step;
+    {
+        Prof pr(h, S_FRAME);
+        launchProjectLastTwoEyes(h->stream, (const Keypoint*)d_kps, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
+int orbx_search_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, const orbx_proj_query* d_queries,
+                                           const uint8_t* d_query_desc, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                                           int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4,
+                                           uint8_t* d_occupied, int max_distance, int check_orientation, int* d_matches, int* d_n_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_queries || !d_query_desc || !d_kps || !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_matches || !d_n_matches ||
+        capacity < 1 || n_pairs < 1 || cur_first < 0 || cur_step < 0 || max_distance < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, negative rig index/step, negative max_distance or empty bounds");
+    if (capacity > 8191 || lastTwoEyesLdsBytes(capacity) > 160 * 1024 - 512)
+        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident two-eye frame-to-frame search (96 bytes per keypoint of an "
+                                             "eye, 12 per request pair, 12 KB of cell offsets: 160 KB per CU)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    LastTwoEyesSearchParams p;
+    p.minX = bounds4[0]; p.minY = bounds4[2];
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    p.checkOrientation = check_orientation != 0; p.capacity = capacity; p.curFirst = cur_first; p.curStep = cur_step;
+    p.maxDist = max_distance < 255 ? max_distance : 255;
+    {
+        Prof pr(h, S_FRAME);
+        launchSearchLastTwoEyes(h->stream, (const ProjQuery*)d_queries, d_query_desc, (const Keypoint*)d_kps, d_desc, d_n_out, d_grid_off, d_grid_idx,
+                                d_occupied, p, d_matches, d_n_matches, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"
 
 struct orbx_vocabulary {

@@ -167,6 +167,12 @@ def load_library():
     L.orbx_search_by_projection_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp,
                                                             C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
     L.orbx_debug_two_eyes_search_stats.argtypes = [ip]
+    L.orbx_kb8_project_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbx_project_last_frame_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp,
+                                                          C.c_float, C.c_float, C.c_int, vp]
+    L.orbx_search_last_frame_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int,
+                                                         C.c_int, vp, vp]
+    L.orbx_debug_last_frame_two_eyes_stats.argtypes = [ip]
     L.orbx_vocabulary_load_text.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int]
     L.orbx_vocabulary_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int]
     L.orbx_vocabulary_destroy.argtypes = [vp]
@@ -320,6 +326,11 @@ def sim3_hamming_bound(th_low=50, ratio_hamming=1.0):
 def camera(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
     """orbx_camera: Frame::mK and Frame::mDistCoef as nine floats."""
     return np.array([fx, fy, cx, cy, k1, k2, p1, p2, k3], np.float32)
+
+
+def camera_kb8(fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, k4=0.0):
+    """orbx_camera_kb8: KannalaBrandt8::mvParameters as eight floats."""
+    return np.array([fx, fy, cx, cy, k1, k2, k3, k4], np.float32)
 
 
 def compute_image_bounds(cam, cols, rows):
@@ -556,6 +567,38 @@ class ORBextractor:
             self._h, n_pairs, pairs[0], pairs[1], dp(d_queries), dp(d_query_desc), desc_blocks[0], desc_blocks[1], dp(d_n_queries), query_capacity,
             dp(d_kps), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), dp(d_left_to_right), dp(d_right_to_left),
             dp(d_occupied), nnratio, max_distance, dp(d_matches), dp(d_n_matches)))
+
+    def kb8_project_device(self, n, d_xyz, cam, d_uv):
+        """KannalaBrandt8::project (reference src/CameraModels/KannalaBrandt8.cpp:28-44) over n device-resident points; cam = camera_kb8(...)."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        self._check(self._L.orbx_kb8_project_device(self._h, n, dp(d_xyz), None if cam is None else _ptr(np.ascontiguousarray(cam, np.float32)),
+                                                    dp(d_uv)))
+
+    def project_last_frame_two_eyes_device(self, n_pairs, last, cur, d_kps, d_n, capacity, d_mp_flags, d_world, d_poses, trl, cam, bounds, mb, th,
+                                           mono, d_queries):
+        """Front half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for two-camera frames (reference
+        src/ORBmatcher.cc:1971-2023, :2084-2101); last / cur = (first, step) of the last / current RIG frame of pair p (device frames 2r, 2r + 1);
+        d_poses per rig frame; trl = mTrl (3x4); cam = camera_kb8(...).  d_queries: 2 * capacity requests per pair, two records (L, R) each."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        def hp(a):
+            return None if a is None else _ptr(np.ascontiguousarray(a, np.float32))
+        self._check(self._L.orbx_project_last_frame_two_eyes_device(self._h, n_pairs, last[0], last[1], cur[0], cur[1], dp(d_kps), dp(d_n), capacity,
+                                                                    dp(d_mp_flags), dp(d_world), dp(d_poses), hp(trl), hp(cam), hp(bounds), mb, th,
+                                                                    int(mono), dp(d_queries)))
+
+    def search_last_frame_two_eyes_device(self, n_pairs, cur, d_queries, d_query_desc, d_kps, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds,
+                                          d_occupied, check_orientation, d_matches, d_n_matches, max_distance=100):
+        """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for two-camera frames, the search (reference
+        src/ORBmatcher.cc:2013-2174); cur = (first, step) of the current RIG frame of pair q.  d_queries / d_query_desc: 2 * capacity requests
+        per pair; d_matches / d_occupied are [(2q + eye)*capacity + i]."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
+        self._check(self._L.orbx_search_last_frame_two_eyes_device(
+            self._h, n_pairs, cur[0], cur[1], dp(d_queries), dp(d_query_desc), dp(d_kps), dp(d_desc), dp(d_n), capacity, dp(d_grid_off),
+            dp(d_grid_idx), _ptr(bounds), dp(d_occupied), max_distance, int(check_orientation), dp(d_matches), dp(d_n_matches)))
 
     def compute_bow_device(self, vocab, n_frames, d_desc, d_n, capacity, d_word_ids, d_word_weights, d_n_words, d_feat_nodes, d_feat_idx,
                            d_n_feat, levels_up=4):

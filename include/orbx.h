@@ -356,6 +356,64 @@ int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int p
                                               const int* d_left_to_right, const int* d_right_to_left, uint8_t* d_occupied, float nn_ratio,
                                               int max_distance, int* d_matches, int* d_n_matches);
 
+/* ---- ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for TWO-CAMERA frames (src/ORBmatcher.cc:1961-2177 with
+ * CurrentFrame.Nleft != -1; caller Tracking::TrackWithMotionModel) -------------------------------------------------------------------
+ * KannalaBrandt8::mvParameters[0..7] (src/CameraModels/KannalaBrandt8.cpp:28-44) as plain floats. */
+typedef struct orbx_camera_kb8 { float fx, fy, cx, cy, k1, k2, k3, k4; } orbx_camera_kb8;
+
+/* KannalaBrandt8::project(const cv::Point3f&) (src/CameraModels/KannalaBrandt8.cpp:28-44) over n device-resident points:
+ *   d_xyz[i*3 + {0,1,2}] in, d_uv[i*2 + {0,1}] out.
+ * Every operation is rounded in binary32 in the reference's order; atan2f is glibc 2.35's binary32 routine, cos(psi) / sin(psi) are taken
+ * as cosf / sinf.  What callers need for their own isInFrustum on such rigs (Frame::isInFrustumChecks, src/Frame.cc:1181-1254, is not
+ * built).  Asynchronous on the handle's stream. */
+int orbx_kb8_project_device(orbx_handle* h, int n, const float* d_xyz, const orbx_camera_kb8* cam, float* d_uv);
+
+/* Front half (src/ORBmatcher.cc:1971-2023 and :2084-2101).  A rig frame r is device frames 2r (left eye, mvKeys) and 2r + 1 (right eye,
+ * mvKeysRight), as in orbx_frame_finish_two_eyes_device.  For pair p the MapPoints of rig last_first + p*last_step are projected into rig
+ * cur_first + p*cur_step.  MapPoint i of LastFrame (i < Nleft: left keypoint i; i >= Nleft: right keypoint i - Nleft) is request
+ * j = eye*capacity + i, 2*capacity per pair, which keeps the reference's order.
+ *   d_kps    : the RAW keypoints of all device frames (octave :2009-2010, angle :2066-2068)      d_n_out : Nleft / Nright per device frame
+ *   d_mp_flags[f*capacity + i] : bit 0 = LastFrame.mvpMapPoints[..] != NULL && !mvbOutlier[..], bit 1 = Observations() > 0, per device frame f
+ *   d_world[(f*capacity + i)*3]: MapPoint::GetWorldPos(), per device frame
+ *   d_poses[r*12]       : Frame::mTcw, rows 0..2 (3x4, row-major), per RIG frame
+ *   trl12               : CurrentFrame.mTrl (3x4, row-major; host memory): x3Dr = mTrl.R * x3Dc + mTrl.t as a cv::Mat product (:2084)
+ *   cam                 : CurrentFrame.mpCamera.  The right request is projected with the LEFT camera's parameters too, as :2086 does
+ *                         (mpCamera, not mpCamera2); it has no depth test and no bounds test.
+ *   bounds4: mnMinX, mnMaxX, mnMinY, mnMaxY;  mb: Frame::mb;  th, mono as passed
+ *   d_queries[(p*2*capacity + j)*2 + {0: L, 1: R}] : out.  flags bit 0 of L: the MapPoint exists, invzc >= 0 (:1999) and the left projection
+ *            is inside the bounds (:2004-2007); bit 0 of R: the same condition; bit 1 of both: Observations() > 0.  radius = th *
+ *            mvScaleFactors[octave]; min_level, max_level by bForward / bBackward (:2017-2022, :2096-2101); angle = the last keypoint's raw
+ *            angle; ur is unused (0).  Where the reference `continue`s both records are all zero.
+ * A last frame with Nleft == -1 against a two-camera current frame is not built.  Asynchronous on the handle's stream. */
+int orbx_project_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int last_first, int last_step, int cur_first, int cur_step,
+                                            const orbx_keypoint* d_kps, const int* d_n_out, int capacity, const uint8_t* d_mp_flags,
+                                            const float* d_world, const float* d_poses, const float* trl12, const orbx_camera_kb8* cam,
+                                            const float* bounds4, float mb, float th, int mono, orbx_proj_query* d_queries);
+
+/* The search (src/ORBmatcher.cc:2013-2174) for n_pairs rigs cur_first + q*cur_step, on the grids of orbx_frame_finish_two_eyes_device.
+ *   d_queries[(q*2*capacity + j)*2 + {0: L, 1: R}] : the requests above, or a caller's own; request j's L searches the left eye (mGrid, mvKeys),
+ *            its R the right eye (mGridRight, mvKeysRight).  Requests are settled in the order of j, L before R.
+ *   d_query_desc[(q*2*capacity + j)*32] : MapPoint::GetDescriptor() of request j
+ *            (d_query_desc and d_desc are read 16 bytes at a time: both buffers must be 16-byte aligned, as hipMalloc's are)
+ *   d_kps, d_desc, d_n_out : RAW keypoints, descriptors and counts of all device frames;  d_grid_off, d_grid_idx, bounds4 : as written by /
+ *            passed to orbx_frame_finish_two_eyes_device
+ *   d_occupied[(2q + eye)*capacity + i] : in/out or NULL (= all free): the keypoint holds a MapPoint with Observations() > 0
+ *   max_distance : TH_HIGH = 100 (:2059, :2126);  check_orientation : ONE rotation histogram over both eyes (:2155-2174)
+ *   d_matches[(2q + eye)*capacity + i] : out, the request j whose MapPoint the keypoint holds afterwards, -1 = none;  d_n_matches[q] : the return value
+ * R is NOT run when its request's L has flags bit 0 set and L's GetFeaturesInArea result (cell window, level range, box test; closed
+ * keypoints count) is empty: the `continue` of :2024 skips the rest of the MapPoint.  That rule belongs to this entry because it needs
+ * the grid.  An L whose best distance is above max_distance, or whose candidates are all closed, does not stop R; an L with flags bit 0
+ * clear is not run and does not stop an R whose own bit 0 is set.  Keypoints outside the grid never match.  A keypoint octave outside [0, 255]
+ * (no extractor writes one) is taken as 0 or 255 when the frame is staged, where the reference compares the value as it is.  Supported: the tables of
+ * a pair live in LDS,
+ *   96 * ((capacity + 3) & ~3) + 12 * capacity + 12 496 <= 163 328 bytes
+ * (capacity <= 1396: 2 x orbx_max_keypoints() = 1302 of a 1200-feature extractor is inside); a larger call returns ORBX_ERR_UNSUPPORTED
+ * before anything is launched.  Asynchronous on the handle's stream. */
+int orbx_search_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, const orbx_proj_query* d_queries,
+                                           const uint8_t* d_query_desc, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                                           int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4,
+                                           uint8_t* d_occupied, int max_distance, int check_orientation, int* d_matches, int* d_n_matches);
+
 /* ---- next row: Frame::ComputeBoW (src/Frame.cc:739-746) --------------------------------------------------
  * = DBoW2::TemplatedVocabulary<FORB>::transform(features, BowVector, FeatureVector, levelsup = 4)
  * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1196, 1218-1262; BowVector.cpp:34-83; FeatureVector.cpp:31-46).
@@ -737,6 +795,9 @@ int orbx_debug_search_rounds(int* out4);
  * needed, [1] 1 if pair 0 was settled by the walk (forced, or a MapPoint without observations reopened a keypoint), [2] pairs settled by the
  * walk since the last read (the read resets it), [3] 100-MHz ticks of pair 0's workgroup.  Returns 0, or a negative orbx_status. */
 int orbx_debug_two_eyes_search_stats(int* out4);
+/* the two-eye frame-to-frame search (orbx_search_last_frame_two_eyes_device), the last launch's pair 0: out4[0] rounds of the fixed point,
+ * out4[1..3] 100 MHz ticks of staging, of the first scan and of the rounds */
+int orbx_debug_last_frame_two_eyes_stats(int* out4);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
  * (the last one changes nothing), [1] requests of the last launch whose decision came from scanning the window again (every key of a
