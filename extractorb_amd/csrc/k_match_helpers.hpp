@@ -89,4 +89,16 @@ __device__ __forceinline__ float gemmRow(float a0, float a1, float a2, const flo
     return (float)s;
 }
 
+// A 3x3 * 3x3 cv::Mat product of float data (Rrl * mRcw of Frame::isInFrustumChecks): every element is one gemmRow of a row of A and a column
+// of B, no addend.  A and B are row-major with row strides sa / sb (3 for a 3x3 block, 4 for the rotation of a 3x4 pose); out is 3x3 row-major.
+// Parity unpinned, as the other cv::Mat roundings of the matchers: a later pin against the reference's cv::gemm changes this one place.
+__device__ __forceinline__ float gemmMat3Element(const float* A, int sa, const float* B, int sb, int r, int c) {
+    const float col[3] = {B[c], B[sb + c], B[2 * sb + c]};
+    return gemmRow(A[sa * r], A[sa * r + 1], A[sa * r + 2], col, 1.0, 0.f, false);
+}
+__device__ __forceinline__ void gemmMat3(const float* A, int sa, const float* B, int sb, float* out) {
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) out[3 * r + c] = gemmMat3Element(A, sa, B, sb, r, c);
+}
+
 }  // namespace orbx

@@ -61,6 +61,9 @@ void launchProjectLast(hipStream_t, const Keypoint*, const Keypoint*, const int*
 void launchSearchProj(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                       const int*, const float*, uint8_t*, const ProjSearchParams&, int*, int*, int);
 void launchFrustum(hipStream_t, const float*, const float*, const float*, const uint8_t*, const float*, const int*, const uint8_t*, const float*, const FrustumParams&, ProjQuery*, uint8_t*, int*, int*, TrackRecord*, int*, int);
+int frustumTwoEyesGroups(int mpCapacity);
+void launchFrustumTwoEyes(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const float*,
+                          const FrustumTwoEyesParams&, int*, ProjQuery*, uint8_t*, int*, int*, int*, TrackRecord*, int*, int);
 size_t twoEyesSearchLdsBytes(int capacity, int queryCapacity);
 void launchSearchProjTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
                              const int*, const int*, const int*, uint8_t*, const TwoEyesSearchParams&, int*, int*, int);
@@ -222,6 +225,9 @@ struct orbx_handle {
     // the Sim3 projection search's records (allocated on first use): the key list, the candidate count and the window of every (pair, MapPoint)
     size_t sim3Entries = 0;
     void* d_sim3Rec = nullptr;
+    // the two-eye frustum requests' workspace (allocated on first use): a (slot count, in-view count) pair per workgroup of k_frustum_two_eyes_check
+    size_t frustumCountEntries = 0;
+    int* d_frustumCounts = nullptr;
     // stereo matching (allocated on first use)
     int stereoPairs = 0, stereoCap = 0, stereoRows = 0;
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;

@@ -129,4 +129,16 @@ struct FrustumParams {           // k_frustum.hip / k_frustum_point.hpp
     int nlevels, mode, farPoints, mpCapacity, curFirst, curStep, mpFirst, mpStep;
 };
 
+struct FrustumTwoEyesParams {    // k_frustum_two_eyes.hip / k_frustum_two_eyes_point.hpp
+    float cam[2][8];                                   // KannalaBrandt8::mvParameters of mpCamera (left eye) and mpCamera2 (right eye)
+    float minX, maxX, minY, maxY;                      // Frame's float bounds, as they are; the same four for both eyes
+    float scale[kMaxLevels];                           // mvScaleFactors of the handle
+    float breaks[kMaxLevels];                          // PredictScale's breakpoints, as FrustumParams
+    float trl[12], tlr[12];                            // Frame::mTrl, Frame::mTlr, 3x4 row-major, as the Frame holds them
+    float viewCosLimit, th, thFarPoints;
+    int nlevels, farPoints, mpCapacity, queryCapacity;
+    int groups;                                        // workgroups per pair: ceil(mpCapacity / MapPoints per workgroup)
+    int curFirst, curStep, mpFirst, mpStep;            // cur: RIG frames (d_poses holds one pose per rig)
+};
+
 }  // namespace orbx

@@ -772,4 +772,61 @@ int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int
     return ORBX_OK;
 }
 
+int orbx_frustum_requests_two_eyes_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, int mp_first, int mp_step,
+                                          const float* d_mp_world, const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc,
+                                          const int* d_n_mp, int mp_capacity, const uint8_t* d_mp_flags, const float* d_mp_prev_depth,
+                                          const float* d_poses, const float* trl12, const float* tlr12, const orbx_camera_kb8* cam_left,
+                                          const orbx_camera_kb8* cam_right, const float* bounds4, int nlevels, float view_cos_limit, float th,
+                                          int far_points, float th_far_points, int query_capacity, orbx_proj_query* d_queries,
+                                          uint8_t* d_query_desc, int* d_query_src, int* d_n_queries, int* d_n_wanted, orbx_track_record* d_track,
+                                          int* d_n_in_view) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    // d_n_mp, d_mp_prev_depth and d_n_wanted may be NULL
+    if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !trl12 || !tlr12 || !cam_left || !cam_right ||
+        !bounds4 || !d_queries || !d_query_desc || !d_query_src || !d_n_queries || !d_track || !d_n_in_view || mp_capacity < 1 ||
+        mp_capacity > (1 << 30) || query_capacity < 1 || query_capacity > mp_capacity || n_pairs < 1 || n_pairs > 65535 || cur_first < 0 ||
+        mp_first < 0 || cur_first + (long long)(n_pairs - 1) * cur_step < 0 || mp_first + (long long)(n_pairs - 1) * mp_step < 0)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, mp_capacity/n_pairs < 1, more than 65535 pairs, a query_capacity outside 1 .. mp_capacity "
+                                              "or a negative rig or list index");
+    if (nlevels != h->nlevels)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
+    if (!h->scaleBreaksReady) {
+        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
+            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
+        h->scaleBreaksReady = true;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    FrustumTwoEyesParams p{};
+    p.groups = frustumTwoEyesGroups(mp_capacity);
+    const size_t need = (size_t)n_pairs * p.groups * 2;
+    if (need > h->frustumCountEntries) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (h->d_frustumCounts) (void)hipFree(h->d_frustumCounts);
+        h->d_frustumCounts = nullptr; h->frustumCountEntries = 0;
+        HIP_TRY(h, hipMalloc(&h->d_frustumCounts, need * sizeof(int)));      // what k_frustum_two_eyes_check leaves for k_frustum_two_eyes_place
+        h->frustumCountEntries = need;
+    }
+    const orbx_camera_kb8* cams[2] = {cam_left, cam_right};                  // mpCamera, mpCamera2 (Frame.cc:1210-1211)
+    for (int e = 0; e < 2; e++) {
+        const float k[8] = {cams[e]->fx, cams[e]->fy, cams[e]->cx, cams[e]->cy, cams[e]->k1, cams[e]->k2, cams[e]->k3, cams[e]->k4};
+        for (int i = 0; i < 8; i++) p.cam[e][i] = k[i];
+    }
+    // Frame's own float bounds, compared as they are (Frame.cc:1213-1216); the same four for both eyes
+    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
+    for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
+    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    for (int i = 0; i < 12; i++) { p.trl[i] = trl12[i]; p.tlr[i] = tlr12[i]; }
+    p.viewCosLimit = view_cos_limit; p.th = th; p.thFarPoints = th_far_points;
+    p.nlevels = h->nlevels; p.farPoints = far_points ? 1 : 0; p.mpCapacity = mp_capacity; p.queryCapacity = query_capacity;
+    p.curFirst = cur_first; p.curStep = cur_step; p.mpFirst = mp_first; p.mpStep = mp_step;
+    {
+        Prof pr(h, S_FRAME);
+        launchFrustumTwoEyes(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_mp_prev_depth, d_poses, p,
+                             h->d_frustumCounts, (ProjQuery*)d_queries, d_query_desc, d_query_src, d_n_queries, d_n_wanted, (TrackRecord*)d_track,
+                             d_n_in_view, n_pairs);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}
+
 }  // extern "C"

@@ -194,6 +194,9 @@ def load_library():
                                                         vp, vp, vp, vp, vp]
     L.orbx_frustum_requests_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp,
                                                C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp]
+    L.orbx_frustum_requests_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp,
+                                                        vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, vp, vp, vp,
+                                                        vp, vp, vp, vp]
     L.orbx_sim3_hamming_bound.argtypes = [C.c_int, C.c_float]
     L.orbx_debug_sim3_search_stats.argtypes = [ip]
     L.orbx_debug_sim3_search_list_length.argtypes = []
@@ -706,6 +709,28 @@ class ORBextractor:
             mp_capacity, dp(d_mp_flags), dp(d_poses), _ptr(cam), _ptr(bounds), self.nlevels if nlevels is None else nlevels, int(mode), mbf,
             view_cos_limit, th, int(bool(far_points)), th_far_points, dp(d_queries), dp(d_query_desc), dp(d_query_src), dp(d_n_queries),
             dp(d_track), dp(d_n_in_view)))
+
+    def frustum_requests_two_eyes_device(self, n_pairs, cur, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
+                                         d_mp_prev_depth, d_poses, trl, tlr, cam_left, cam_right, bounds, query_capacity, d_queries, d_query_desc,
+                                         d_query_src, d_n_queries, d_n_wanted, d_track, d_n_in_view, view_cos_limit=0.5, th=1.0, far_points=False,
+                                         th_far_points=0.0, nlevels=None):
+        """Frame::isInFrustum's Nleft != -1 branch (isInFrustumChecks per eye) over a MapPoint list plus the prelude of
+        ORBmatcher::SearchByProjection(F, vpMapPoints, ...) for two-camera rigs (reference src/Frame.cc:571-581, :1181-1254,
+        src/Tracking.cc:2941-2959, src/ORBmatcher.cc:50-73, :145-151).  cur and mp = (first, step) of the RIG frame / MapPoint list of pair
+        p; d_poses per rig frame; trl / tlr = mTrl / mTlr (3x4); cam_left / cam_right = camera_kb8(...) of mpCamera / mpCamera2.  Writes two
+        TRACK_RECORD_DTYPE per list entry (left, right), the slots of every pair compacted in list order (two PROJ_QUERY_DTYPE each in
+        d_queries, d_query_desc, d_query_src, d_n_queries: feed them to search_by_projection_two_eyes_device with the same query_capacity
+        and desc_blocks = (0, 1)), the count the list produced (d_n_wanted) and nToMatch per pair.  d_n_mp, d_mp_prev_depth and d_n_wanted
+        may be None."""
+        def dp(x):
+            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+        def hp(a):
+            return None if a is None else _ptr(np.ascontiguousarray(a, np.float32))
+        self._check(self._L.orbx_frustum_requests_two_eyes_device(
+            self._h, n_pairs, cur[0], cur[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_n_mp), mp_capacity,
+            dp(d_mp_flags), dp(d_mp_prev_depth), dp(d_poses), hp(trl), hp(tlr), hp(cam_left), hp(cam_right), hp(bounds),
+            self.nlevels if nlevels is None else nlevels, view_cos_limit, th, int(bool(far_points)), th_far_points, query_capacity, dp(d_queries),
+            dp(d_query_desc), dp(d_query_src), dp(d_n_queries), dp(d_n_wanted), dp(d_track), dp(d_n_in_view)))
 
     def debug_sim3_search_stats(self):
         """(rounds of pair 0, requests settled by a re-scan, 100-MHz ticks of pair 0's settling workgroup, 0) of the last Sim3 search"""

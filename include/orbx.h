@@ -364,8 +364,8 @@ typedef struct orbx_camera_kb8 { float fx, fy, cx, cy, k1, k2, k3, k4; } orbx_ca
 /* KannalaBrandt8::project(const cv::Point3f&) (src/CameraModels/KannalaBrandt8.cpp:28-44) over n device-resident points:
  *   d_xyz[i*3 + {0,1,2}] in, d_uv[i*2 + {0,1}] out.
  * Every operation is rounded in binary32 in the reference's order; atan2f is glibc 2.35's binary32 routine, cos(psi) / sin(psi) are taken
- * as cosf / sinf.  What callers need for their own isInFrustum on such rigs (Frame::isInFrustumChecks, src/Frame.cc:1181-1254, is not
- * built).  Asynchronous on the handle's stream. */
+ * as cosf / sinf.  The projection by itself, for callers' own tests on such rigs; Frame::isInFrustumChecks (src/Frame.cc:1181-1254) over a
+ * local map is orbx_frustum_requests_two_eyes_device, which projects inside its kernel.  Asynchronous on the handle's stream. */
 int orbx_kb8_project_device(orbx_handle* h, int n, const float* d_xyz, const orbx_camera_kb8* cam, float* d_uv);
 
 /* Front half (src/ORBmatcher.cc:1971-2023 and :2084-2101).  A rig frame r is device frames 2r (left eye, mvKeys) and 2r + 1 (right eye,
@@ -729,7 +729,8 @@ typedef struct orbx_track_record {
 
 /* Tracking::SearchLocalPoints' loop over the local map (src/Tracking.cc:2941-2959) and the front half of Relocalization's projection search,
  * on the device: MapPoint lists and frame poses in, the request lists of orbx_search_by_projection_device out.  For frames with Nleft == -1 and
- * the Pinhole model.  NOT covered: isInFrustum's Nleft != -1 branch (src/Frame.cc:571 on: isInFrustumChecks, mpCamera2 - the KannalaBrandt8 pair).
+ * the Pinhole model.  NOT covered here: isInFrustum's Nleft != -1 branch (src/Frame.cc:571 on: isInFrustumChecks, mpCamera2 - the KannalaBrandt8
+ * pair), which is orbx_frustum_requests_two_eyes_device below; the relocalisation mode has no two-camera form.
  * Pair p projects MapPoint list mp_first + p*mp_step into frame cur_first + p*cur_step (mp_step = 0: one local map into several frames).
  *   per MapPoint, in blocks of mp_capacity per list (m = list*mp_capacity + i), the conventions of orbx_fuse_device:
  *   d_mp_world[m*3], d_mp_normal[m*3] : GetWorldPos(), GetNormal() (the normals are read in mode 0 only and may be NULL in mode 1)
@@ -780,6 +781,64 @@ int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int
                                  const float* bounds4, int nlevels, int mode, float mbf, float view_cos_limit, float th, int far_points,
                                  float th_far_points, orbx_proj_query* d_queries, uint8_t* d_query_desc, int* d_query_src, int* d_n_queries,
                                  orbx_track_record* d_track, int* d_n_in_view);
+
+/* Tracking::SearchLocalPoints' loop over the local map (src/Tracking.cc:2941-2959) for TWO-CAMERA rigs (Nleft != -1, a KannalaBrandt8 pair), on
+ * the device: MapPoint lists and rig poses in, the request lists of orbx_search_by_projection_two_eyes_device out.  The statement is
+ * Frame::isInFrustum's else branch (src/Frame.cc:571-581): Frame::isInFrustumChecks (:1181-1254) once per eye, then the prelude of
+ * ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) for F.Nleft != -1 (src/ORBmatcher.cc:50-73, :145-151, :216-222).
+ * Pair p projects MapPoint list mp_first + p*mp_step into RIG frame cur_first + p*cur_step.  The list / pair indexing, the d_mp_dist triples,
+ * d_n_mp (clamped to 0 .. mp_capacity, NULL = mp_capacity), d_mp_flags per pair (bit 0 = pMP->mnLastFrameSeen != mCurrentFrame.mnId &&
+ * !pMP->isBad(), bit 1 = Observations() > 0) and nlevels are those of orbx_frustum_requests_device.
+ *   d_poses[r*12]              : Frame::mTcw, rows 0..2 (3x4, row-major: Rcw | tcw), per RIG frame, as orbx_project_last_frame_two_eyes_device
+ *   trl12, tlr12               : Frame::mTrl and Frame::mTlr (3x4, row-major; host memory), BOTH as the Frame holds them: neither is derived from the other
+ *   cam_left, cam_right        : mpCamera and mpCamera2.  The right eye is projected with ITS OWN eight parameters (:1210) - unlike the
+ *                 frame-to-frame search, which uses the left camera for both eyes
+ *   bounds4                    : Frame's FLOAT mnMinX, mnMaxX, mnMinY, mnMaxY, the same four for both eyes, compared NON-STRICTLY in the
+ *                 reference's form (uv.x < mnMinX || uv.x > mnMaxX leaves, :1213-1216): a projection on a bound passes, and so does a NaN
+ *   d_mp_prev_depth[p*mp_capacity + i] : mTrackDepth as an earlier frame left it in the MapPoint; may be NULL (= 0 everywhere).  It decides only for a
+ *                 MapPoint that the right eye sees and the left eye does not (below)
+ * Rig invariants, once per pair: left eye mR = Rcw, mt = tcw, twc = mOw = -Rcw.t()*tcw; right eye mR = Rrl*Rcw (a 3x3 cv::Mat product: every
+ * element one row-by-column sum in double, rounded to float once), mt = Rrl*tcw + trl (ONE gemm with the addend), twc = mRwc*mTlr.col(3) + mOw
+ * (one gemm of the transposed Rcw with the float mOw as addend) (:1186-1197).  These cv::Mat roundings are parity unpinned, as orbx_fuse_device's.
+ * Per eye, every operation rounded on its own: Pc = mR*P + mt as cv::gemm; Pc_dist = cv::norm(Pc) (squares summed in double in element order,
+ * one square root, then float); PcZ < 0.0f leaves, z == 0 goes on (:1205); uv = KannalaBrandt8::project(Pc) with that eye's camera, as
+ * orbx_kb8_project_device; the bounds (:1213-1216); PO = P - twc in float; dist = cv::norm(PO); dist < min || dist > max leaves (:1224);
+ * viewCos = (float)(PO.dot(Pn) / (double)dist) (:1230); viewCos < view_cos_limit leaves (:1232); level = PredictScale(dist) (:1236).  A check
+ * that returns false assigns NOTHING - unlike the one-camera branch there is no mTrackProjX = uv.x in front of the distance test and no invz.
+ * Per MapPoint: mbTrackInView = L, mbTrackInViewR = R; nToMatch counts L || R (src/Tracking.cc:2950-2954).  The matcher skips the MapPoint when
+ * neither eye is in view (:53) and when far_points && mTrackDepth > th_far_points (:56).  mTrackDepth is the LEFT eye's Pc_dist; when the left
+ * check failed nothing assigned it in this frame, the reference reads what an earlier frame left there, and the entry takes that value from
+ * d_mp_prev_depth (NULL or 0: never far).  Left request: radius = RadiusByViewingCos(mTrackViewCos) (viewCos >= 0.998f gives 2.5, else 4.0),
+ * times th only when th != 1.0f (:69-70), times mvScaleFactors[level]; levels level - 1, level (:73).  Right request: radius =
+ * RadiusByViewingCos(mTrackViewCosR) * mvScaleFactors[levelR], WITHOUT th (:148); levels levelR - 1, levelR (:151).  flags of each request =
+ * (that eye in view ? 1 : 0) | (bit 1 of the input flag); a request whose eye is not in view is all zero apart from that bit 1; ur and angle
+ * are 0.  A MapPoint becomes a slot (two requests, one descriptor) when L || R and it is not far.
+ *   d_track[(p*mp_capacity + i)*2 + eye] : out, one orbx_track_record per eye.  L: proj_x / proj_y = mTrackProjX / Y, depth = mTrackDepth,
+ *                 view_cos = mTrackViewCos, level = mnTrackScaleLevel.  R: proj_x / proj_y = mTrackProjXR / YR, depth = mTrackDepthR, view_cos =
+ *                 mTrackViewCosR, level = mnTrackScaleLevelR.  proj_xr is 0 in both.  A record whose check returned false, or that was not looked
+ *                 at, is -1, -1, 0, 0, 0, -1 (the level src/Frame.cc:574-575 leave) plus its exit, an orbx_frustum_exit per eye: every byte
+ *                 is defined.  In view is exit >= ORBX_FRUSTUM_FAR; ORBX_FRUSTUM_FAR is set on every in-view eye of a far MapPoint.
+ *   d_queries[(p*query_capacity + k)*2 + {0: L, 1: R}], d_query_desc[(p*query_capacity + k)*32], d_query_src[p*query_capacity + k],
+ *   k < d_n_queries[p]         : out, the slots of pair p COMPACTED IN LIST ORDER (the same order in every run: no atomic decides a position),
+ *                 their descriptors (16-byte aligned, as d_mp_desc) and the list index each came from.  They are what
+ *                 orbx_search_by_projection_two_eyes_device takes with the same query_capacity, desc_first = 0, desc_step = 1 and d_n_queries
+ *                 as it is.  Slots k >= d_n_queries[p] get two all-zero requests and src = -1; their descriptor slots are left untouched.
+ *   query_capacity             : 1 .. mp_capacity, a stride of its own (the search keeps 8 bytes per request in LDS: a 4096-point local map with
+ *                 half of its points in view need not force 4096 on a multi-pair call).  Slots beyond it are dropped from the END of the list:
+ *                 d_n_queries[p] is the number written, d_n_wanted[p] (may be NULL) the number the list produced.
+ *   d_n_in_view[p]             : out, nToMatch: the MapPoints with L || R, counted BEFORE the far test
+ * Two launches on the handle's stream (the statement and one slot count per workgroup; the placement), a list spread over ceil(mp_capacity / 256)
+ * workgroups per pair; the counts live in a workspace of the handle that grows on first use.  Errors: ORBX_ERR_BAD_ARGUMENT before any launch
+ * (null pointer, nlevels, n_pairs outside 1 .. 65535, query_capacity outside 1 .. mp_capacity, negative sizes or indices).  Nothing lives in
+ * LDS tables: there is no capacity bound and no ORBX_ERR_UNSUPPORTED case.  Asynchronous on the handle's stream. */
+int orbx_frustum_requests_two_eyes_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, int mp_first, int mp_step,
+                                          const float* d_mp_world, const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc,
+                                          const int* d_n_mp, int mp_capacity, const uint8_t* d_mp_flags, const float* d_mp_prev_depth,
+                                          const float* d_poses, const float* trl12, const float* tlr12, const orbx_camera_kb8* cam_left,
+                                          const orbx_camera_kb8* cam_right, const float* bounds4, int nlevels, float view_cos_limit, float th,
+                                          int far_points, float th_far_points, int query_capacity, orbx_proj_query* d_queries,
+                                          uint8_t* d_query_desc, int* d_query_src, int* d_n_queries, int* d_n_wanted, orbx_track_record* d_track,
+                                          int* d_n_in_view);
 
 /* Stream control.  By default the handle owns a stream; orbx_set_stream adopts a caller stream
  * (hipStream_t passed as void*, e.g. torch.cuda.current_stream().cuda_stream) so the caller's events
