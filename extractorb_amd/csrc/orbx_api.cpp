@@ -52,7 +52,7 @@ void freeAll(orbx_handle* h) {
 int installGeometry(orbx_handle* h, int rows, int cols) {
     FrameGeom g;
     std::string why = makeFrameGeom(h->tabs, rows, cols, g, h->colPx);
-    if (!why.empty()) return fail(h, why.find("small") != std::string::npos ? ORBX_ERR_IMAGE_TOO_SMALL : ORBX_ERR_UNSUPPORTED, why);
+    if (!why.empty()) return fail(h, geometryRefusalCode(why), why);
     layoutArenas(g, h->maxB);
     const LevelGeom& last = g.lv[g.nlevels - 1];
     if ((size_t)(last.pyrOff + last.pyrFrameBytes * h->maxB) > h->pyrBytes ||
@@ -617,7 +617,7 @@ int orbx_compute_cell_grid(float scale_factor, int nlevels, int rows, int cols, 
     ScaleTables t = makeScaleTables(1000, scale_factor, nlevels);
     FrameGeom g;
     std::string why = makeFrameGeom(t, rows, cols, g);
-    if (!why.empty()) return why.find("small") != std::string::npos ? ORBX_ERR_IMAGE_TOO_SMALL : ORBX_ERR_UNSUPPORTED;
+    if (!why.empty()) return geometryRefusalCode(why);
     const LevelGeom& L = g.lv[level];
     if (n_cols) *n_cols = L.nCols;
     if (n_rows) *n_rows = L.nRows;
@@ -638,11 +638,7 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
         g_createError = "orbx_create: bad argument (need nfeatures>=1, 1<=nlevels<=16, scale>1, 1<=thresholds<=254)";
         return ORBX_ERR_BAD_ARGUMENT;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        g_createError = "orbx_create: no HIP device (this library has no CPU path)";
-        return ORBX_ERR_NO_DEVICE;
-    }
+    if (int rc = selectDevice("orbx_create", &device)) return rc;
     orbx_handle* h = new orbx_handle();
     auto bail = [&](int code) {
         g_createError = h->err;
@@ -658,8 +654,6 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
             return bail(ORBX_ERR_HIP);                                                   \
         }                                                                                \
     } while (0)
-    if (device < 0) CREATE_TRY(hipGetDevice(&device));
-    if (device >= ndev) { h->err = "orbx_create: device index out of range"; return bail(ORBX_ERR_BAD_ARGUMENT); }
     h->device = device;
     CREATE_TRY(hipSetDevice(device));
     h->nfeatures = nfeatures; h->nlevels = nlevels; h->iniTh = ini_th; h->minTh = min_th; h->scaleFactor = scale_factor;
@@ -674,7 +668,7 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
         return v;
     };
     std::string why = makeFrameGeom(h->tabs, max_height, max_width, h->maxGeom);
-    if (!why.empty()) { h->err = "orbx_create: " + why; return bail(why.find("small") != std::string::npos ? ORBX_ERR_IMAGE_TOO_SMALL : ORBX_ERR_UNSUPPORTED); }
+    if (!why.empty()) { h->err = "orbx_create: " + why; return bail(geometryRefusalCode(why)); }
     layoutArenas(h->maxGeom, max_batch);
     const FrameGeom& mg = h->maxGeom;
     // a smaller image can need slightly more of a rounded quantity (cell grid, strides): 12.5 % + slack head-room

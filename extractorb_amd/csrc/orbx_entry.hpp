@@ -1,0 +1,94 @@
+// orbx_entry.hpp - the plain statements the C entry points of orbx_rows.cpp share: argument predicates, the LDS budget, the fills of the kernels'
+// parameter blocks (templates over the block: no layout is named here), the level-table padding rules, and the order of "free, then allocate
+// all or nothing" of a growable set of buffers.  Host only, no HIP, allocates nothing: tests/cpp/entry_check.cpp compiles it with g++ behind
+// tests/cpp/host_shim and tests/test_entry_helpers.py compares every function with an independent statement.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <initializer_list>
+
+#include "orbx.h"
+#include "orbx_geometry.hpp"
+#include "orbx_params.hpp"
+
+namespace orbx {
+
+// ---- predicates -------------------------------------------------------------------------------------------------------------------
+// written so that a NaN bound is empty
+inline bool emptyBounds(const float* bounds4) { return !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]); }
+// The entries name the frames (keyframes, MapPoint lists) of pair p as first + p * step.  Two rules exist and they differ on negative steps:
+// the walk rule lets a step be negative as long as no pair's index is (BoW, triangulation, Fuse, Sim3, frustum) ...
+inline bool negativeWalk(int first, int step, int n) { return first < 0 || first + (long long)(n - 1) * step < 0; }
+// ... the older rule refuses every negative step (SearchForInitialization, the frame-to-frame and local-map projection searches)
+inline bool negativeFirstOrStep(int first, int step) { return first < 0 || step < 0; }
+
+// ---- limits -----------------------------------------------------------------------------------------------------------------------
+constexpr size_t kLdsBudget = 160 * 1024 - 512;      // dynamic + static LDS a workgroup of the LDS-resident searches may ask for (160 KB per CU)
+inline bool fitsLds(size_t bytes) { return bytes <= kLdsBudget; }
+// orbx_search_by_bow_device alone keeps a bound of its own, NOT kLdsBudget: the 150 KB its launch wrapper (k_bow_match.hip) chooses its staged
+// form with.  The one-camera BoW search predates kLdsBudget and which capacities it accepts is behaviour
+constexpr size_t kBowMatchLdsBudget = 150 * 1024;
+inline int clampDistance(int d) { return d < 255 ? d : 255; }      // no descriptor distance exceeds 255: a larger bound accepts the same matches
+
+// ---- fills of a parameter block ---------------------------------------------------------------------------------------------------
+template <class P> inline void fillGridInverses(P& p, const float* bounds4) {
+    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
+    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+}
+template <class P> inline void fillGrid(P& p, const float* bounds4) {
+    p.minX = bounds4[0]; p.minY = bounds4[2];
+    fillGridInverses(p, bounds4);
+}
+// Frame's own float bounds, compared as they are (Frame.cc:520-523, :1213-1216, ORBmatcher.cc:2209-2212)
+template <class P> inline void fillBounds(P& p, const float* bounds4) {
+    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
+}
+// KeyFrame's mnMinX .. mnMaxY are const int (inc/KeyFrame.h:484) initialised from Frame's floats (KeyFrame.cc:58): truncated toward zero.
+// IsInImage (:816-819) and GetFeaturesInArea (:778-790) compare with and subtract the truncated values, but scale by Frame's inverses, made
+// from the untruncated floats and copied as they are (KeyFrame.cc:50): a KeyFrame's block takes this and fillGridInverses
+template <class P> inline void fillBoundsTruncated(P& p, const float* bounds4) {
+    p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
+}
+template <class P> inline void fillPinhole(P& p, const orbx_camera& cam) { p.fx = cam.fx; p.fy = cam.fy; p.cx = cam.cx; p.cy = cam.cy; }
+// KannalaBrandt8::mvParameters
+inline void fillKb8(float (&dst)[8], const orbx_camera_kb8& cam) {
+    dst[0] = cam.fx; dst[1] = cam.fy; dst[2] = cam.cx; dst[3] = cam.cy; dst[4] = cam.k1; dst[5] = cam.k2; dst[6] = cam.k3; dst[7] = cam.k4;
+}
+// MapPoint::PredictScale's nlevels - 1 breakpoints; the elements from nlevels - 1 on stay what they are (zero in a block made with {})
+template <class P> inline void fillBreaks(P& p, const float* breaks, int nlevels) {
+    for (int l = 0; l + 1 < nlevels; l++) p.breaks[l] = breaks[l];
+}
+
+// ---- level tables: one function per padding rule.  dst is a block's table of kMaxLevels, src the handle's (ScaleTables) ------------------------
+// Whether the rules need to differ is not decided here; each is what its kernels have always been given, the elements past nlevels included.
+// stereo: 1 past nlevels
+inline void levelsPaddedWithOne(float (&dst)[kMaxLevels], const float* src, int nlevels) {
+    for (int l = 0; l < kMaxLevels; l++) dst[l] = l < nlevels ? src[l] : 1.f;
+}
+// the two project_last entries: the coarsest level's value past nlevels (CurrentFrame.mvScaleFactors)
+inline void levelsPaddedWithLast(float (&dst)[kMaxLevels], const float* src, int nlevels) {
+    for (int l = 0; l < kMaxLevels; l++) dst[l] = l < nlevels ? src[l] : src[nlevels - 1];
+}
+// triangulation: all kMaxLevels elements of the handle's table, whatever it holds past nlevels (makeScaleTables leaves zeros)
+inline void levelsWholeTable(float (&dst)[kMaxLevels], const float* src) {
+    for (int l = 0; l < kMaxLevels; l++) dst[l] = src[l];
+}
+// Fuse, Sim3, the frustum entries: the first nlevels; the rest stays what it is (zero in a block made with {})
+inline void levelsOnly(float (&dst)[kMaxLevels], const float* src, int nlevels) {
+    for (int l = 0; l < nlevels; l++) dst[l] = src[l];
+}
+
+// ---- growable buffers -------------------------------------------------------------------------------------------------------------
+// Frees and nulls every item, then allocates all of them.  alloc(void** p, size_t bytes) returns false on failure; on the first failure
+// what was obtained is freed again, every pointer is null and the result is false: the caller never holds a part of the set.
+struct GrowItem { void** ptr; size_t bytes; };
+template <class Alloc, class Free>
+inline bool regrow(std::initializer_list<GrowItem> items, Alloc alloc, Free release) {
+    auto drop = [&] { for (const GrowItem& it : items) { if (*it.ptr) release(*it.ptr); *it.ptr = nullptr; } };
+    drop();
+    for (const GrowItem& it : items)
+        if (!alloc(it.ptr, it.bytes)) { *it.ptr = nullptr; drop(); return false; }
+    return true;
+}
+
+}  // namespace orbx

@@ -1,7 +1,9 @@
 // orbx_internal.hpp - what the three host files of liborbx.so share: the launch wrappers the kernel files define, the handle, the error / profiling
 // helpers.  orbx_api.cpp holds the extraction path (create, geometry installation, the launch sequence, the extract entry points, the pyramid),
 // orbx_rows.cpp the rows behind it (stereo matching, Frame finishing, the window searches, the vocabulary and ComputeBoW / SearchByBoW),
-// orbx_debug.cpp the introspection, profiling and test aids.  Not installed: callers see include/orbx.h only.
+// orbx_debug.cpp the introspection, profiling and test aids.  The entry points' plain statements (predicates, parameter fills, padding rules) are
+// in orbx_entry.hpp, which needs no HIP; what they need of the handle or the runtime is at the end of this file.  Not installed: callers see
+// include/orbx.h only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "orbx.h"
+#include "orbx_entry.hpp"
 #include "orbx_geometry.hpp"
 #include "orbx_params.hpp"
 
@@ -229,7 +232,7 @@ struct orbx_handle {
     size_t frustumCountEntries = 0;
     int* d_frustumCounts = nullptr;
     // stereo matching (allocated on first use)
-    int stereoPairs = 0, stereoCap = 0, stereoRows = 0;
+    struct StereoShape { int pairs = 0, cap = 0, rows = 0; } stereo;      // what the six buffers below are sized for
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;
     unsigned short* d_rowList = nullptr;
     float *d_uRight = nullptr, *d_depth = nullptr;
@@ -299,3 +302,64 @@ struct Prof {
     }
 };
 
+// makeFrameGeom says why it refuses an image size; the code is read off that sentence
+inline int geometryRefusalCode(const std::string& why) {
+    return why.find("small") != std::string::npos ? ORBX_ERR_IMAGE_TOO_SMALL : ORBX_ERR_UNSUPPORTED;
+}
+
+// The device orbx_create / orbx_vocabulary_create is to use: *device < 0 names the current one.  A refusal leaves its sentence, with the
+// entry's name in front, in g_createError (there is no handle yet to hold it).
+inline int selectDevice(const char* entry, int* device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        g_createError = std::string(entry) + ": no HIP device (this library has no CPU path)";
+        return ORBX_ERR_NO_DEVICE;
+    }
+    if (*device < 0) {
+        const hipError_t e = hipGetDevice(device);
+        if (e != hipSuccess) { g_createError = std::string("hipGetDevice(&device): ") + hipGetErrorString(e); return ORBX_ERR_HIP; }
+    }
+    if (*device >= ndev) { g_createError = std::string(entry) + ": device index out of range"; return ORBX_ERR_BAD_ARGUMENT; }
+    return ORBX_OK;
+}
+
+// ---- what the entry points of orbx_rows.cpp share and that needs the handle or the runtime (the rest: orbx_entry.hpp) ----------------------
+constexpr const char* kCapacityAbove32767Msg = "capacity above 32767 keypoints per frame";
+
+// Grows a set of handle-owned device buffers (scratch allocated on first use).  The kernels in flight may still read the old ones: the stream
+// drains first.  The recorded capacity says "nothing" from the moment the old buffers go until every new one is there, so a failed
+// allocation leaves null pointers beside a capacity that makes the next call allocate again.
+template <class Cap>
+inline int growDevice(orbx_handle* h, Cap& recorded, const Cap& wanted, std::initializer_list<GrowItem> items) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    recorded = Cap{};
+    hipError_t e = hipSuccess;
+    if (!regrow(items, [&](void** p, size_t bytes) { return (e = hipMalloc(p, bytes)) == hipSuccess; }, [](void* p) { (void)hipFree(p); })) {
+        h->err = std::string("hipMalloc (growDevice): ") + hipGetErrorString(e);
+        return ORBX_ERR_HIP;
+    }
+    recorded = wanted;
+    return ORBX_OK;
+}
+
+// MapPoint::PredictScale's breakpoints for the handle's (scaleFactor, nlevels), computed by the first entry that needs them
+inline int ensureScaleBreaks(orbx_handle* h) {
+    if (h->scaleBreaksReady) return ORBX_OK;
+    if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
+    h->scaleBreaksReady = true;
+    return ORBX_OK;
+}
+
+// the nlevels an entry is given must be the handle's
+inline int sameLevels(orbx_handle* h, int nlevels) {
+    if (nlevels != h->nlevels)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
+    return ORBX_OK;
+}
+
+// the tail of every entry, after its Prof scope has closed: a launch that the runtime refused shows here
+inline int finishLaunch(orbx_handle* h) {
+    HIP_TRY(h, hipGetLastError());
+    return ORBX_OK;
+}

@@ -1,7 +1,8 @@
 // orbx_rows.cpp - the C ABI of the rows behind the extraction (include/orbx.h): ComputeStereoMatches, ComputeStereoFromRGBD, the
 // caller's cvtColor, UndistortKeyPoints + AssignFeaturesToGrid, SearchForInitialization, SearchByProjection, the DBoW2 vocabulary, ComputeBoW and
 // SearchByBoW.  Thin: argument checks, parameter structs, one launch wrapper each (the kernels are in k_stereo / k_frame / k_gray / k_match /
-// k_project / k_bow / k_bow_match.hip).  No CPU path.
+// k_project / k_bow / k_bow_match.hip).  The checks and fills that entries share are stated once, in orbx_entry.hpp (plain) and at the end of
+// orbx_internal.hpp (with the handle); the ORDER of an entry's checks is its own: it decides the code of a call with two bad arguments.  No CPU path.
 #include "orbx_internal.hpp"
 
 extern "C" {
@@ -12,26 +13,18 @@ int bandRows(const orbx_handle* h) { return 2 * (int)std::ceil(2.0 * h->tabs.sca
 
 // k_stereo_filter holds one int per slot of the capacity in dynamic LDS (whole int4s) beside its static block; include/orbx.h documents the bound
 size_t stereoFilterLdsBytes(int capacity) { return 4 * (((size_t)capacity + 3) & ~(size_t)3) + ORBX_STEREO_FILTER_STATIC_LDS_BYTES; }
-bool stereoCapacityFits(int capacity) { return capacity <= 65535 && stereoFilterLdsBytes(capacity) <= 160 * 1024 - 512; }
+bool stereoCapacityFits(int capacity) { return capacity <= 65535 && fitsLds(stereoFilterLdsBytes(capacity)); }
 constexpr const char* kStereoCapacityMsg = "capacity too large for the LDS-resident median filter (4 bytes per slot of the capacity, 160 KB per CU)";
 
 int stereoEnsure(orbx_handle* h, int nPairs, int capacity, int rows) {
-    if (nPairs <= h->stereoPairs && capacity <= h->stereoCap && rows <= h->stereoRows) return ORBX_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    void* old[] = {h->d_rowOff, h->d_sadDist, h->d_nMatched, h->d_rowList, h->d_uRight, h->d_depth};
-    for (void* p : old) if (p) (void)hipFree(p);
-    h->d_rowOff = h->d_sadDist = h->d_nMatched = nullptr; h->d_rowList = nullptr; h->d_uRight = h->d_depth = nullptr;
-    h->stereoPairs = nPairs > h->stereoPairs ? nPairs : h->stereoPairs;
-    h->stereoCap = capacity > h->stereoCap ? capacity : h->stereoCap;
-    h->stereoRows = rows > h->stereoRows ? rows : h->stereoRows;
-    const size_t P = h->stereoPairs, C = h->stereoCap;
-    HIP_TRY(h, hipMalloc(&h->d_rowOff, P * (h->stereoRows + 1) * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->d_rowList, P * C * bandRows(h) * sizeof(unsigned short)));
-    HIP_TRY(h, hipMalloc(&h->d_sadDist, P * C * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->d_nMatched, P * sizeof(int)));
-    HIP_TRY(h, hipMalloc(&h->d_uRight, P * C * sizeof(float)));
-    HIP_TRY(h, hipMalloc(&h->d_depth, P * C * sizeof(float)));
-    return ORBX_OK;
+    const orbx_handle::StereoShape& have = h->stereo;
+    if (nPairs <= have.pairs && capacity <= have.cap && rows <= have.rows) return ORBX_OK;
+    const orbx_handle::StereoShape want{std::max(nPairs, have.pairs), std::max(capacity, have.cap), std::max(rows, have.rows)};      // no dimension shrinks
+    const size_t P = want.pairs, C = want.cap;
+    return growDevice(h, h->stereo, want,
+                      {{(void**)&h->d_rowOff, P * (want.rows + 1) * sizeof(int)}, {(void**)&h->d_rowList, P * C * bandRows(h) * sizeof(unsigned short)},
+                       {(void**)&h->d_sadDist, P * C * sizeof(int)}, {(void**)&h->d_nMatched, P * sizeof(int)},
+                       {(void**)&h->d_uRight, P * C * sizeof(float)}, {(void**)&h->d_depth, P * C * sizeof(float)}});
 }
 
 int stereoEnqueue(orbx_handle* h, int n_pairs, const Keypoint* d_kps, const uint8_t* d_desc, const int* d_n, int capacity,
@@ -42,18 +35,17 @@ int stereoEnqueue(orbx_handle* h, int n_pairs, const Keypoint* d_kps, const uint
     if (!stereoCapacityFits(capacity)) return fail(h, ORBX_ERR_UNSUPPORTED, kStereoCapacityMsg);      // before any launch or allocation
     HIP_TRY(h, hipSetDevice(h->device));
     const int rows = h->geom.rows;
-    int rc = stereoEnsure(h, n_pairs, capacity, rows);
-    if (rc != ORBX_OK) return rc;
+    if (int rc = stereoEnsure(h, n_pairs, capacity, rows)) return rc;
     StereoParams sp;
-    for (int l = 0; l < kMaxLevels; l++) { sp.scale[l] = l < h->nlevels ? h->tabs.scale[l] : 1.f; sp.invScale[l] = l < h->nlevels ? h->tabs.invScale[l] : 1.f; }
-    sp.bf = bf; sp.b = b; sp.nlevels = h->nlevels; sp.capacity = capacity; sp.rowCap = h->stereoCap * bandRows(h);
+    levelsPaddedWithOne(sp.scale, h->tabs.scale, h->nlevels);
+    levelsPaddedWithOne(sp.invScale, h->tabs.invScale, h->nlevels);
+    sp.bf = bf; sp.b = b; sp.nlevels = h->nlevels; sp.capacity = capacity; sp.rowCap = h->stereo.cap * bandRows(h);
     {
         Prof p(h, S_STEREO);
         launchStereo(h->stream, h->d_lv, h->d_pyr, d_kps, d_desc, d_n, sp, rows, h->d_rowOff, h->d_rowList, d_u, d_d, h->d_sadDist,
                      d_nm, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 }  // namespace
 
@@ -65,8 +57,7 @@ int orbx_stereo_match_device(orbx_handle* h, int n_pairs, const orbx_keypoint* d
     return stereoEnqueue(h, n_pairs, (const Keypoint*)d_kps, d_desc, d_n_out, capacity, bf, b, d_u_right, d_depth, d_n_matched);
 }
 
-int orbx_stereo_match_last(orbx_handle* h, int n_pairs, float bf, float b, float* u_right, float* depth, int capacity,
-                           int* n_matched) {
+int orbx_stereo_match_last(orbx_handle* h, int n_pairs, float bf, float b, float* u_right, float* depth, int capacity, int* n_matched) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!u_right || !depth || !n_matched || capacity < 1 || n_pairs < 1) return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity < 1 or n_pairs < 1");
     // the handle only holds results of the host-buffer path (orbx_extract / orbx_extract_batch / _begin + _end); after
@@ -82,10 +73,8 @@ int orbx_stereo_match_last(orbx_handle* h, int n_pairs, float bf, float b, float
         if (n < 0 || n > cap) return fail(h, ORBX_ERR_HIP, "corrupt keypoint count in the handle's staging (internal)");
         if (n > capacity) return fail(h, ORBX_ERR_CAPACITY, "capacity smaller than the left keypoint count");
     }
-    int rc = stereoEnsure(h, n_pairs, cap, h->geom.rows > 0 ? h->geom.rows : 1);
-    if (rc != ORBX_OK) return rc;
-    rc = stereoEnqueue(h, n_pairs, h->dev.k, h->dev.d, h->dev.n, cap, bf, b, h->d_uRight, h->d_depth, h->d_nMatched);
-    if (rc != ORBX_OK) return rc;
+    if (int rc = stereoEnsure(h, n_pairs, cap, h->geom.rows > 0 ? h->geom.rows : 1)) return rc;
+    if (int rc = stereoEnqueue(h, n_pairs, h->dev.k, h->dev.d, h->dev.n, cap, bf, b, h->d_uRight, h->d_depth, h->d_nMatched)) return rc;
     std::vector<float> hu((size_t)n_pairs * cap), hd((size_t)n_pairs * cap);
     HIP_TRY(h, hipMemcpyAsync(hu.data(), h->d_uRight, hu.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(hd.data(), h->d_depth, hd.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -153,8 +142,7 @@ int orbx_stereo_from_rgbd_device(orbx_handle* h, int n_frames, const orbx_keypoi
     p.stride = depth_stride_bytes; p.frame = depth_frame_stride_bytes; p.factor = depth_map_factor; p.mbf = mbf;
     launchStereoFromRgbd(h->stream, (const Keypoint*)d_kps, (const Keypoint*)d_kps_un, d_n_out, (const uint8_t*)d_depth, p, d_u_right,
                          d_depth_out, n_frames);
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_gray_from_color_device(orbx_handle* h, int n_frames, const uint8_t* d_src, int rows, int cols, int channels, int red_first,
@@ -170,47 +158,37 @@ int orbx_gray_from_color_device(orbx_handle* h, int n_frames, const uint8_t* d_s
     p.srcStride = src_stride; p.srcFrame = src_frame_stride; p.dstStride = gray_stride; p.dstFrame = gray_frame_stride;
     p.aligned = (((uintptr_t)d_src | (uintptr_t)src_stride | (uintptr_t)src_frame_stride) & 3) == 0;
     launchGray(h->stream, d_src, d_gray, p, n_frames);
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
-}
-
-static int frameFinish(orbx_handle* h, int n_frames, const orbx_keypoint* d_kps, const int* d_n_out, int capacity, const orbx_camera* cam,
-                       const float* bounds4, orbx_keypoint* d_kps_un, int* d_grid_off, int* d_grid_idx, int* d_n_inside, int rawGrid);
-
-int orbx_frame_finish_device(orbx_handle* h, int n_frames, const orbx_keypoint* d_kps, const int* d_n_out, int capacity,
-                             const orbx_camera* cam, const float* bounds4, orbx_keypoint* d_kps_un, int* d_grid_off,
-                             int* d_grid_idx, int* d_n_inside) {
-    return frameFinish(h, n_frames, d_kps, d_n_out, capacity, cam, bounds4, d_kps_un, d_grid_off, d_grid_idx, d_n_inside, 0);
-}
-
-int orbx_frame_finish_two_eyes_device(orbx_handle* h, int n_pairs, const orbx_keypoint* d_kps, const int* d_n_out, int capacity,
-                                      const orbx_camera* cam, const float* bounds4, orbx_keypoint* d_kps_un, int* d_grid_off,
-                                      int* d_grid_idx, int* d_n_inside) {
-    if (n_pairs < 1 || n_pairs > (1 << 29)) return h ? fail(h, ORBX_ERR_BAD_ARGUMENT, "n_pairs < 1") : ORBX_ERR_BAD_ARGUMENT;
-    return frameFinish(h, 2 * n_pairs, d_kps, d_n_out, capacity, cam, bounds4, d_kps_un, d_grid_off, d_grid_idx, d_n_inside, 1);
+    return finishLaunch(h);
 }
 
 static int frameFinish(orbx_handle* h, int n_frames, const orbx_keypoint* d_kps, const int* d_n_out, int capacity, const orbx_camera* cam,
                        const float* bounds4, orbx_keypoint* d_kps_un, int* d_grid_off, int* d_grid_idx, int* d_n_inside, int rawGrid) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_kps || !d_n_out || !cam || !bounds4 || !d_kps_un || !d_grid_off || !d_grid_idx || !d_n_inside || capacity < 1 ||
-        n_frames < 1 || !(cam->fx > 0.f) || !(cam->fy > 0.f) || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        n_frames < 1 || !(cam->fx > 0.f) || !(cam->fy > 0.f) || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_frames < 1, non-positive focal length or empty bounds");
-    if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity above 32767 keypoints per frame");
+    if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, kCapacityAbove32767Msg);
     HIP_TRY(h, hipSetDevice(h->device));
     FrameFinishParams p;
     p.cam = CameraParams{cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2, cam->k3};
-    p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
-    p.capacity = capacity;
-    p.rawGrid = rawGrid;
+    fillGrid(p, bounds4);
+    p.capacity = capacity; p.rawGrid = rawGrid;
     {
         Prof pr(h, S_FRAME);
         launchFrameFinish(h->stream, (const Keypoint*)d_kps, d_n_out, p, (Keypoint*)d_kps_un, d_grid_off, d_grid_idx, d_n_inside, n_frames);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
+}
+
+int orbx_frame_finish_device(orbx_handle* h, int n_frames, const orbx_keypoint* d_kps, const int* d_n_out, int capacity, const orbx_camera* cam,
+                             const float* bounds4, orbx_keypoint* d_kps_un, int* d_grid_off, int* d_grid_idx, int* d_n_inside) {
+    return frameFinish(h, n_frames, d_kps, d_n_out, capacity, cam, bounds4, d_kps_un, d_grid_off, d_grid_idx, d_n_inside, 0);
+}
+
+int orbx_frame_finish_two_eyes_device(orbx_handle* h, int n_pairs, const orbx_keypoint* d_kps, const int* d_n_out, int capacity, const orbx_camera* cam,
+                                      const float* bounds4, orbx_keypoint* d_kps_un, int* d_grid_off, int* d_grid_idx, int* d_n_inside) {
+    if (n_pairs < 1 || n_pairs > (1 << 29)) return h ? fail(h, ORBX_ERR_BAD_ARGUMENT, "n_pairs < 1") : ORBX_ERR_BAD_ARGUMENT;
+    return frameFinish(h, 2 * n_pairs, d_kps, d_n_out, capacity, cam, bounds4, d_kps_un, d_grid_off, d_grid_idx, d_n_inside, 1);
 }
 
 int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame1_first, int frame1_step, int frame2_first,
@@ -220,16 +198,14 @@ int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame
                                           int check_orientation, int* d_matches12, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_kps_un || !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_prev_matched || !d_matches12 ||
-        !d_n_matches || capacity < 1 || n_pairs < 1 || frame1_first < 0 || frame2_first < 0 || frame1_step < 0 || frame2_step < 0 ||
-        window_size < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        !d_n_matches || capacity < 1 || n_pairs < 1 || negativeFirstOrStep(frame1_first, frame1_step) ||
+        negativeFirstOrStep(frame2_first, frame2_step) || window_size < 0 || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, negative frame index/step/window or empty bounds");
-    if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity above 32767 keypoints per frame");
+    if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, kCapacityAbove32767Msg);
     const int slotCap = initMatchSlotCapacity(capacity);      // >= capacity or 2456: any capacity up to 32767 has a table (include/orbx.h)
     HIP_TRY(h, hipSetDevice(h->device));
     InitMatchParams p;
-    p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    fillGrid(p, bounds4);
     p.r = (float)window_size; p.nnRatio = nn_ratio; p.checkOrientation = check_orientation != 0; p.capacity = capacity; p.slotCapacity = slotCap;
     p.f1First = frame1_first; p.f1Step = frame1_step; p.f2First = frame2_first; p.f2Step = frame2_step;
     {
@@ -237,8 +213,7 @@ int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame
         launchSearchInit(h->stream, (const Keypoint*)d_kps_un, d_desc, d_n_out, d_grid_off, d_grid_idx, p, d_prev_matched, d_matches12,
                          d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_project_last_frame_device(orbx_handle* h, int n_pairs, int last_first, int last_step, int cur_first, int cur_step,
@@ -247,21 +222,20 @@ int orbx_project_last_frame_device(orbx_handle* h, int n_pairs, int last_first, 
                                    const float* bounds4, float mbf, float mb, float th, int mono, orbx_proj_query* d_queries) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_kps || !d_kps_un || !d_n_out || !d_mp_flags || !d_world || !d_poses || !cam || !bounds4 || !d_queries || capacity < 1 || n_pairs < 1 ||
-        n_pairs > 65535 || last_first < 0 || cur_first < 0 || last_step < 0 || cur_step < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        n_pairs > 65535 || negativeFirstOrStep(last_first, last_step) || negativeFirstOrStep(cur_first, cur_step) || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, more than 65535 pairs, negative frame index/step or empty bounds");
     HIP_TRY(h, hipSetDevice(h->device));
     ProjectParams p;
-    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
-    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
-    for (int l = 0; l < kMaxLevels; l++) p.scale[l] = l < h->nlevels ? h->tabs.scale[l] : h->tabs.scale[h->nlevels - 1];   // CurrentFrame.mvScaleFactors
+    fillPinhole(p, *cam);
+    fillBounds(p, bounds4);
+    levelsPaddedWithLast(p.scale, h->tabs.scale, h->nlevels);
     p.mbf = mbf; p.mb = mb; p.th = th; p.mono = mono != 0; p.capacity = capacity;
     p.lastFirst = last_first; p.lastStep = last_step; p.curFirst = cur_first; p.curStep = cur_step;
     {
         Prof pr(h, S_FRAME);
         launchProjectLast(h->stream, (const Keypoint*)d_kps, (const Keypoint*)d_kps_un, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, const orbx_proj_query* d_queries,
@@ -272,27 +246,24 @@ int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first,
                                      int* d_matches, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_queries || !d_query_desc || !d_kps_un || !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_matches || !d_n_matches ||
-        capacity < 1 || query_capacity < 1 || n_pairs < 1 || cur_first < 0 || cur_step < 0 || desc_first < 0 || desc_step < 0 || max_distance < 0 ||
-        !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        capacity < 1 || query_capacity < 1 || n_pairs < 1 || negativeFirstOrStep(cur_first, cur_step) ||
+        negativeFirstOrStep(desc_first, desc_step) || max_distance < 0 || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/query_capacity/n_pairs < 1, negative frame index/step or empty bounds");
-    if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity above 32767 keypoints per frame");
-    if (projSearchLdsBytes(capacity, query_capacity, false) > 160 * 1024 - 512)
+    if (capacity > 32767) return fail(h, ORBX_ERR_UNSUPPORTED, kCapacityAbove32767Msg);
+    if (!fitsLds(projSearchLdsBytes(capacity, query_capacity, false)))
         return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident search (64 bytes per keypoint, 160 KB per CU)");
     HIP_TRY(h, hipSetDevice(h->device));
     ProjSearchParams p;
-    p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    fillGrid(p, bounds4);
     p.nnRatio = nn_ratio; p.ratioMode = ratio_mode != 0; p.checkOrientation = check_orientation != 0;
     p.capacity = capacity; p.queryCapacity = query_capacity; p.curFirst = cur_first; p.curStep = cur_step;
-    p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = max_distance < 255 ? max_distance : 255;
+    p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = clampDistance(max_distance);
     {
         Prof pr(h, S_FRAME);
         launchSearchProj(h->stream, (const ProjQuery*)d_queries, d_query_desc, d_n_queries, (const Keypoint*)d_kps_un, d_desc, d_n_out, d_grid_off,
                          d_grid_idx, d_u_right, d_occupied, p, d_matches, d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int pair_first, int pair_step, const orbx_proj_query* d_queries,
@@ -303,40 +274,37 @@ int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int p
                                               int max_distance, int* d_matches, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_queries || !d_query_desc || !d_kps || !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_matches || !d_n_matches ||
-        capacity < 1 || query_capacity < 1 || n_pairs < 1 || pair_first < 0 || pair_step < 0 || desc_first < 0 || desc_step < 0 || max_distance < 0 ||
-        !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        capacity < 1 || query_capacity < 1 || n_pairs < 1 || negativeFirstOrStep(pair_first, pair_step) ||
+        negativeFirstOrStep(desc_first, desc_step) || max_distance < 0 || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/query_capacity/n_pairs < 1, negative pair/descriptor index or step, "
                                               "negative max_distance or empty bounds");
-    if (capacity > 32767 || query_capacity > (1 << 20) || twoEyesSearchLdsBytes(capacity, query_capacity) > 160 * 1024 - 512)
+    if (capacity > 32767 || query_capacity > (1 << 20) || !fitsLds(twoEyesSearchLdsBytes(capacity, query_capacity)))
         return fail(h, ORBX_ERR_UNSUPPORTED, "capacity / query_capacity too large for the LDS-resident two-eye search (100 bytes per keypoint of "
                                              "an eye, 8 per MapPoint, 12 KB of cell offsets: 160 KB per CU)");
     HIP_TRY(h, hipSetDevice(h->device));
     TwoEyesSearchParams p;
-    p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
+    fillGrid(p, bounds4);
     p.nnRatio = nn_ratio; p.capacity = capacity; p.queryCapacity = query_capacity; p.pairFirst = pair_first; p.pairStep = pair_step;
-    p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = max_distance < 255 ? max_distance : 255; p.forceWalk = h->twoEyesWalk ? 1 : 0;
+    p.descFirst = desc_first; p.descStep = desc_step; p.maxDist = clampDistance(max_distance); p.forceWalk = h->twoEyesWalk ? 1 : 0;
     {
         Prof pr(h, S_FRAME);
         launchSearchProjTwoEyes(h->stream, (const ProjQuery*)d_queries, d_query_desc, d_n_queries, (const Keypoint*)d_kps, d_desc, d_n_out,
                                 d_grid_off, d_grid_idx, d_left_to_right, d_right_to_left, d_occupied, p, d_matches, d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_kb8_project_device(orbx_handle* h, int n, const float* d_xyz, const orbx_camera_kb8* cam, float* d_uv) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_xyz || !cam || !d_uv || n < 1) return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer or n < 1");
     HIP_TRY(h, hipSetDevice(h->device));
-    const float k[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->k3, cam->k4};
+    float k[8];
+    fillKb8(k, *cam);
     {
         Prof pr(h, S_FRAME);
         launchKb8Project(h->stream, d_xyz, k, n, d_uv);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_project_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int last_first, int last_step, int cur_first, int cur_step,
@@ -345,15 +313,14 @@ int orbx_project_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int las
                                             const float* bounds4, float mb, float th, int mono, orbx_proj_query* d_queries) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_kps || !d_n_out || !d_mp_flags || !d_world || !d_poses || !trl12 || !cam || !bounds4 || !d_queries || capacity < 1 || n_pairs < 1 ||
-        n_pairs > 65535 || capacity > (1 << 24) || last_first < 0 || cur_first < 0 || last_step < 0 || cur_step < 0 || !(bounds4[1] > bounds4[0]) ||
-        !(bounds4[3] > bounds4[2]))
+        n_pairs > 65535 || capacity > (1 << 24) || negativeFirstOrStep(last_first, last_step) || negativeFirstOrStep(cur_first, cur_step) ||
+        emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, more than 65535 pairs, negative rig index/step or empty bounds");
     HIP_TRY(h, hipSetDevice(h->device));
     ProjectTwoEyesParams p;
-    const float k[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->k3, cam->k4};
-    for (int i = 0; i < 8; i++) p.cam[i] = k[i];
-    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
-    for (int l = 0; l < kMaxLevels; l++) p.scale[l] = l < h->nlevels ? h->tabs.scale[l] : h->tabs.scale[h->nlevels - 1];   // CurrentFrame.mvScaleFactors
+    fillKb8(p.cam, *cam);
+    fillBounds(p, bounds4);
+    levelsPaddedWithLast(p.scale, h->tabs.scale, h->nlevels);
     for (int i = 0; i < 12; i++) p.trl[i] = trl12[i];
     p.mb = mb; p.th = th; p.mono = mono != 0; p.capacity = capacity;
     p.lastFirst = last_first; p.lastStep = last_step; p.curFirst = cur_first; p.curStep = cur_step;
@@ -361,8 +328,7 @@ int orbx_project_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int las
         Prof pr(h, S_FRAME);
         launchProjectLastTwoEyes(h->stream, (const Keypoint*)d_kps, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_search_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, const orbx_proj_query* d_queries,
@@ -371,25 +337,21 @@ int orbx_search_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int cur_
                                            uint8_t* d_occupied, int max_distance, int check_orientation, int* d_matches, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_queries || !d_query_desc || !d_kps || !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_matches || !d_n_matches ||
-        capacity < 1 || n_pairs < 1 || cur_first < 0 || cur_step < 0 || max_distance < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        capacity < 1 || n_pairs < 1 || negativeFirstOrStep(cur_first, cur_step) || max_distance < 0 || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, negative rig index/step, negative max_distance or empty bounds");
-    if (capacity > 8191 || lastTwoEyesLdsBytes(capacity) > 160 * 1024 - 512)
+    if (capacity > 8191 || !fitsLds(lastTwoEyesLdsBytes(capacity)))
         return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident two-eye frame-to-frame search (96 bytes per keypoint of an "
                                              "eye, 12 per request pair, 12 KB of cell offsets: 160 KB per CU)");
     HIP_TRY(h, hipSetDevice(h->device));
     LastTwoEyesSearchParams p;
-    p.minX = bounds4[0]; p.minY = bounds4[2];
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv (Frame.cc:340)
-    p.checkOrientation = check_orientation != 0; p.capacity = capacity; p.curFirst = cur_first; p.curStep = cur_step;
-    p.maxDist = max_distance < 255 ? max_distance : 255;
+    fillGrid(p, bounds4);
+    p.checkOrientation = check_orientation != 0; p.capacity = capacity; p.curFirst = cur_first; p.curStep = cur_step; p.maxDist = clampDistance(max_distance);
     {
         Prof pr(h, S_FRAME);
         launchSearchLastTwoEyes(h->stream, (const ProjQuery*)d_queries, d_query_desc, (const Keypoint*)d_kps, d_desc, d_n_out, d_grid_off, d_grid_idx,
                                 d_occupied, p, d_matches, d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 }  // extern "C"
@@ -438,10 +400,7 @@ int orbx_vocabulary_create(orbx_vocabulary** out, int k, int L, int scoring, int
     if (!cnt[0]) { g_createError = "orbx_vocabulary_create: the root has no children"; return ORBX_ERR_BAD_ARGUMENT; }
     for (int n = 0; n < n_nodes; n++)      // k_bow_words packs (distance << 8 | child rank): a node's fan-out must fit the rank byte
         if (cnt[n] > 256) { g_createError = "orbx_vocabulary_create: a node with more than 256 children (the header's k allows at most 20)"; return ORBX_ERR_BAD_ARGUMENT; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_createError = "orbx_vocabulary_create: no HIP device (this library has no CPU path)"; return ORBX_ERR_NO_DEVICE; }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return ORBX_ERR_HIP;
-    if (device >= ndev) { g_createError = "orbx_vocabulary_create: device index out of range"; return ORBX_ERR_BAD_ARGUMENT; }
+    if (int rc = selectDevice("orbx_vocabulary_create", &device)) return rc;
     orbx_vocabulary* v = new orbx_vocabulary();
     v->device = device; v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting; v->nNodes = n_nodes; v->nWords = words;
     // the uploads go through a stream of their own and the function returns when THAT stream has drained: the tables have landed before any
@@ -517,24 +476,17 @@ int orbx_compute_bow_device(orbx_handle* h, const orbx_vocabulary* v, int n_fram
     if (capacity > 16384) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity above 16384 keypoints per frame (the per-frame sort runs in LDS)");
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t need = (size_t)n_frames * capacity;
-    if (need > h->bowEntries) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        void* old[] = {h->d_bowWord, h->d_bowNode, h->d_bowWeight};
-        for (void* p : old) if (p) (void)hipFree(p);
-        h->d_bowWord = h->d_bowNode = nullptr; h->d_bowWeight = nullptr; h->bowEntries = 0;
-        HIP_TRY(h, hipMalloc(&h->d_bowWord, need * sizeof(uint32_t)));
-        HIP_TRY(h, hipMalloc(&h->d_bowNode, need * sizeof(uint32_t)));
-        HIP_TRY(h, hipMalloc(&h->d_bowWeight, need * sizeof(double)));
-        h->bowEntries = need;
-    }
+    if (need > h->bowEntries)
+        if (int rc = growDevice(h, h->bowEntries, need, {{(void**)&h->d_bowWord, need * sizeof(uint32_t)},
+                                                         {(void**)&h->d_bowNode, need * sizeof(uint32_t)}, {(void**)&h->d_bowWeight, need * sizeof(double)}}))
+            return rc;
     VocabDevice V{v->d_childOff, v->d_childList, v->d_desc, v->d_weight, v->d_wordId, v->nNodes, v->k, v->L, v->scoring, v->weighting};
     {
         Prof pr(h, S_FRAME);
         launchBow(h->stream, V, d_desc, d_n_out, capacity, levels_up, h->d_bowWord, h->d_bowWeight, h->d_bowNode, d_word_ids, d_word_weights, d_n_words,
                   d_feat_nodes, d_feat_idx, d_n_feat, n_frames);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 static int searchByBow(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int cur_first, int cur_step, const uint32_t* d_feat_nodes,
@@ -543,10 +495,9 @@ static int searchByBow(orbx_handle* h, int n_pairs, int kf_first, int kf_step, i
                        int check_orientation, int* d_matches, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_feat_nodes || !d_feat_idx || !d_n_feat || !d_kf_mp_flags || !d_kps || !d_desc || !d_n_out || !d_matches || !d_n_matches ||
-        capacity < 1 || n_pairs < 1 || kf_first < 0 || cur_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
-        cur_first + (long long)(n_pairs - 1) * cur_step < 0)
+        capacity < 1 || n_pairs < 1 || negativeWalk(kf_first, kf_step, n_pairs) || negativeWalk(cur_first, cur_step, n_pairs))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1 or a negative frame index");
-    if (capacity > 65535 || bowMatchLdsBytes(capacity, false) > 150 * 1024) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large: the node columns and the match table of a pair live in LDS");
+    if (capacity > 65535 || bowMatchLdsBytes(capacity, false) > kBowMatchLdsBudget) return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large: the node columns and the match table of a pair live in LDS");
     HIP_TRY(h, hipSetDevice(h->device));
     BowMatchParams p{nn_ratio, th_low, check_orientation ? 1 : 0, capacity, kf_first, kf_step, cur_first, cur_step, d_cur_mp_flags ? 1 : 0};
     {
@@ -554,8 +505,7 @@ static int searchByBow(orbx_handle* h, int n_pairs, int kf_first, int kf_step, i
         launchSearchBow(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, d_cur_mp_flags, (const Keypoint*)d_kps, d_desc, d_n_out, p, d_matches,
                         d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 int orbx_search_by_bow_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int cur_first, int cur_step,
                               const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat, const uint8_t* d_kf_mp_flags,
@@ -580,22 +530,20 @@ int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first
                                        int capacity, float nn_ratio, int th_low, int check_orientation, int* d_matches, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_feat_nodes || !d_feat_idx || !d_n_feat || !d_kf_mp_flags || !d_kps || !d_desc || !d_n_out || !d_matches || !d_n_matches ||
-        capacity < 1 || n_pairs < 1 || kf_first < 0 || cur_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
-        cur_first + (long long)(n_pairs - 1) * cur_step < 0)
+        capacity < 1 || n_pairs < 1 || negativeWalk(kf_first, kf_step, n_pairs) || negativeWalk(cur_first, cur_step, n_pairs))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1 or a negative pair index");
-    if (bowTwoEyesLdsBytes(capacity, false) > 160 * 1024 - 512)
+    if (!fitsLds(bowTwoEyesLdsBytes(capacity, false)))
         return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident two-eye BoW search (40 bytes per slot of the capacity "
                                              "rounded up to 16, + 64: 160 KB per CU)");
     HIP_TRY(h, hipSetDevice(h->device));
-    BowTwoEyesParams p{nn_ratio, th_low < 255 ? th_low : 255, check_orientation ? 1 : 0, capacity, kf_first, kf_step, cur_first, cur_step};
-    const bool stage = h->twoEyesBowStage && bowTwoEyesLdsBytes(capacity, true) <= 160 * 1024 - 512;
+    BowTwoEyesParams p{nn_ratio, clampDistance(th_low), check_orientation ? 1 : 0, capacity, kf_first, kf_step, cur_first, cur_step};
+    const bool stage = h->twoEyesBowStage && fitsLds(bowTwoEyesLdsBytes(capacity, true));
     {
         Prof pr(h, S_FRAME);
         launchSearchBowTwoEyes(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, (const Keypoint*)d_kps, d_desc, d_n_out, p, stage,
                                d_matches, d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
@@ -606,26 +554,26 @@ int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_fi
                                          int* d_matches12, int* d_pairs, int* d_n_matches) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_feat_nodes || !d_feat_idx || !d_n_feat || !d_kf1_mp_flags || !d_kf2_mp_flags || !d_kps_un || !d_desc || !d_n_out || !d_f12 ||
-        !d_epipole || !d_matches12 || !d_pairs || !d_n_matches || capacity < 1 || n_pairs < 1 || kf1_first < 0 || kf2_first < 0 ||
-        kf1_first + (long long)(n_pairs - 1) * kf1_step < 0 || kf2_first + (long long)(n_pairs - 1) * kf2_step < 0)
+        !d_epipole || !d_matches12 || !d_pairs || !d_n_matches || capacity < 1 || n_pairs < 1 || negativeWalk(kf1_first, kf1_step, n_pairs) ||
+        negativeWalk(kf2_first, kf2_step, n_pairs))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1 or a negative frame index");
-    if (triMatchLdsBytes(capacity, false) > 160 * 1024 - 512)
+    if (!fitsLds(triMatchLdsBytes(capacity, false)))
         return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident triangulation search (28 bytes per slot of the capacity "
                                              "rounded up to 16, + 64: 160 KB per CU)");
     HIP_TRY(h, hipSetDevice(h->device));
     TriMatchParams p{};
-    for (int i = 0; i < kMaxLevels; i++) { p.scale[i] = h->tabs.scale[i]; p.sigma2[i] = h->tabs.sigma2[i]; }
+    levelsWholeTable(p.scale, h->tabs.scale);
+    levelsWholeTable(p.sigma2, h->tabs.sigma2);
     p.nlevels = std::max(1, std::min(h->nlevels, (int)kMaxLevels));
     p.thLow = th_low; p.checkOrientation = check_orientation ? 1 : 0; p.onlyStereo = only_stereo ? 1 : 0; p.coarse = coarse ? 1 : 0;
     p.capacity = capacity; p.kf1First = kf1_first; p.kf1Step = kf1_step; p.kf2First = kf2_first; p.kf2Step = kf2_step;
-    const bool stage = triMatchLdsBytes(capacity, true) <= 160 * 1024 - 512;
+    const bool stage = fitsLds(triMatchLdsBytes(capacity, true));
     {
         Prof pr(h, S_FRAME);
         launchSearchTriangulation(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, (const Keypoint*)d_kps_un, d_u_right,
                                   d_desc, d_n_out, d_f12, d_epipole, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step, const float* d_mp_world,
@@ -637,29 +585,20 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !d_kps_un || !d_desc || !d_n_out || !d_grid_off ||
         !d_grid_idx || !bounds4 || !cam || !d_best_idx || !d_best_dist || !d_n_fused || capacity < 1 || mp_capacity < 1 || n_pairs < 1 ||
-        n_pairs > 65535 || kf_first < 0 || mp_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
-        mp_first + (long long)(n_pairs - 1) * mp_step < 0 || th_low < 0 || !(bounds4[1] > bounds4[0]) || !(bounds4[3] > bounds4[2]))
+        n_pairs > 65535 || negativeWalk(kf_first, kf_step, n_pairs) || negativeWalk(mp_first, mp_step, n_pairs) || th_low < 0 || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/mp_capacity/n_pairs < 1, more than 65535 pairs, a negative keyframe or list "
                                               "index, negative th_low or empty bounds");
-    if (nlevels != h->nlevels)
-        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
-    if (!h->scaleBreaksReady) {
-        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
-            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
-        h->scaleBreaksReady = true;
-    }
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (int rc = ensureScaleBreaks(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     FuseParams p{};
-    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
-    // KeyFrame's mnMinX .. mnMaxY are const int (inc/KeyFrame.h:484) initialised from Frame's floats (KeyFrame.cc:58): truncated toward zero.
-    // IsInImage (:816-819) and GetFeaturesInArea (:778-790) compare with and subtract the truncated values ...
-    p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
-    // ... but scale by Frame's inverses, made from the untruncated floats and copied as they are (Frame.cc:339-340, KeyFrame.cc:50)
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);      // mfGridElementHeightInv
-    for (int l = 0; l < h->nlevels; l++) { p.scale[l] = h->tabs.scale[l]; p.invSigma2[l] = h->tabs.invSigma2[l]; }
-    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
-    p.mbf = mbf; p.th = th; p.nlevels = h->nlevels; p.thLow = th_low < 255 ? th_low : 255; p.reprojCheck = reproj_check ? 1 : 0;
+    fillPinhole(p, *cam);
+    fillBoundsTruncated(p, bounds4);      // a KeyFrame's bounds ...
+    fillGridInverses(p, bounds4);         // ... and the Frame's inverses it copied
+    levelsOnly(p.scale, h->tabs.scale, h->nlevels);
+    levelsOnly(p.invSigma2, h->tabs.invSigma2, h->nlevels);
+    fillBreaks(p, h->scaleBreaks, h->nlevels);
+    p.mbf = mbf; p.th = th; p.nlevels = h->nlevels; p.thLow = clampDistance(th_low); p.reprojCheck = reproj_check ? 1 : 0;
     p.capacity = capacity; p.mpCapacity = mp_capacity; p.kfFirst = kf_first; p.kfStep = kf_step; p.mpFirst = mp_first; p.mpStep = mp_step;
     {
         Prof pr(h, S_FRAME);
@@ -667,8 +606,7 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
         launchFuse(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps_un, d_u_right, d_desc,
                    d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_sim3_hamming_bound(int th_low, float ratio_hamming) {
@@ -687,38 +625,25 @@ int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_fi
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
     if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !d_kps_un || !d_desc || !d_n_out || !d_grid_off ||
         !d_grid_idx || !bounds4 || !cam || !d_matches || !d_match_idx || !d_match_dist || !d_n_matches || capacity < 1 || mp_capacity < 1 ||
-        n_pairs < 1 || n_pairs > 65535 || kf_first < 0 || mp_first < 0 || kf_first + (long long)(n_pairs - 1) * kf_step < 0 ||
-        mp_first + (long long)(n_pairs - 1) * mp_step < 0 || th_low < 0 || (projection != 0 && projection != 1) || !(bounds4[1] > bounds4[0]) ||
-        !(bounds4[3] > bounds4[2]))
+        n_pairs < 1 || n_pairs > 65535 || negativeWalk(kf_first, kf_step, n_pairs) || negativeWalk(mp_first, mp_step, n_pairs) || th_low < 0 ||
+        (projection != 0 && projection != 1) || emptyBounds(bounds4))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/mp_capacity/n_pairs < 1, more than 65535 pairs, a negative keyframe or list "
                                               "index, negative th_low, a projection form other than 0 / 1 or empty bounds");
-    if (nlevels != h->nlevels)
-        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
-    if (capacity > 65536 || sim3SettleLdsBytes(capacity, mp_capacity) > 160 * 1024 - 512)
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (capacity > 65536 || !fitsLds(sim3SettleLdsBytes(capacity, mp_capacity)))
         return fail(h, ORBX_ERR_UNSUPPORTED, "capacity / mp_capacity too large for the LDS-resident settling of the Sim3 projection search "
                                              "(4 bytes per keypoint + 4 per MapPoint, + 64: 160 KB per CU; a key holds a 16-bit slot)");
-    if (!h->scaleBreaksReady) {
-        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
-            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
-        h->scaleBreaksReady = true;
-    }
+    if (int rc = ensureScaleBreaks(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t need = (size_t)n_pairs * mp_capacity;
-    if (need > h->sim3Entries) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_sim3Rec) (void)hipFree(h->d_sim3Rec);
-        h->d_sim3Rec = nullptr; h->sim3Entries = 0;
-        HIP_TRY(h, hipMalloc(&h->d_sim3Rec, need * sim3RecordBytes()));      // what k_sim3_window leaves for k_sim3_settle
-        h->sim3Entries = need;
-    }
+    if (need > h->sim3Entries)      // what k_sim3_window leaves for k_sim3_settle
+        if (int rc = growDevice(h, h->sim3Entries, need, {{&h->d_sim3Rec, need * sim3RecordBytes()}})) return rc;
     Sim3SearchParams p{};
-    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
-    // KeyFrame's truncated bounds and Frame's untruncated inverses, as orbx_fuse_device
-    p.minX = truncf(bounds4[0]); p.maxX = truncf(bounds4[1]); p.minY = truncf(bounds4[2]); p.maxY = truncf(bounds4[3]);
-    p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);
-    p.hInv = (float)kGridRows / (bounds4[3] - bounds4[2]);
-    for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
-    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    fillPinhole(p, *cam);
+    fillBoundsTruncated(p, bounds4);      // a KeyFrame's bounds and the Frame's inverses, as orbx_fuse_device
+    fillGridInverses(p, bounds4);
+    levelsOnly(p.scale, h->tabs.scale, h->nlevels);
+    fillBreaks(p, h->scaleBreaks, h->nlevels);
     p.th = th; p.nlevels = h->nlevels; p.maxDist = orbx_sim3_hamming_bound(th_low, ratio_hamming); p.projection = projection;
     p.capacity = capacity; p.mpCapacity = mp_capacity; p.kfFirst = kf_first; p.kfStep = kf_step; p.mpFirst = mp_first; p.mpStep = mp_step;
     {
@@ -727,8 +652,7 @@ int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_fi
                          d_n_out, d_grid_off, d_grid_idx, d_occupied, p, h->d_sim3Rec, d_matches, d_match_idx, d_match_dist, d_exit,
                          d_n_matches, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, int mp_first, int mp_step, const float* d_mp_world,
@@ -743,23 +667,16 @@ int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int
     // the normals are read by the local-map mode alone, the keypoint angles by the relocalisation mode alone
     if (!d_mp_world || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !cam || !bounds4 || !d_queries || !d_query_desc || !d_query_src ||
         !d_n_queries || !d_track || !d_n_in_view || (mode == ORBX_FRUSTUM_LOCAL_MAP ? !d_mp_normal : !d_mp_angle) || mp_capacity < 1 ||
-        n_pairs < 1 || cur_first < 0 || mp_first < 0 || cur_first + (long long)(n_pairs - 1) * cur_step < 0 ||
-        mp_first + (long long)(n_pairs - 1) * mp_step < 0)
+        n_pairs < 1 || negativeWalk(cur_first, cur_step, n_pairs) || negativeWalk(mp_first, mp_step, n_pairs))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, mp_capacity/n_pairs < 1 or a negative frame or list index");
-    if (nlevels != h->nlevels)
-        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
-    if (!h->scaleBreaksReady) {
-        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
-            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
-        h->scaleBreaksReady = true;
-    }
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (int rc = ensureScaleBreaks(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     FrustumParams p{};
-    p.fx = cam->fx; p.fy = cam->fy; p.cx = cam->cx; p.cy = cam->cy;
-    // Frame's own float bounds, compared as they are (Frame.cc:520-523, ORBmatcher.cc:2209-2212): no truncation here, unlike orbx_fuse_device
-    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
-    for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
-    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    fillPinhole(p, *cam);
+    fillBounds(p, bounds4);      // a Frame's: no truncation here, unlike orbx_fuse_device
+    levelsOnly(p.scale, h->tabs.scale, h->nlevels);
+    fillBreaks(p, h->scaleBreaks, h->nlevels);
     p.mbf = mbf; p.viewCosLimit = view_cos_limit; p.th = th; p.thFarPoints = th_far_points;
     p.nlevels = h->nlevels; p.mode = mode; p.farPoints = far_points ? 1 : 0; p.mpCapacity = mp_capacity;
     p.curFirst = cur_first; p.curStep = cur_step; p.mpFirst = mp_first; p.mpStep = mp_step;
@@ -768,8 +685,7 @@ int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int
         launchFrustum(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_mp_angle, d_n_mp, d_mp_flags, d_poses, p, (ProjQuery*)d_queries,
                       d_query_desc, d_query_src, d_n_queries, (TrackRecord*)d_track, d_n_in_view, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 int orbx_frustum_requests_two_eyes_device(orbx_handle* h, int n_pairs, int cur_first, int cur_step, int mp_first, int mp_step,
@@ -784,37 +700,23 @@ int orbx_frustum_requests_two_eyes_device(orbx_handle* h, int n_pairs, int cur_f
     // d_n_mp, d_mp_prev_depth and d_n_wanted may be NULL
     if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !trl12 || !tlr12 || !cam_left || !cam_right ||
         !bounds4 || !d_queries || !d_query_desc || !d_query_src || !d_n_queries || !d_track || !d_n_in_view || mp_capacity < 1 ||
-        mp_capacity > (1 << 30) || query_capacity < 1 || query_capacity > mp_capacity || n_pairs < 1 || n_pairs > 65535 || cur_first < 0 ||
-        mp_first < 0 || cur_first + (long long)(n_pairs - 1) * cur_step < 0 || mp_first + (long long)(n_pairs - 1) * mp_step < 0)
+        mp_capacity > (1 << 30) || query_capacity < 1 || query_capacity > mp_capacity || n_pairs < 1 || n_pairs > 65535 ||
+        negativeWalk(cur_first, cur_step, n_pairs) || negativeWalk(mp_first, mp_step, n_pairs))
         return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, mp_capacity/n_pairs < 1, more than 65535 pairs, a query_capacity outside 1 .. mp_capacity "
                                               "or a negative rig or list index");
-    if (nlevels != h->nlevels)
-        return fail(h, ORBX_ERR_BAD_ARGUMENT, "nlevels differs from the handle's: the scale tables and PredictScale's breakpoints are the handle's");
-    if (!h->scaleBreaksReady) {
-        if (orbx_predict_scale_breakpoints(h->scaleFactor, h->nlevels, h->scaleBreaks) != ORBX_OK)
-            return fail(h, ORBX_ERR_BAD_ARGUMENT, "no PredictScale breakpoints for the handle's scale factor");
-        h->scaleBreaksReady = true;
-    }
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (int rc = ensureScaleBreaks(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     FrustumTwoEyesParams p{};
     p.groups = frustumTwoEyesGroups(mp_capacity);
     const size_t need = (size_t)n_pairs * p.groups * 2;
-    if (need > h->frustumCountEntries) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->d_frustumCounts) (void)hipFree(h->d_frustumCounts);
-        h->d_frustumCounts = nullptr; h->frustumCountEntries = 0;
-        HIP_TRY(h, hipMalloc(&h->d_frustumCounts, need * sizeof(int)));      // what k_frustum_two_eyes_check leaves for k_frustum_two_eyes_place
-        h->frustumCountEntries = need;
-    }
-    const orbx_camera_kb8* cams[2] = {cam_left, cam_right};                  // mpCamera, mpCamera2 (Frame.cc:1210-1211)
-    for (int e = 0; e < 2; e++) {
-        const float k[8] = {cams[e]->fx, cams[e]->fy, cams[e]->cx, cams[e]->cy, cams[e]->k1, cams[e]->k2, cams[e]->k3, cams[e]->k4};
-        for (int i = 0; i < 8; i++) p.cam[e][i] = k[i];
-    }
-    // Frame's own float bounds, compared as they are (Frame.cc:1213-1216); the same four for both eyes
-    p.minX = bounds4[0]; p.maxX = bounds4[1]; p.minY = bounds4[2]; p.maxY = bounds4[3];
-    for (int l = 0; l < h->nlevels; l++) p.scale[l] = h->tabs.scale[l];
-    for (int l = 0; l + 1 < h->nlevels; l++) p.breaks[l] = h->scaleBreaks[l];
+    if (need > h->frustumCountEntries)      // what k_frustum_two_eyes_check leaves for k_frustum_two_eyes_place
+        if (int rc = growDevice(h, h->frustumCountEntries, need, {{(void**)&h->d_frustumCounts, need * sizeof(int)}})) return rc;
+    fillKb8(p.cam[0], *cam_left);       // mpCamera, mpCamera2 (Frame.cc:1210-1211)
+    fillKb8(p.cam[1], *cam_right);
+    fillBounds(p, bounds4);             // the same four for both eyes
+    levelsOnly(p.scale, h->tabs.scale, h->nlevels);
+    fillBreaks(p, h->scaleBreaks, h->nlevels);
     for (int i = 0; i < 12; i++) { p.trl[i] = trl12[i]; p.tlr[i] = tlr12[i]; }
     p.viewCosLimit = view_cos_limit; p.th = th; p.thFarPoints = th_far_points;
     p.nlevels = h->nlevels; p.farPoints = far_points ? 1 : 0; p.mpCapacity = mp_capacity; p.queryCapacity = query_capacity;
@@ -825,8 +727,7 @@ int orbx_frustum_requests_two_eyes_device(orbx_handle* h, int n_pairs, int cur_f
                              h->d_frustumCounts, (ProjQuery*)d_queries, d_query_desc, d_query_src, d_n_queries, d_n_wanted, (TrackRecord*)d_track,
                              d_n_in_view, n_pairs);
     }
-    HIP_TRY(h, hipGetLastError());
-    return ORBX_OK;
+    return finishLaunch(h);
 }
 
 }  // extern "C"

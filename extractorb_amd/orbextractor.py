@@ -236,6 +236,31 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dev(x):
+    """a device pointer argument: None (NULL: optional, or refused by the C entry with ORBX_ERR_BAD_ARGUMENT), an int, or an object with .data_ptr()"""
+    return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
+
+
+def _host_f32(a):
+    """a small host array the C entry reads during the call (camera, bounds, a 3x4 transform): None stays NULL"""
+    return None if a is None else _ptr(np.ascontiguousarray(a, np.float32))
+
+
+def _split_levels(lvl, counts):
+    """the per-level keypoint arrays out of the level-major array and its counts"""
+    per_level, o = [], 0
+    for c in counts.tolist():
+        per_level.append(lvl[o:o + c].copy()); o += c
+    return per_level
+
+
+def _lapping(lapping, n):
+    """vLappingArea per frame as int32 [n, 2] (one pair is given to every frame), or None"""
+    if lapping is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(lapping, np.int32).reshape(-1, 2), (n, 2)))
+
+
 # ---- test aids (include/orbx.h: orbx_debug_set_option).  Not reachable from the environment; handles created AFTERWARDS carry the setting ----
 TEST_AIDS = ("poison", "lds_pollute", "fail_after_fast")
 
@@ -340,7 +365,7 @@ def compute_image_bounds(cam, cols, rows):
     """Frame::ComputeImageBounds (reference src/Frame.cc:784-811): (mnMinX, mnMaxX, mnMinY, mnMaxY).  Host only."""
     L = load_library()
     b = np.zeros(4, np.float32)
-    rc = L.orbx_compute_image_bounds(_ptr(np.ascontiguousarray(cam, np.float32)), cols, rows, _ptr(b))
+    rc = L.orbx_compute_image_bounds(_host_f32(cam), cols, rows, _ptr(b))
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbx_compute_image_bounds")
     return b
@@ -411,10 +436,7 @@ class ORBextractor:
         self._check(self._L.orbx_extract(self._h, _ptr(image), image.shape[0], image.shape[1], image.strides[0],
                                          int(lapping[0]), int(lapping[1]), _ptr(kps), _ptr(desc), cap,
                                          C.byref(n), C.byref(mono), _ptr(lvl), _ptr(counts)))
-        per_level, o = [], 0
-        for c in counts.tolist():
-            per_level.append(lvl[o:o + c].copy()); o += c
-        return mono.value, kps[:n.value].copy(), desc[:n.value].copy(), per_level
+        return mono.value, kps[:n.value].copy(), desc[:n.value].copy(), _split_levels(lvl, counts)
 
     def extract_batch(self, images, lapping=None):
         """images: uint8 [B, rows, cols].  Returns a list of (mono_index, keypoints, descriptors, per_level)."""
@@ -424,27 +446,17 @@ class ORBextractor:
         kps = np.zeros((B, cap), KEYPOINT_DTYPE); desc = np.zeros((B, cap, 32), np.uint8)
         lvl = np.zeros((B, cap), KEYPOINT_DTYPE); counts = np.zeros((B, self.nlevels), np.int32)
         n = np.zeros(B, np.int32); mono = np.zeros(B, np.int32)
-        lap = None
-        if lapping is not None:
-            lap = np.ascontiguousarray(np.broadcast_to(np.asarray(lapping, np.int32).reshape(-1, 2), (B, 2)))
+        lap = _lapping(lapping, B)
         self._check(self._L.orbx_extract_batch(self._h, B, _ptr(images), rows, cols, cols, rows * cols, _ptr(lap),
                                                _ptr(kps), _ptr(desc), cap, _ptr(n), _ptr(mono), _ptr(lvl), _ptr(counts)))
-        out = []
-        for f in range(B):
-            per_level, o = [], 0
-            for c in counts[f].tolist():
-                per_level.append(lvl[f, o:o + c].copy()); o += c
-            out.append((int(mono[f]), kps[f, :n[f]].copy(), desc[f, :n[f]].copy(), per_level))
-        return out
+        return [(int(mono[f]), kps[f, :n[f]].copy(), desc[f, :n[f]].copy(), _split_levels(lvl[f], counts[f])) for f in range(B)]
 
     def extract_batch_begin(self, images, lapping=None, want_levels=False):
         """Asynchronous host-buffer form: enqueue H2D + path + D2H and return (one batch in flight per handle)."""
         # rows may be padded (a view into a wider buffer, as a cv::Mat ROI): stride / frame_stride are passed as they are
         assert images.dtype == np.uint8 and images.ndim == 3 and images.strides[2] == 1 and images.strides[1] >= images.shape[2] and images.strides[0] > 0
         B, rows, cols = images.shape
-        lap = None
-        if lapping is not None:
-            lap = np.ascontiguousarray(np.broadcast_to(np.asarray(lapping, np.int32).reshape(-1, 2), (B, 2)))
+        lap = _lapping(lapping, B)
         self._check(self._L.orbx_extract_batch_begin(self._h, B, _ptr(images), rows, cols, images.strides[1], images.strides[0], _ptr(lap), int(want_levels)))
         self._pending = (B, images, lap)     # keep the buffers alive until the batch ends
 
@@ -477,16 +489,12 @@ class ORBextractor:
     def extract_batch_device(self, d_images, n_frames, rows, cols, d_kps, d_desc, d_n, d_mono, capacity,
                              stride=None, frame_stride=None, lapping=None, d_level_kps=0, d_level_counts=0):
         """Device-pointer form (ints or objects with .data_ptr()); asynchronous on the handle's stream."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
         stride = cols if stride is None else stride
         frame_stride = rows * stride if frame_stride is None else frame_stride
-        lap = None
-        if lapping is not None:
-            lap = np.ascontiguousarray(np.broadcast_to(np.asarray(lapping, np.int32).reshape(-1, 2), (n_frames, 2)))
-        self._check(self._L.orbx_extract_batch_device(self._h, n_frames, dp(d_images), rows, cols, stride, frame_stride,
-                                                      _ptr(lap), dp(d_kps), dp(d_desc), capacity, dp(d_n), dp(d_mono),
-                                                      dp(d_level_kps), dp(d_level_counts)))
+        lap = _lapping(lapping, n_frames)
+        self._check(self._L.orbx_extract_batch_device(self._h, n_frames, _dev(d_images), rows, cols, stride, frame_stride,
+                                                      _ptr(lap), _dev(d_kps), _dev(d_desc), capacity, _dev(d_n), _dev(d_mono),
+                                                      _dev(d_level_kps), _dev(d_level_counts)))
 
     # ---- Frame::ComputeStereoMatches (reference src/Frame.cc:813-991) on the last batch ----
     def stereo_match_last(self, n_pairs, bf, b):
@@ -499,63 +507,46 @@ class ORBextractor:
         return u, d, nm
 
     def stereo_match_device(self, n_pairs, d_kps, d_desc, d_n, capacity, bf, b, d_u_right, d_depth, d_n_matched):
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self._L.orbx_stereo_match_device(self._h, n_pairs, dp(d_kps), dp(d_desc), dp(d_n), capacity, bf, b,
-                                                     dp(d_u_right), dp(d_depth), dp(d_n_matched)))
+        self._check(self._L.orbx_stereo_match_device(self._h, n_pairs, _dev(d_kps), _dev(d_desc), _dev(d_n), capacity, bf, b,
+                                                     _dev(d_u_right), _dev(d_depth), _dev(d_n_matched)))
 
     def frame_finish_device(self, n_frames, d_kps, d_n, capacity, cam, bounds, d_kps_un, d_grid_off, d_grid_idx, d_n_inside):
         """UndistortKeyPoints + AssignFeaturesToGrid (reference src/Frame.cc:748-782, 383-417) on device buffers."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        cam = np.ascontiguousarray(cam, np.float32); bounds = np.ascontiguousarray(bounds, np.float32)
-        self._check(self._L.orbx_frame_finish_device(self._h, n_frames, dp(d_kps), dp(d_n), capacity, _ptr(cam), _ptr(bounds),
-                                                     dp(d_kps_un), dp(d_grid_off), dp(d_grid_idx), dp(d_n_inside)))
+        self._check(self._L.orbx_frame_finish_device(self._h, n_frames, _dev(d_kps), _dev(d_n), capacity, _host_f32(cam), _host_f32(bounds),
+                                                     _dev(d_kps_un), _dev(d_grid_off), _dev(d_grid_idx), _dev(d_n_inside)))
 
     def frame_finish_two_eyes_device(self, n_pairs, d_kps, d_n, capacity, cam, bounds, d_kps_un, d_grid_off, d_grid_idx, d_n_inside):
         """AssignFeaturesToGrid's Nleft != -1 branch (reference src/Frame.cc:404-414: mGrid / mGridRight from the RAW keys of frames 2p / 2p + 1)
         + UndistortKeyPoints, on device buffers of 2 * n_pairs frames."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        cam = np.ascontiguousarray(cam, np.float32); bounds = np.ascontiguousarray(bounds, np.float32)
-        self._check(self._L.orbx_frame_finish_two_eyes_device(self._h, n_pairs, dp(d_kps), dp(d_n), capacity, _ptr(cam), _ptr(bounds),
-                                                              dp(d_kps_un), dp(d_grid_off), dp(d_grid_idx), dp(d_n_inside)))
+        self._check(self._L.orbx_frame_finish_two_eyes_device(self._h, n_pairs, _dev(d_kps), _dev(d_n), capacity, _host_f32(cam), _host_f32(bounds),
+                                                              _dev(d_kps_un), _dev(d_grid_off), _dev(d_grid_idx), _dev(d_n_inside)))
 
     def search_for_initialization_device(self, n_pairs, frames1, frames2, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx,
                                          bounds, d_prev_matched, d_matches12, d_n_matches, window=100, nnratio=0.9,
                                          check_orientation=True):
         """ORBmatcher::SearchForInitialization (reference src/ORBmatcher.cc:706-821) for n_pairs pairs of device-resident
         frames; frames1 / frames2 = (first, step) of the F1 / F2 frame index of pair p."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        bounds = np.ascontiguousarray(bounds, np.float32)
         self._check(self._L.orbx_search_for_initialization_device(
-            self._h, n_pairs, frames1[0], frames1[1], frames2[0], frames2[1], dp(d_kps_un), dp(d_desc), dp(d_n), capacity,
-            dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), dp(d_prev_matched), window, nnratio, int(check_orientation),
-            dp(d_matches12), dp(d_n_matches)))
+            self._h, n_pairs, frames1[0], frames1[1], frames2[0], frames2[1], _dev(d_kps_un), _dev(d_desc), _dev(d_n), capacity,
+            _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), _dev(d_prev_matched), window, nnratio, int(check_orientation),
+            _dev(d_matches12), _dev(d_n_matches)))
 
     def project_last_frame_device(self, n_pairs, last, cur, d_kps, d_kps_un, d_n, capacity, d_mp_flags, d_world, d_poses, cam, bounds,
                                   mbf, mb, th, mono, d_queries):
         """Front half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (reference src/ORBmatcher.cc:1961-2023);
         last / cur = (first, step) of the last / current frame index of pair p."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        cam = np.ascontiguousarray(cam, np.float32); bounds = np.ascontiguousarray(bounds, np.float32)
-        self._check(self._L.orbx_project_last_frame_device(self._h, n_pairs, last[0], last[1], cur[0], cur[1], dp(d_kps), dp(d_kps_un), dp(d_n),
-                                                           capacity, dp(d_mp_flags), dp(d_world), dp(d_poses), _ptr(cam), _ptr(bounds),
-                                                           mbf, mb, th, int(mono), dp(d_queries)))
+        self._check(self._L.orbx_project_last_frame_device(self._h, n_pairs, last[0], last[1], cur[0], cur[1], _dev(d_kps), _dev(d_kps_un), _dev(d_n),
+                                                           capacity, _dev(d_mp_flags), _dev(d_world), _dev(d_poses), _host_f32(cam), _host_f32(bounds),
+                                                           mbf, mb, th, int(mono), _dev(d_queries)))
 
     def search_by_projection_device(self, n_pairs, cur, d_queries, d_query_desc, desc_blocks, d_n_queries, query_capacity, d_kps_un, d_desc,
                                     d_n, capacity, d_grid_off, d_grid_idx, bounds, d_u_right, d_occupied, ratio_mode, nnratio,
                                     check_orientation, d_matches, d_n_matches, max_distance=100):
         """ORBmatcher::SearchByProjection, the search (reference src/ORBmatcher.cc:2025-2175 / :44-135); cur and desc_blocks = (first, step)."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        bounds = np.ascontiguousarray(bounds, np.float32)
         self._check(self._L.orbx_search_by_projection_device(
-            self._h, n_pairs, cur[0], cur[1], dp(d_queries), dp(d_query_desc), desc_blocks[0], desc_blocks[1], dp(d_n_queries), query_capacity,
-            dp(d_kps_un), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), dp(d_u_right), dp(d_occupied),
-            int(ratio_mode), nnratio, max_distance, int(check_orientation), dp(d_matches), dp(d_n_matches)))
+            self._h, n_pairs, cur[0], cur[1], _dev(d_queries), _dev(d_query_desc), desc_blocks[0], desc_blocks[1], _dev(d_n_queries), query_capacity,
+            _dev(d_kps_un), _dev(d_desc), _dev(d_n), capacity, _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), _dev(d_u_right), _dev(d_occupied),
+            int(ratio_mode), nnratio, max_distance, int(check_orientation), _dev(d_matches), _dev(d_n_matches)))
 
     def search_by_projection_two_eyes_device(self, n_pairs, pairs, d_queries, d_query_desc, desc_blocks, d_n_queries, query_capacity, d_kps,
                                              d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, d_left_to_right, d_right_to_left,
@@ -563,84 +554,63 @@ class ORBextractor:
         """ORBmatcher::SearchByProjection(F, vpMapPoints, th, ...) for two-camera frames (reference src/ORBmatcher.cc:44-213, F.Nleft != -1);
         pairs = (first, step): pair q's left eye is frame 2*(first + q*step), its right eye the next frame; desc_blocks = (first, step).
         d_queries holds two requests per MapPoint (left, right); d_matches / d_occupied are [(2q + eye)*capacity + i]."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        bounds = np.ascontiguousarray(bounds, np.float32)
         self._check(self._L.orbx_search_by_projection_two_eyes_device(
-            self._h, n_pairs, pairs[0], pairs[1], dp(d_queries), dp(d_query_desc), desc_blocks[0], desc_blocks[1], dp(d_n_queries), query_capacity,
-            dp(d_kps), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), dp(d_left_to_right), dp(d_right_to_left),
-            dp(d_occupied), nnratio, max_distance, dp(d_matches), dp(d_n_matches)))
+            self._h, n_pairs, pairs[0], pairs[1], _dev(d_queries), _dev(d_query_desc), desc_blocks[0], desc_blocks[1], _dev(d_n_queries), query_capacity,
+            _dev(d_kps), _dev(d_desc), _dev(d_n), capacity, _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), _dev(d_left_to_right), _dev(d_right_to_left),
+            _dev(d_occupied), nnratio, max_distance, _dev(d_matches), _dev(d_n_matches)))
 
     def kb8_project_device(self, n, d_xyz, cam, d_uv):
         """KannalaBrandt8::project (reference src/CameraModels/KannalaBrandt8.cpp:28-44) over n device-resident points; cam = camera_kb8(...)."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        self._check(self._L.orbx_kb8_project_device(self._h, n, dp(d_xyz), None if cam is None else _ptr(np.ascontiguousarray(cam, np.float32)),
-                                                    dp(d_uv)))
+        self._check(self._L.orbx_kb8_project_device(self._h, n, _dev(d_xyz), _host_f32(cam), _dev(d_uv)))
 
     def project_last_frame_two_eyes_device(self, n_pairs, last, cur, d_kps, d_n, capacity, d_mp_flags, d_world, d_poses, trl, cam, bounds, mb, th,
                                            mono, d_queries):
         """Front half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for two-camera frames (reference
         src/ORBmatcher.cc:1971-2023, :2084-2101); last / cur = (first, step) of the last / current RIG frame of pair p (device frames 2r, 2r + 1);
         d_poses per rig frame; trl = mTrl (3x4); cam = camera_kb8(...).  d_queries: 2 * capacity requests per pair, two records (L, R) each."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        def hp(a):
-            return None if a is None else _ptr(np.ascontiguousarray(a, np.float32))
-        self._check(self._L.orbx_project_last_frame_two_eyes_device(self._h, n_pairs, last[0], last[1], cur[0], cur[1], dp(d_kps), dp(d_n), capacity,
-                                                                    dp(d_mp_flags), dp(d_world), dp(d_poses), hp(trl), hp(cam), hp(bounds), mb, th,
-                                                                    int(mono), dp(d_queries)))
+        self._check(self._L.orbx_project_last_frame_two_eyes_device(self._h, n_pairs, last[0], last[1], cur[0], cur[1], _dev(d_kps), _dev(d_n), capacity,
+                                                                    _dev(d_mp_flags), _dev(d_world), _dev(d_poses), _host_f32(trl), _host_f32(cam), _host_f32(bounds), mb, th,
+                                                                    int(mono), _dev(d_queries)))
 
     def search_last_frame_two_eyes_device(self, n_pairs, cur, d_queries, d_query_desc, d_kps, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds,
                                           d_occupied, check_orientation, d_matches, d_n_matches, max_distance=100):
         """ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) for two-camera frames, the search (reference
         src/ORBmatcher.cc:2013-2174); cur = (first, step) of the current RIG frame of pair q.  d_queries / d_query_desc: 2 * capacity requests
         per pair; d_matches / d_occupied are [(2q + eye)*capacity + i]."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
         self._check(self._L.orbx_search_last_frame_two_eyes_device(
-            self._h, n_pairs, cur[0], cur[1], dp(d_queries), dp(d_query_desc), dp(d_kps), dp(d_desc), dp(d_n), capacity, dp(d_grid_off),
-            dp(d_grid_idx), _ptr(bounds), dp(d_occupied), max_distance, int(check_orientation), dp(d_matches), dp(d_n_matches)))
+            self._h, n_pairs, cur[0], cur[1], _dev(d_queries), _dev(d_query_desc), _dev(d_kps), _dev(d_desc), _dev(d_n), capacity, _dev(d_grid_off),
+            _dev(d_grid_idx), _host_f32(bounds), _dev(d_occupied), max_distance, int(check_orientation), _dev(d_matches), _dev(d_n_matches)))
 
     def compute_bow_device(self, vocab, n_frames, d_desc, d_n, capacity, d_word_ids, d_word_weights, d_n_words, d_feat_nodes, d_feat_idx,
                            d_n_feat, levels_up=4):
         """Frame::ComputeBoW (reference src/Frame.cc:739-746) for n_frames device-resident frames."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self._L.orbx_compute_bow_device(self._h, vocab._v, n_frames, dp(d_desc), dp(d_n), capacity, levels_up, dp(d_word_ids),
-                                                    dp(d_word_weights), dp(d_n_words), dp(d_feat_nodes), dp(d_feat_idx), dp(d_n_feat)))
+        self._check(self._L.orbx_compute_bow_device(self._h, vocab._v, n_frames, _dev(d_desc), _dev(d_n), capacity, levels_up, _dev(d_word_ids),
+                                                    _dev(d_word_weights), _dev(d_n_words), _dev(d_feat_nodes), _dev(d_feat_idx), _dev(d_n_feat)))
 
     def search_by_bow_device(self, n_pairs, kf, cur, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, d_kps, d_desc, d_n, capacity,
                              d_matches, d_n_matches, nnratio=0.7, th_low=50, check_orientation=True):
         """ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (reference src/ORBmatcher.cc:269-471); kf and cur = (first, step)."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self._L.orbx_search_by_bow_device(self._h, n_pairs, kf[0], kf[1], cur[0], cur[1], dp(d_feat_nodes), dp(d_feat_idx),
-                                                      dp(d_n_feat), dp(d_kf_mp_flags), dp(d_kps), dp(d_desc), dp(d_n), capacity,
-                                                      C.c_float(nnratio), th_low, int(check_orientation), dp(d_matches), dp(d_n_matches)))
+        self._check(self._L.orbx_search_by_bow_device(self._h, n_pairs, kf[0], kf[1], cur[0], cur[1], _dev(d_feat_nodes), _dev(d_feat_idx),
+                                                      _dev(d_n_feat), _dev(d_kf_mp_flags), _dev(d_kps), _dev(d_desc), _dev(d_n), capacity,
+                                                      C.c_float(nnratio), th_low, int(check_orientation), _dev(d_matches), _dev(d_n_matches)))
 
     def search_by_bow_keyframes_device(self, n_pairs, kf1, kf2, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, d_kps, d_desc,
                                        d_n, capacity, d_matches12, d_n_matches, nnratio=0.8, th_low=50, check_orientation=True):
         """ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, ...) (reference src/ORBmatcher.cc:823-963); kf1 and kf2 = (first, step)."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self._L.orbx_search_by_bow_keyframes_device(self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], dp(d_feat_nodes), dp(d_feat_idx),
-                                                                dp(d_n_feat), dp(d_kf1_mp_flags), dp(d_kf2_mp_flags), dp(d_kps), dp(d_desc), dp(d_n),
-                                                                capacity, C.c_float(nnratio), th_low, int(check_orientation), dp(d_matches12),
-                                                                dp(d_n_matches)))
+        self._check(self._L.orbx_search_by_bow_keyframes_device(self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], _dev(d_feat_nodes), _dev(d_feat_idx),
+                                                                _dev(d_n_feat), _dev(d_kf1_mp_flags), _dev(d_kf2_mp_flags), _dev(d_kps), _dev(d_desc), _dev(d_n),
+                                                                capacity, C.c_float(nnratio), th_low, int(check_orientation), _dev(d_matches12),
+                                                                _dev(d_n_matches)))
 
     def search_by_bow_two_eyes_device(self, n_pairs, kf, cur, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, d_kps, d_desc, d_n, capacity,
                                       d_matches, d_n_matches, nnratio=0.7, th_low=50, check_orientation=True):
         """ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) for two-camera frames (reference src/ORBmatcher.cc:269-471, F.Nleft != -1); kf and
         cur = (first, step) in PAIRS: pair X is frame 2X (left eye) and 2X + 1 (right eye).  d_kf_mp_flags and d_matches are
         [(2p + eye)*capacity + i]; a match names the keyframe feature by its concatenated index (left: i, right: Nleft of the keyframe + j)."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        self._check(self._L.orbx_search_by_bow_two_eyes_device(self._h, n_pairs, kf[0], kf[1], cur[0], cur[1], dp(d_feat_nodes), dp(d_feat_idx),
-                                                               dp(d_n_feat), dp(d_kf_mp_flags), dp(d_kps), dp(d_desc), dp(d_n), capacity,
-                                                               C.c_float(nnratio), th_low, int(check_orientation), dp(d_matches),
-                                                               dp(d_n_matches)))
+        self._check(self._L.orbx_search_by_bow_two_eyes_device(self._h, n_pairs, kf[0], kf[1], cur[0], cur[1], _dev(d_feat_nodes), _dev(d_feat_idx),
+                                                               _dev(d_n_feat), _dev(d_kf_mp_flags), _dev(d_kps), _dev(d_desc), _dev(d_n), capacity,
+                                                               C.c_float(nnratio), th_low, int(check_orientation), _dev(d_matches),
+                                                               _dev(d_n_matches)))
 
     def search_for_triangulation_device(self, n_pairs, kf1, kf2, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, d_kps_un,
                                         d_u_right, d_desc, d_n, capacity, d_f12, d_epipole, d_matches12, d_pairs, d_n_matches,
@@ -649,12 +619,10 @@ class ORBextractor:
         model (reference src/ORBmatcher.cc:965-1206); kf1 and kf2 = (first, step), step 0 = one keyframe against many.  d_f12 [p*9] row-major
         and d_epipole [p*2] are inputs; d_u_right may be None (no feature is stereo).  d_matches12 is [p*capacity + i], d_pairs
         [(p*capacity + k)*2] holds d_n_matches[p] pairs (i, d_matches12[i]) in increasing i."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
         self._check(self._L.orbx_search_for_triangulation_device(
-            self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], dp(d_feat_nodes), dp(d_feat_idx), dp(d_n_feat), dp(d_kf1_mp_flags),
-            dp(d_kf2_mp_flags), dp(d_kps_un), dp(d_u_right), dp(d_desc), dp(d_n), capacity, dp(d_f12), dp(d_epipole), int(only_stereo),
-            int(coarse), th_low, int(check_orientation), dp(d_matches12), dp(d_pairs), dp(d_n_matches)))
+            self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], _dev(d_feat_nodes), _dev(d_feat_idx), _dev(d_n_feat), _dev(d_kf1_mp_flags),
+            _dev(d_kf2_mp_flags), _dev(d_kps_un), _dev(d_u_right), _dev(d_desc), _dev(d_n), capacity, _dev(d_f12), _dev(d_epipole), int(only_stereo),
+            int(coarse), th_low, int(check_orientation), _dev(d_matches12), _dev(d_pairs), _dev(d_n_matches)))
 
     def fuse_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags, d_poses, d_kps_un,
                     d_u_right, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, mbf, d_best_idx, d_best_dist, d_exit, d_n_fused,
@@ -662,15 +630,11 @@ class ORBextractor:
         """The search half of ORBmatcher::Fuse (reference src/ORBmatcher.cc:1399-1609; reproj_check=False: the Sim3 overload, :1611-1733) for
         one-camera keyframes with the Pinhole model; kf and mp = (first, step) of the keyframe / MapPoint list of pair p, mp step 0 = one list
         into many keyframes.  d_n_mp, d_u_right and d_exit may be None.  The caller replays the map-changing tail on the host in list order."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
-        cam = None if cam is None else np.ascontiguousarray(cam, np.float32)
         self._check(self._L.orbx_fuse_device(
-            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_n_mp), mp_capacity,
-            dp(d_mp_flags), dp(d_poses), dp(d_kps_un), dp(d_u_right), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds),
-            _ptr(cam), self.nlevels if nlevels is None else nlevels, mbf, th, th_low, int(reproj_check), dp(d_best_idx), dp(d_best_dist),
-            dp(d_exit), dp(d_n_fused)))
+            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], _dev(d_mp_world), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_mp_desc), _dev(d_n_mp), mp_capacity,
+            _dev(d_mp_flags), _dev(d_poses), _dev(d_kps_un), _dev(d_u_right), _dev(d_desc), _dev(d_n), capacity, _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds),
+            _host_f32(cam), self.nlevels if nlevels is None else nlevels, mbf, th, th_low, int(reproj_check), _dev(d_best_idx), _dev(d_best_dist),
+            _dev(d_exit), _dev(d_n_fused)))
 
     def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,
@@ -680,15 +644,11 @@ class ORBextractor:
         loop closing) for one-camera keyframes with the Pinhole model; kf and mp = (first, step) of the keyframe / MapPoint list of pair p,
         kf step 0 = several candidates into one keyframe.  d_poses is [p*12], per pair.  d_n_mp, d_occupied and d_exit may be None.  A match
         closes its keypoint for the later MapPoints of the list, as in the reference; d_matches [p*capacity + idx] names the list index."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
-        cam = None if cam is None else np.ascontiguousarray(cam, np.float32)
         self._check(self._L.orbx_search_by_projection_sim3_device(
-            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_n_mp), mp_capacity,
-            dp(d_mp_flags), dp(d_poses), dp(d_kps_un), dp(d_desc), dp(d_n), capacity, dp(d_grid_off), dp(d_grid_idx), _ptr(bounds), _ptr(cam),
-            self.nlevels if nlevels is None else nlevels, int(projection), th, th_low, ratio_hamming, dp(d_occupied), dp(d_matches),
-            dp(d_match_idx), dp(d_match_dist), dp(d_exit), dp(d_n_matches)))
+            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], _dev(d_mp_world), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_mp_desc), _dev(d_n_mp), mp_capacity,
+            _dev(d_mp_flags), _dev(d_poses), _dev(d_kps_un), _dev(d_desc), _dev(d_n), capacity, _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), _host_f32(cam),
+            self.nlevels if nlevels is None else nlevels, int(projection), th, th_low, ratio_hamming, _dev(d_occupied), _dev(d_matches),
+            _dev(d_match_idx), _dev(d_match_dist), _dev(d_exit), _dev(d_n_matches)))
 
     def frustum_requests_device(self, n_pairs, cur, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_mp_angle, d_n_mp, mp_capacity, d_mp_flags,
                                 d_poses, cam, bounds, d_queries, d_query_desc, d_query_src, d_n_queries, d_track, d_n_in_view,
@@ -700,15 +660,11 @@ class ORBextractor:
         d_query_src, d_n_queries: feed them to search_by_projection_device with query_capacity = mp_capacity and desc_blocks = (0, 1)), one
         TRACK_RECORD_DTYPE per list entry and nToMatch per pair.  d_n_mp may be None; d_mp_angle in the local-map mode and d_mp_normal in
         the relocalisation mode as well."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        bounds = None if bounds is None else np.ascontiguousarray(bounds, np.float32)
-        cam = None if cam is None else np.ascontiguousarray(cam, np.float32)
         self._check(self._L.orbx_frustum_requests_device(
-            self._h, n_pairs, cur[0], cur[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_mp_angle), dp(d_n_mp),
-            mp_capacity, dp(d_mp_flags), dp(d_poses), _ptr(cam), _ptr(bounds), self.nlevels if nlevels is None else nlevels, int(mode), mbf,
-            view_cos_limit, th, int(bool(far_points)), th_far_points, dp(d_queries), dp(d_query_desc), dp(d_query_src), dp(d_n_queries),
-            dp(d_track), dp(d_n_in_view)))
+            self._h, n_pairs, cur[0], cur[1], mp[0], mp[1], _dev(d_mp_world), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_mp_desc), _dev(d_mp_angle), _dev(d_n_mp),
+            mp_capacity, _dev(d_mp_flags), _dev(d_poses), _host_f32(cam), _host_f32(bounds), self.nlevels if nlevels is None else nlevels, int(mode), mbf,
+            view_cos_limit, th, int(bool(far_points)), th_far_points, _dev(d_queries), _dev(d_query_desc), _dev(d_query_src), _dev(d_n_queries),
+            _dev(d_track), _dev(d_n_in_view)))
 
     def frustum_requests_two_eyes_device(self, n_pairs, cur, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_mp_prev_depth, d_poses, trl, tlr, cam_left, cam_right, bounds, query_capacity, d_queries, d_query_desc,
@@ -722,15 +678,11 @@ class ORBextractor:
         d_queries, d_query_desc, d_query_src, d_n_queries: feed them to search_by_projection_two_eyes_device with the same query_capacity
         and desc_blocks = (0, 1)), the count the list produced (d_n_wanted) and nToMatch per pair.  d_n_mp, d_mp_prev_depth and d_n_wanted
         may be None."""
-        def dp(x):
-            return C.c_void_p(0 if x is None else (x.data_ptr() if hasattr(x, "data_ptr") else int(x)))
-        def hp(a):
-            return None if a is None else _ptr(np.ascontiguousarray(a, np.float32))
         self._check(self._L.orbx_frustum_requests_two_eyes_device(
-            self._h, n_pairs, cur[0], cur[1], mp[0], mp[1], dp(d_mp_world), dp(d_mp_normal), dp(d_mp_dist), dp(d_mp_desc), dp(d_n_mp), mp_capacity,
-            dp(d_mp_flags), dp(d_mp_prev_depth), dp(d_poses), hp(trl), hp(tlr), hp(cam_left), hp(cam_right), hp(bounds),
-            self.nlevels if nlevels is None else nlevels, view_cos_limit, th, int(bool(far_points)), th_far_points, query_capacity, dp(d_queries),
-            dp(d_query_desc), dp(d_query_src), dp(d_n_queries), dp(d_n_wanted), dp(d_track), dp(d_n_in_view)))
+            self._h, n_pairs, cur[0], cur[1], mp[0], mp[1], _dev(d_mp_world), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_mp_desc), _dev(d_n_mp), mp_capacity,
+            _dev(d_mp_flags), _dev(d_mp_prev_depth), _dev(d_poses), _host_f32(trl), _host_f32(tlr), _host_f32(cam_left), _host_f32(cam_right), _host_f32(bounds),
+            self.nlevels if nlevels is None else nlevels, view_cos_limit, th, int(bool(far_points)), th_far_points, query_capacity, _dev(d_queries),
+            _dev(d_query_desc), _dev(d_query_src), _dev(d_n_queries), _dev(d_n_wanted), _dev(d_track), _dev(d_n_in_view)))
 
     def debug_sim3_search_stats(self):
         """(rounds of pair 0, requests settled by a re-scan, 100-MHz ticks of pair 0's settling workgroup, 0) of the last Sim3 search"""
@@ -741,26 +693,22 @@ class ORBextractor:
     def stereo_from_rgbd_device(self, n_frames, d_kps, d_kps_un, d_n, capacity, d_depth, depth_is_u16, rows, cols, depth_map_factor, mbf,
                                 d_u_right, d_depth_out, depth_stride_bytes=None, depth_frame_stride_bytes=None):
         """Frame::ComputeStereoFromRGBD with GrabImageRGBD's depth conversion (reference src/Frame.cc:994-1015, src/Tracking.cc:1003-1004)."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
         elem = 2 if depth_is_u16 else 4
         depth_stride_bytes = cols * elem if depth_stride_bytes is None else depth_stride_bytes
         depth_frame_stride_bytes = rows * depth_stride_bytes if depth_frame_stride_bytes is None else depth_frame_stride_bytes
-        self._check(self._L.orbx_stereo_from_rgbd_device(self._h, n_frames, dp(d_kps), dp(d_kps_un), dp(d_n), capacity, dp(d_depth),
+        self._check(self._L.orbx_stereo_from_rgbd_device(self._h, n_frames, _dev(d_kps), _dev(d_kps_un), _dev(d_n), capacity, _dev(d_depth),
                                                          int(depth_is_u16), rows, cols, depth_stride_bytes, depth_frame_stride_bytes,
-                                                         depth_map_factor, mbf, dp(d_u_right), dp(d_depth_out)))
+                                                         depth_map_factor, mbf, _dev(d_u_right), _dev(d_depth_out)))
 
     def gray_from_color_device(self, n_frames, d_src, rows, cols, channels, red_first, d_gray, src_stride=None, src_frame_stride=None,
                                gray_stride=None, gray_frame_stride=None):
         """cv::cvtColor(RGB/BGR/RGBA/BGRA -> GRAY) as Tracking::GrabImage* applies it (reference src/Tracking.cc:915-941)."""
-        def dp(x):
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
         src_stride = cols * channels if src_stride is None else src_stride
         src_frame_stride = rows * src_stride if src_frame_stride is None else src_frame_stride
         gray_stride = cols if gray_stride is None else gray_stride
         gray_frame_stride = rows * gray_stride if gray_frame_stride is None else gray_frame_stride
-        self._check(self._L.orbx_gray_from_color_device(self._h, n_frames, dp(d_src), rows, cols, channels, int(red_first), src_stride,
-                                                        src_frame_stride, dp(d_gray), gray_stride, gray_frame_stride))
+        self._check(self._L.orbx_gray_from_color_device(self._h, n_frames, _dev(d_src), rows, cols, channels, int(red_first), src_stride,
+                                                        src_frame_stride, _dev(d_gray), gray_stride, gray_frame_stride))
 
     def set_stream(self, stream_ptr):
         self._check(self._L.orbx_set_stream(self._h, C.c_void_p(int(stream_ptr))))
@@ -810,10 +758,7 @@ class ORBextractor:
         cap = self.capacity
         lvl = np.zeros(cap, KEYPOINT_DTYPE); counts = np.zeros(self.nlevels, np.int32)
         self._check(self._L.orbx_compute_keypoints_octree(self._h, _ptr(lvl), cap, _ptr(counts)))
-        per_level, o = [], 0
-        for c in counts.tolist():
-            per_level.append(lvl[o:o + c].copy()); o += c
-        return per_level
+        return _split_levels(lvl, counts)
 
     def policy(self):
         """The launch-policy switches as orbx_create read them (include/orbx.h: orbx_debug_policy)."""

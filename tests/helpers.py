@@ -22,6 +22,15 @@ def load_case(case):
 GOLDEN_CASES = ["luna_1000", "luna_1000_lap00", "luna_7500", "robot_865_1000", "robot_865_1200_lap", "tum_corridor_1000", "tum_room4_1500"]
 
 
+def entry_lds_budget():
+    """kLdsBudget where the entry points take it from (extractorb_amd/csrc/orbx_entry.hpp); the tests that spell the documented bound
+    themselves check that the two statements agree"""
+    import re
+    text = open(os.path.join(ROOT, "extractorb_amd", "csrc", "orbx_entry.hpp")).read()
+    a, b, c = re.search(r"constexpr size_t kLdsBudget = (\d+) \* (\d+) - (\d+);", text).groups()
+    return int(a) * int(b) - int(c)
+
+
 def sort_kps(k):
     return k[np.lexsort((k["x"], k["y"]))]
 

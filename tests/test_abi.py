@@ -50,7 +50,7 @@ def test_no_test_hook_is_reachable_from_the_environment():
     for name in X.orbextractor.TEST_AIDS:
         assert L.orbx_debug_set_option(name.encode(), 1) == 0
     X.debug_reset_options()
-    api = "".join(open(os.path.join(ROOT, "extractorb_amd", "csrc", f)).read() for f in ("orbx_api.cpp", "orbx_rows.cpp", "orbx_debug.cpp", "orbx_internal.hpp"))
+    api = "".join(open(os.path.join(ROOT, "extractorb_amd", "csrc", f)).read() for f in ("orbx_api.cpp", "orbx_rows.cpp", "orbx_debug.cpp", "orbx_internal.hpp", "orbx_entry.hpp"))
     import re
     read = set(re.findall(r'getenv\("(ORBX_[A-Z0-9_]+)"\)', api)) | set(re.findall(r'envInt\("(ORBX_[A-Z0-9_]+)"', api))
     assert read and not [n for n in read if "TEST" in n or "POISON" in n or "POLLUTE" in n], read
@@ -61,7 +61,7 @@ def test_handle_owned_memory_is_only_touched_in_stream_order():
     hipMemcpy2DAsync on the handle's stream, or the vocabulary's own upload stream) - no null-stream hipMemcpy / hipMemset whose order against
     the handle's non-blocking stream would be an assumption, and no device-wide barrier that stalls other handles."""
     import re
-    api = "".join(open(os.path.join(ROOT, "extractorb_amd", "csrc", f)).read() for f in ("orbx_api.cpp", "orbx_rows.cpp", "orbx_debug.cpp", "orbx_internal.hpp"))
+    api = "".join(open(os.path.join(ROOT, "extractorb_amd", "csrc", f)).read() for f in ("orbx_api.cpp", "orbx_rows.cpp", "orbx_debug.cpp", "orbx_internal.hpp", "orbx_entry.hpp"))
     code = re.sub(r"//[^\n]*", "", api)
     assert not re.findall(r"\bhipMem(?:cpy|set|cpy2D|setD8|setD32)\s*\(", code)
     assert "hipDeviceSynchronize" not in code
@@ -71,6 +71,63 @@ def test_handle_owned_memory_is_only_touched_in_stream_order():
         text = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "extractorb_amd", "csrc", f)).read())
         text = re.sub(r"#if defined\(ORBX_FAST_CLOCK\).*?#else", "", text, flags=re.S)      # (the stamped diagnostic build of k_fast: tools/fast_clock.py)
         assert "hipMemcpyToSymbol" not in text and not re.findall(r"\bhipMem(?:cpy|set)\s*\(", text), f
+
+
+NO_ARGTYPES = {"orbx_abi_version", "orbx_debug_search_rounds", "orbx_debug_host_timing"}      # called with ctypes' defaults (no or one pointer argument)
+
+
+def _header_parameter_classes():
+    """{function: [class of every parameter]} of include/orbx.h; a class is what ctypes has to be told: p(ointer), f(loat), d(ouble),
+    ptrdiff, size or i(nt)"""
+    import re
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "orbx.h")).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for name, params in re.findall(r"\b(orbx_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        classes = []
+        for prm in [q.strip() for q in params.split(",")]:
+            if prm in ("void", ""):
+                continue
+            kind = re.sub(r"\b(const|struct|unsigned|signed)\b", "", prm)
+            if "*" in kind or "[" in kind:
+                classes.append("p")
+                continue
+            base = kind.split()[0]
+            classes.append({"float": "f", "double": "d", "ptrdiff_t": "ptrdiff", "size_t": "size"}.get(base, "i"))
+            assert base in ("float", "double", "ptrdiff_t", "size_t", "int", "long"), (name, prm)
+        out[name] = classes
+    return out
+
+
+def _ctypes_class(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "p"
+    return {ctypes.c_float: "f", ctypes.c_double: "d", ctypes.c_ssize_t: "ptrdiff", ctypes.c_size_t: "size"}.get(t, "i" if t in (ctypes.c_int, ctypes.c_long) else "?")
+
+
+def test_argtypes_match_the_header():
+    """The argtypes of load_library() are written by hand, one list per function: every list is compared, class by class, with the parameter
+    list include/orbx.h declares.  A miscounted pointer or an int where the header has a float shows here, not as a corrupted call."""
+    L = X.load_library()
+    declared = _header_parameter_classes()
+    assert set(declared) == set(X.header_symbols()) and len(declared) >= 75
+    without, wrong = set(), {}
+    for name, classes in declared.items():
+        argtypes = getattr(L, name).argtypes
+        if argtypes is None:
+            without.add(name)
+            continue
+        mine = [_ctypes_class(t) for t in argtypes]
+        # ctypes has one 64-bit signed and one unsigned integer type here: ptrdiff_t is c_ssize_t, size_t is c_size_t
+        if mine != classes:
+            wrong[name] = (classes, mine)
+    assert not wrong, wrong
+    assert without == NO_ARGTYPES, without ^ NO_ARGTYPES
+    # the classifier itself, on worked examples
+    assert declared["orbx_kb8_project_device"] == ["p", "i", "p", "p", "p"]
+    assert declared["orbx_sim3_hamming_bound"] == ["i", "f"]
+    assert declared["orbx_host_alloc"] == ["size"] and declared["orbx_abi_version"] == []
+    assert declared["orbx_gray_from_color_device"] == ["p", "i", "p", "i", "i", "i", "i", "ptrdiff", "ptrdiff", "p", "ptrdiff", "ptrdiff"]
 
 
 def test_keypoint_layout():

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import extractorb_amd as X
+import helpers
 import last_frame_two_eyes_scenes as S
 import last_frame_two_eyes_walk as W
 import oracle_lib as O
@@ -263,6 +264,7 @@ def test_entries_are_declared_documented_exported_and_check_their_arguments():
     assert L.orbx_search_last_frame_two_eyes_device(None, 1, 0, 1, z, z, z, z, z, 16, z, z, b, None, 100, 1, z, z) == -2
     assert L.orbx_debug_last_frame_two_eyes_stats(None) == -2
     assert np.array_equal(X.camera_kb8(1, 2, 3, 4, 5, 6, 7, 8), np.arange(1, 9, dtype=f32))
+    assert LDS_LIMIT == helpers.entry_lds_budget()
     assert max(c for c in range(1, 3000) if lds_bytes(c) <= LDS_LIMIT) >= CAP_1200          # the required envelope
 
 

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import helpers
 import oracle_lib as O
 import extractorb_amd as X
 import two_eyes_bow_walk as W
@@ -490,7 +491,7 @@ def test_gpu_capacity_bound_both_sides():
     import torch
     ex = X.ORBextractor(1000)
     cap = max(c for c in range(1, 8000) if lds_bytes(c) <= LDS_LIMIT)
-    assert lds_bytes(cap + 1) > LDS_LIMIT and cap >= CAP_1200
+    assert lds_bytes(cap + 1) > LDS_LIMIT and cap >= CAP_1200 and LDS_LIMIT == helpers.entry_lds_budget()
     s = make(CAPACITY_CASE)
     m, nm = run_searches(ex, [s], cap)                  # the largest accepted capacity runs
     assert_equals_walk(s, m[0], nm[0])

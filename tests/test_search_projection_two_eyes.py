@@ -8,6 +8,7 @@ import functools
 import numpy as np
 import pytest
 
+import helpers
 import oracle_lib as O
 import extractorb_amd as X
 import two_eyes_walk as W
@@ -428,6 +429,7 @@ def test_gpu_forced_walk_equals_the_fixed_point_and_the_walk():
 def test_gpu_size_bound_both_sides():
     import torch
     limit = 160 * 1024 - 512
+    assert limit == helpers.entry_lds_budget()
     rng = np.random.default_rng(51)
     ex = X.ORBextractor(1000)
     s = random_scene(rng, nl=500, nr=450, nq=600)

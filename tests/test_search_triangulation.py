@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import helpers
 import extractorb_amd as X
 from extractorb_amd import synth
 from test_bow import make_vocab
@@ -283,6 +284,7 @@ def test_python_method_exists():
 def test_lds_formula_admits_the_capacities_of_the_usual_extractors():
     # orbx_max_keypoints() = sum over the levels of max(quota + 3, 4 * nIni) + 8 * nlevels: about nfeatures + 100 at 640 x 480 (1302 for 1200
     # features); what the handles of 1000-, 1200- and 2000-feature extractors report is asserted against the formula on the GPU
+    assert LDS_LIMIT == helpers.entry_lds_budget()
     for cap in (1024, 1100, CAP_1200, 2024, 2200, 4080):
         assert lds_bytes(cap) <= LDS_LIMIT
     for cap in (1024, 1100, CAP_1200, 2024, 2200):

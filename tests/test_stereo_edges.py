@@ -13,6 +13,7 @@ import re
 import numpy as np
 import pytest
 
+import helpers
 import oracle_lib as O
 import extractorb_amd as X
 import stereo_statement as S
@@ -413,7 +414,7 @@ def test_lds_bound_follows_the_kernel_table_and_the_header_documents_it():
     table = json.load(open(os.path.join(os.path.dirname(X.orbextractor.__file__), "csrc", "kernel_table.json")))
     assert header_static_lds() >= table["k_stereo_filter"]["lds_static_bytes"]
     largest = max(c for c in range(1, 65536) if filter_lds_bytes(c) <= LDS_LIMIT)
-    assert largest == 40568 and filter_lds_bytes(largest + 1) > LDS_LIMIT
+    assert largest == 40568 and filter_lds_bytes(largest + 1) > LDS_LIMIT and LDS_LIMIT == helpers.entry_lds_budget()
     text = open(X.orbextractor._HEADER).read()
     pos = text.index("int orbx_stereo_match_device(")
     doc = text[text.rindex("/*", 0, pos):pos]
