@@ -8,14 +8,14 @@ There is no CPU fallback: importing works anywhere (so the C ABI can be inspecte
 extractor without the built library or without a HIP device raises.
 """
 from .orbextractor import (KEYPOINT_DTYPE, ORBextractor, OrbxError, build_library, library_path, load_library,
-                           compute_tables, compute_level_sizes, compute_cell_grid, header_symbols, camera, camera_kb8,
+                           compute_tables, describe_tables, compute_level_sizes, compute_cell_grid, header_symbols, camera, camera_kb8,
                            compute_image_bounds, pinned_empty, pinned_free, source_hash, Vocabulary, debug_set_option,
                            debug_reset_options, predict_scale, predict_scale_breakpoints, sim3_hamming_bound, PROJ_QUERY_DTYPE,
                            TRACK_RECORD_DTYPE, FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION, FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH,
                            FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR, FRUSTUM_REQUEST)
 
 __all__ = ["KEYPOINT_DTYPE", "ORBextractor", "OrbxError", "build_library", "library_path", "load_library",
-           "compute_tables", "compute_level_sizes", "compute_cell_grid", "header_symbols", "camera", "camera_kb8", "compute_image_bounds", "pinned_empty", "pinned_free", "source_hash", "Vocabulary",
+           "compute_tables", "describe_tables", "compute_level_sizes", "compute_cell_grid", "header_symbols", "camera", "camera_kb8", "compute_image_bounds", "pinned_empty", "pinned_free", "source_hash", "Vocabulary",
            "debug_set_option", "debug_reset_options", "predict_scale", "predict_scale_breakpoints", "sim3_hamming_bound",
            "PROJ_QUERY_DTYPE", "TRACK_RECORD_DTYPE", "FRUSTUM_LOCAL_MAP", "FRUSTUM_RELOCALIZATION", "FRUSTUM_FLAG", "FRUSTUM_NEG_DEPTH",
            "FRUSTUM_NOT_IN_IMAGE", "FRUSTUM_DISTANCE", "FRUSTUM_VIEW_COS", "FRUSTUM_FAR", "FRUSTUM_REQUEST"]

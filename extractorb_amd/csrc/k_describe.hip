@@ -2,6 +2,7 @@
 // (reference ORBextractor.cc:75-145, 1137-1158).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "orbx_device.hpp"
 #define ORBX_DESCRIBE_TU 1
@@ -48,6 +49,10 @@ void launchDescribe(hipStream_t st, const LevelGeom* lv, int nlevels, const uint
 bool checkUmax(const int* umax16) {      // the static device table is the one the reference's constructor computes
     for (int i = 0; i < 16; i++) if (umax16[i] != kUmaxStatic[i]) return false;
     return true;
+}
+void describeTables(unsigned* pb384, unsigned* plain256) {      // the arrays the __constant__ weight words are initialised from
+    memcpy(pb384, &kWeightsPb, sizeof(kWeightsPb));
+    memcpy(plain256, &kWeightsPlain, sizeof(kWeightsPlain));
 }
 
 

@@ -11,11 +11,32 @@ namespace orbx {
 // ================================================================================================
 // IC_Angle + rotated BRIEF + final placement.  One wave64 per kept keypoint.
 // ================================================================================================
-// Both tables are the same for every extractor (HALF_PATCH_SIZE = 15 and the learned pattern are compile-time constants of the reference,
+// The tables below are the same for every extractor (HALF_PATCH_SIZE = 15 and the learned pattern are compile-time constants of the reference,
 // ORBextractor.cc:71, 148-406), so they are initialised statically: no upload, nothing for a second handle's creation to overwrite while a
-// first handle's kernels read them.  checkUmax compares the static c_umax with the table the host derives by the reference's formula (:459-474).
+// first handle's kernels read them.  checkUmax compares kUmaxStatic with the table the host derives by the reference's formula (:459-474).
 constexpr int kUmaxStatic[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-static __constant__ int c_umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
+constexpr int kBriefReach = 18;                       // |rounded rotated pattern coordinate| <= 18 (max radius 18.385)
+// IC_Angle's weight words: row |v| = a of the disc as the dwords of a staged tile row, byte b of dword j <-> u = 4 j + b - U0; plane 0 holds u + 16
+// inside the disc (|u| <= umax[a]; sum(u I) = dot(I, u + 16) - 16 dot(I, 1)), plane 1 holds 1 there, both 0 outside.  A function of kUmaxStatic and
+// the tile layout alone, so it is evaluated by the compiler: ONE constexpr array initialises the __constant__ copy a workgroup fills its LDS table
+// from and is what the host exports (describeTables; tests/test_describe_tables.py restates it from the reference's formula).
+template <int W> struct WeightWords { unsigned w[2][16][W]; };
+template <int W, int U0>
+constexpr WeightWords<W> makeWeightWords() {
+    WeightWords<W> t{};
+    for (int which = 0; which < 2; which++)
+        for (int a = 0; a < 16; a++)
+            for (int j = 0; j < W; j++)
+                for (int b = 0; b < 4; b++) {
+                    const int u = 4 * j + b - U0, au = u < 0 ? -u : u;
+                    if (au <= kHalfPatch && au <= kUmaxStatic[a]) t.w[which][a][j] |= (unsigned)(which ? 1 : u + 16) << (8 * b);
+                }
+    return t;
+}
+constexpr WeightWords<12> kWeightsPb = makeWeightWords<12, kBriefReach + 4>();      // the re-aligned 44-byte tile row of the patch-blur form: u = t - 22
+constexpr WeightWords<8> kWeightsPlain = makeWeightWords<8, kHalfPatch>();          // the 32 bytes from the patch's first column on: u = k - 15
+static __constant__ WeightWords<12> c_weightsPb = kWeightsPb;
+static __constant__ WeightWords<8> c_weightsPlain = kWeightsPlain;
 static __constant__ __attribute__((aligned(16))) float c_patternF[1024] = {   // the rBRIEF pattern as floats
 #include "orbx_brief_pattern.inc"
 };
@@ -83,7 +104,6 @@ __device__ __forceinline__ void sincosGlibc(float y, float* s_out, float* c_out)
 }
 
 constexpr int kDescWaves = 4;                         // waves per workgroup; each half-wave (32 lanes) owns one keypoint
-constexpr int kBriefReach = 18;                       // |rounded rotated pattern coordinate| <= 18 (max radius 18.385)
 constexpr int kRawRows = 2 * kHalfPatch + 1;          // 31
 constexpr int kRawStride = 40;                        // 3 + 31 bytes -> 9 dwords, staged as five 8-byte pairs
 constexpr int kBlurRows = 2 * kBriefReach + 1;        // 37
@@ -194,7 +214,7 @@ struct DescLds {
 };
 
 // One workgroup = eight keypoint slots [8 chunk, 8 chunk + 8) of frame f.  smem: the patches (DescLds::kPatches bytes), wtab: the weight words.
-// One workgroup barrier (behind the weight table).  A wave whose level lies outside [levelLo, levelHi) belongs to another launch and leaves.
+// One workgroup barrier (behind the weight table, a copy of the static one).  A wave whose level lies outside [levelLo, levelHi) belongs to another launch and leaves.
 template <bool PB>
 __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, int nlevels,
                                               const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ blur,
@@ -206,28 +226,13 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
                                               uint8_t* smem, unsigned (*wtab)[16][PB ? 12 : 8], int chunk, int f, int levelLo, int levelHi) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, hl = lane & 31;
     DSTAMP(0);
-    if constexpr (PB) {   // weight words of row |v| = a over the re-aligned tile row: byte t = 4 j + b <-> u = t - 22
-        for (int e = tid; e < 2 * 16 * 12; e += 256) {
-            const int which = e / 192, a = (e / 12) & 15, j = e % 12;
-            unsigned w = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int u = 4 * j + b - (kBriefReach + 4), au = u < 0 ? -u : u;
-                if (au <= kHalfPatch && au <= c_umax[a]) w |= (unsigned)(which ? 1 : u + 16) << (8 * b);
-            }
-            wtab[which][a][j] = w;
-        }
-    } else {   // weight words of row |v| = a, bytes k = 0..31 <-> u = k - 15
-        const int which = tid >> 7, a = (tid >> 3) & 15, j = tid & 7;
-        unsigned w = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int u = 4 * j + b - kHalfPatch, au = u < 0 ? -u : u;
-            if (au <= c_umax[a]) w |= (unsigned)(which ? 1 : u + 16) << (8 * b);
-        }
-        wtab[which][a][j] = w;
-    }
-    __syncthreads();
+    // the weight words: requested here, stored to LDS behind the level sums (nothing before the barrier needs them)
+    constexpr int kWords = DescLds<PB>::kWtabWords;      // 384 (PB) / 256
+    const unsigned* wsrc;
+    if constexpr (PB) wsrc = &c_weightsPb.w[0][0][0]; else wsrc = &c_weightsPlain.w[0][0][0];
+    const unsigned wA = wsrc[tid];
+    unsigned wB = 0;
+    if (kWords > 256 && tid < kWords - 256) wB = wsrc[256 + tid];
     const int slot0 = __builtin_amdgcn_readfirstlane((chunk * kDescWaves + wave) * 2);   // wave-uniform
     const int slot = slot0 + half;
     // totals of this frame and the level this wave belongs to.  Two forms, by the launch (wave-uniform):
@@ -263,15 +268,19 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
         if (slot0 == 0 && outLevelCounts && lane < nlevels) outLevelCounts[f * nlevels + lane] = levelCount[f * nlevels + lane];
     }
     if (slot0 == 0 && lane == 0) { nOut[f] = total; monoOut[f] = total - totalLap; }      // monoIndex after the loop (:1161)
-    if (level < levelLo || level >= levelHi) return;      // (wave-uniform: the other launch of a blur split by level describes this level)
+    const bool mine = level >= levelLo && level < levelHi;      // (wave-uniform: the other launch of a blur split by level describes the other levels)
     const int i = slot - selOff;
-    const bool active = slot < selPerFrame && i < levelN;
+    const bool active = mine && slot < selPerFrame && i < levelN;
+    (&wtab[0][0][0])[tid] = wA;      // (requested in front of the level sums: here by now)
+    if (kWords > 256 && tid < kWords - 256) (&wtab[0][0][0])[256 + tid] = wB;
+    const uint2 e = active ? sel[(long long)f * selPerFrame + slot] : make_uint2(0u, 0u);      // (in flight across the barrier)
+    __syncthreads();
+    if (!mine) return;
     if (__ballot(active) == 0) return;
     DSTAMP(1);
     const int gw = lv[level].w, gh = lv[level].h, pyrStride = lv[level].pyrStride, blurStride = lv[level].blurStride;
     const uint8_t* pyrL = pyr + lv[level].pyrOff + (long long)f * lv[level].pyrFrameBytes;      // wave-uniform bases:
     const uint8_t* blurL = blur + lv[level].blurOff + (long long)f * lv[level].blurFrameBytes;   // lanes add 32-bit offsets
-    const uint2 e = active ? sel[(long long)f * selPerFrame + slot] : make_uint2(0u, 0u);
     int kx = e.x & 0xffff, ky = e.x >> 16;      // (orbx_device.hpp: the selection entry)
     const float response = (float)(e.y >> 24);
     // the quad-tree only emits points of the FAST rectangle; clamp anyway so a corrupted entry (or an idle half)

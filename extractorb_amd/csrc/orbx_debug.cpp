@@ -26,6 +26,13 @@ int orbx_debug_set_option(const char* name, int value) {
     return ORBX_OK;
 }
 
+// IC_Angle's static weight words as the host holds them (k_describe_body.hpp); needs no device
+int orbx_debug_describe_tables(unsigned* pb384, unsigned* plain256) {
+    if (!pb384 || !plain256) return ORBX_ERR_BAD_ARGUMENT;
+    describeTables(pb384, plain256);
+    return ORBX_OK;
+}
+
 const char* orbx_debug_policy(const orbx_handle* h) { return h ? h->policy.c_str() : ""; }
 
 // The shader clock while the handle's work is running: one sleeping wave per CU on a stream of its own (k_clock.hip), asynchronous.

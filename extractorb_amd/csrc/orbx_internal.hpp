@@ -50,6 +50,7 @@ void launchOctree(hipStream_t, const LevelGeom*, int, const CellDesc*, int, cons
 void launchDescribe(hipStream_t, const LevelGeom*, int, const uint8_t*, const uint8_t*, const uint2*, int, const int*,
                     const int*, Keypoint*, uint8_t*, int, int*, int*, Keypoint*, int*, bool, int, int, int, int, int, int);
 bool checkUmax(const int* umax16);
+void describeTables(unsigned* pb384, unsigned* plain256);
 hipError_t runPackedSelfTest(hipStream_t, unsigned*, unsigned*);
 void launchFrameFinish(hipStream_t, const Keypoint*, const int*, const FrameFinishParams&, Keypoint*, int*, int*, int*, int);
 void launchStereo(hipStream_t, const LevelGeom*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const StereoParams&,

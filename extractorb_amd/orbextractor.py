@@ -144,6 +144,8 @@ def load_library():
     L.orbx_debug_last_forms.argtypes = [vp, ip, ip, ip]
     L.orbx_debug_last_split_level.argtypes = [vp]
     L.orbx_debug_set_option.argtypes = [C.c_char_p, C.c_int]
+    if hasattr(L, "orbx_debug_describe_tables"):      # (an earlier build loaded through ORBX_LIBRARY for an A/B has no such export)
+        L.orbx_debug_describe_tables.argtypes = [vp, vp]
     L.orbx_debug_clock_probe.argtypes = [vp, C.c_int]
     L.orbx_debug_clock_read.argtypes = [vp, C.c_int, vp]
     L.orbx_debug_policy.restype = C.c_char_p
@@ -282,6 +284,15 @@ def debug_reset_options():
 
 
 # ---- handle-free host helpers (no GPU needed) -------------------------------------------------------------
+def describe_tables():
+    """IC_Angle's static weight words (include/orbx.h: orbx_debug_describe_tables): uint32 [2, 16, 12] (patch-blur form) and [2, 16, 8]"""
+    pb = np.zeros((2, 16, 12), np.uint32); plain = np.zeros((2, 16, 8), np.uint32)
+    rc = load_library().orbx_debug_describe_tables(_ptr(pb), _ptr(plain))
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_debug_describe_tables")
+    return pb, plain
+
+
 def compute_tables(nfeatures=1000, scale_factor=1.2, nlevels=8):
     L = load_library()
     sf = np.zeros(nlevels, np.float32); isf = sf.copy(); s2 = sf.copy(); is2 = sf.copy()

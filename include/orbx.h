@@ -884,6 +884,12 @@ int orbx_debug_last_split_level(const orbx_handle* h);
  * BoW search reads the frame pair's descriptors from L2 whatever the capacity; -1 = staged in LDS where they fit).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
 int orbx_debug_set_option(const char* name, int value);
 
+/* IC_Angle's weight words, the static tables the description kernels fill their LDS copy from: pb384 = [2][16][12] words over the 44-byte tile
+ * row of the patch-blur form (byte t <-> u = t - 22), plain256 = [2][16][8] words over the 32 bytes from the patch's first column on (byte k <->
+ * u = k - 15); plane 0 holds u + 16 inside the disc's row (|u| <= umax[|v|], |u| <= 15), plane 1 holds 1 there, both 0 outside.  The host's copy
+ * of the array the device's is initialised from: needs no device. */
+int orbx_debug_describe_tables(unsigned* pb384, unsigned* plain256);
+
 /* The launch-policy switches as orbx_create read them, "NAME=value" separated by blanks, "(env)" behind a value that came from an ORBX_<NAME>
  * environment variable (read once, at orbx_create; they choose between result-identical launch forms), and the test aids in force, if any.
  * bench.py prints it as config.policy. */
