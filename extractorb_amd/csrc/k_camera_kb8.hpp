@@ -3,8 +3,8 @@
 // routines of glibc 2.35 evaluate them, sinf / cosf as k_describe_body.hpp's sincosGlibc does (the same statement, repeated here so that this
 // header stands alone: |psi| <= pi lies inside the range that routine reduces, negative arguments take the same path).  Every operation is
 // rounded individually in binary32 (the reference's x86-64 build has no FMA), the sine / cosine polynomials in binary64 as libm has them.
-// Every Nleft != -1 / bRight branch projects with this: isInFrustumChecks (k_frustum_two_eyes_point.hpp) is built on it; Fuse's bRight and
-// the two-camera triangulation search still wait, now only for being written on top of it.  It is built once, here.  cos(psi) / sin(psi) on a float are taken as the float overloads (DESIGN.md §2 divergence (3)).
+// Every Nleft != -1 / bRight branch projects with this: isInFrustumChecks (k_frustum_two_eyes_point.hpp) and Fuse's bRight
+// (k_fuse_two_eyes.hip) are built on it.  It is built once, here.  cos(psi) / sin(psi) on a float are taken as the float overloads (DESIGN.md §2 divergence (3)).
 // Plain arithmetic only: compiles for the host behind tests/cpp/host_shim (tests/cpp/kb8_host_check.cpp proves each routine against libm).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -22,6 +22,9 @@ inline bool negativeWalk(int first, int step, int n) { return first < 0 || first
 // ... the older rule refuses every negative step (SearchForInitialization, the frame-to-frame and local-map projection searches)
 inline bool negativeFirstOrStep(int first, int step) { return first < 0 || step < 0; }
 
+// orbx_fuse_two_eyes_device's `eyes`: bit 0 the left search, bit 1 the right; the loop-closing overload (reproj_check = 0) has no right-eye form
+inline bool badFuseEyes(int eyes, int reprojCheck) { return eyes < 1 || eyes > 3 || (!reprojCheck && eyes != 1); }
+
 // ---- limits -----------------------------------------------------------------------------------------------------------------------
 constexpr size_t kLdsBudget = 160 * 1024 - 512;      // dynamic + static LDS a workgroup of the LDS-resident searches may ask for (160 KB per CU)
 inline bool fitsLds(size_t bytes) { return bytes <= kLdsBudget; }

@@ -1,0 +1,49 @@
+// orbx_mapping_two_eyes.cpp - the C ABI of the mapping thread's matchers on TWO-CAMERA keyframes (NLeft != -1; include/orbx.h): the search half
+// of ORBmatcher::Fuse with bRight false and true.  Thin, as the entries of orbx_rows.cpp are: argument checks, the parameter block, a memset of
+// the counters asked for and one launch (k_fuse_two_eyes.hip).  The checks and fills are orbx_entry.hpp's and orbx_internal.hpp's.  A file of
+// its own: tests/test_entry_rejections_gpu.py holds a table of exactly the *_device entries of orbx_rows.cpp, and the rejections of the entry
+// here are held by tests/test_fuse_two_eyes_gpu.py.  No CPU path.
+#include "orbx_internal.hpp"
+
+extern "C" {
+
+int orbx_fuse_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step, const float* d_mp_world,
+                              const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc, const int* d_n_mp, int mp_capacity,
+                              const uint8_t* d_mp_flags, const float* d_poses, const float* tlr12, const orbx_camera_kb8* cam_left,
+                              const orbx_camera_kb8* cam_right, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                              int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4, int nlevels, float th,
+                              int th_low, int reproj_check, int eyes, int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    // d_n_mp and d_exit may be NULL
+    if (!d_mp_world || !d_mp_normal || !d_mp_dist || !d_mp_desc || !d_mp_flags || !d_poses || !tlr12 || !cam_left || !cam_right || !d_kps ||
+        !d_desc || !d_n_out || !d_grid_off || !d_grid_idx || !bounds4 || !d_best_idx || !d_best_dist || !d_n_fused || capacity < 1 ||
+        mp_capacity < 1 || n_pairs < 1 || n_pairs > 65535 || negativeWalk(kf_first, kf_step, n_pairs) || negativeWalk(mp_first, mp_step, n_pairs) ||
+        th_low < 0 || emptyBounds(bounds4) || badFuseEyes(eyes, reproj_check))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/mp_capacity/n_pairs < 1, more than 65535 pairs, a negative rig or list index, "
+                                              "negative th_low, empty bounds, eyes outside 1 .. 3 or reproj_check = 0 with eyes != 1");
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (int rc = ensureScaleBreaks(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    FuseTwoEyesParams p{};
+    fillKb8(p.cam[0], *cam_left);         // mpCamera, mpCamera2 (ORBmatcher.cc:1409, :1416)
+    fillKb8(p.cam[1], *cam_right);
+    fillBoundsTruncated(p, bounds4);      // a KeyFrame's bounds and the Frame's inverses, as orbx_fuse_device; the same for both eyes
+    fillGridInverses(p, bounds4);
+    levelsOnly(p.scale, h->tabs.scale, h->nlevels);
+    levelsOnly(p.invSigma2, h->tabs.invSigma2, h->nlevels);
+    fillBreaks(p, h->scaleBreaks, h->nlevels);
+    for (int i = 0; i < 12; i++) p.tlr[i] = tlr12[i];
+    p.th = th; p.nlevels = h->nlevels; p.thLow = clampDistance(th_low); p.reprojCheck = reproj_check ? 1 : 0; p.eyes = eyes;
+    p.capacity = capacity; p.mpCapacity = mp_capacity; p.kfFirst = kf_first; p.kfStep = kf_step; p.mpFirst = mp_first; p.mpStep = mp_step;
+    {
+        Prof pr(h, S_FRAME);
+        // the counters of the eyes asked for: [p*2 + eye]; those of an eye not asked for stay what they are
+        if (eyes == 3) HIP_TRY(h, hipMemsetAsync(d_n_fused, 0, sizeof(int) * 2 * (size_t)n_pairs, h->stream));
+        else HIP_TRY(h, hipMemset2DAsync(d_n_fused + (eyes - 1), 2 * sizeof(int), 0, sizeof(int), (size_t)n_pairs, h->stream));
+        launchFuseTwoEyes(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps, d_desc,
+                          d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs);
+    }
+    return finishLaunch(h);
+}
+
+}  // extern "C"

@@ -113,6 +113,17 @@ struct FuseParams {              // k_fuse.hip
     int nlevels, thLow, reprojCheck, capacity, mpCapacity, kfFirst, kfStep, mpFirst, mpStep;
 };
 
+struct FuseTwoEyesParams {       // k_fuse_two_eyes.hip
+    float cam[2][8];                                     // KannalaBrandt8::mvParameters of mpCamera (left eye) and mpCamera2 (right eye)
+    float minX, maxX, minY, maxY, wInv, hInv;            // KeyFrame's truncated bounds and the Frame's inverses, as FuseParams; the same for both eyes
+    float scale[kMaxLevels], invSigma2[kMaxLevels];      // mvScaleFactors, mvInvLevelSigma2 of the handle
+    float breaks[kMaxLevels];                            // PredictScale's breakpoints, as FuseParams
+    float tlr[12];                                       // KeyFrame::mTlr, 3x4 row-major: the right eye's getters derive everything from it alone
+    float th;
+    int nlevels, thLow, reprojCheck, eyes, capacity, mpCapacity;
+    int kfFirst, kfStep, mpFirst, mpStep;                // kf: RIG keyframes (device frames 2r, 2r + 1; d_poses holds one pose per rig)
+};
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

@@ -191,6 +191,8 @@ def load_library():
                                                        C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.orbx_fuse_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int,
                                    vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.orbx_fuse_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                            vp, C.c_int, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -646,6 +648,21 @@ class ORBextractor:
             _dev(d_mp_flags), _dev(d_poses), _dev(d_kps_un), _dev(d_u_right), _dev(d_desc), _dev(d_n), capacity, _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds),
             _host_f32(cam), self.nlevels if nlevels is None else nlevels, mbf, th, th_low, int(reproj_check), _dev(d_best_idx), _dev(d_best_dist),
             _dev(d_exit), _dev(d_n_fused)))
+
+    def fuse_two_eyes_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags, d_poses, tlr,
+                             cam_left, cam_right, d_kps, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, d_best_idx, d_best_dist, d_exit,
+                             d_n_fused, th=3.0, th_low=50, reproj_check=True, eyes=3, nlevels=None):
+        """The search half of ORBmatcher::Fuse for two-camera keyframes (NLeft != -1, a KannalaBrandt8 pair; reference
+        src/ORBmatcher.cc:1399-1609 with bRight false and true; reproj_check=False: the loop-closing overload, which needs eyes=1).  kf and
+        mp = (first, step) of the RIG keyframe (device frames 2r, 2r + 1: frame_finish_two_eyes_device) / MapPoint list of pair p; d_poses per
+        rig; tlr = mTlr (3x4); cam_left / cam_right = camera_kb8(...) of mpCamera / mpCamera2; d_kps the RAW keypoints.  eyes: bit 0 the left
+        search, bit 1 the right.  The outputs are [(p*2 + eye)*mp_capacity + i] and d_n_fused [p*2 + eye]; d_best_idx is in the keyframe's
+        numbering (right keypoint i = NLeft + i).  d_n_mp and d_exit may be None.  The caller replays the tails: left, then right."""
+        self._check(self._L.orbx_fuse_two_eyes_device(
+            self._h, n_pairs, kf[0], kf[1], mp[0], mp[1], _dev(d_mp_world), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_mp_desc), _dev(d_n_mp), mp_capacity,
+            _dev(d_mp_flags), _dev(d_poses), _host_f32(tlr), _host_f32(cam_left), _host_f32(cam_right), _dev(d_kps), _dev(d_desc), _dev(d_n), capacity,
+            _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), self.nlevels if nlevels is None else nlevels, th, th_low, int(reproj_check), int(eyes),
+            _dev(d_best_idx), _dev(d_best_dist), _dev(d_exit), _dev(d_n_fused)))
 
     def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,

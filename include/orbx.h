@@ -573,7 +573,8 @@ enum orbx_fuse_exit {
 /* ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th, bRight = false) (src/ORBmatcher.cc:1399-1609; reproj_check = 1) and
  * the loop-closing overload Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1611-1733; reproj_check = 0: the same search without the
  * reprojection test of :1533-1557), for keyframes with NLeft == -1 and the Pinhole model (monocular, rectified stereo, RGB-D).  NOT covered:
- * bRight = true and NLeft != -1 (:1404-1410, :1524-1526, :1559: mpCamera2, the KannalaBrandt8 pair).
+ * bRight = true and NLeft != -1 (:1404-1410, :1524-1526, :1559: mpCamera2, the KannalaBrandt8 pair) - those keyframes go through
+ * orbx_fuse_two_eyes_device below.
  * THE SEARCH HALF ONLY.  Everything up to bestIdx / bestDist (:1455-1570, :1643-1712) reads the MapPoint's position, normal, distance bounds and
  * descriptor and the keyframe's pose, keypoints, grid, mvuRight and descriptors; only the tail (:1573-1592, :1715-1729: Replace /
  * AddObservation / AddMapPoint) touches the map, and it closes no keypoint for later MapPoints.  So all MapPoints of all keyframes are searched
@@ -629,6 +630,51 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
                      const uint8_t* d_desc, const int* d_n_out, int capacity, const int* d_grid_off, const int* d_grid_idx,
                      const float* bounds4, const orbx_camera* cam, int nlevels, float mbf, float th, int th_low, int reproj_check,
                      int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused);
+
+/* ORBmatcher::Fuse for TWO-CAMERA keyframes (NLeft != -1, a KannalaBrandt8 pair): Fuse(pKF, vpMapPoints, th, bRight = false) and
+ * Fuse(pKF, vpMapPoints, th, bRight = true) (src/ORBmatcher.cc:1399-1609 with :1404-1410, :1524-1528, :1559), as
+ * LocalMapping::SearchInNeighbors calls them one after the other (src/LocalMapping.cc:787-788, :816-817), and the loop-closing overload
+ * (:1611-1733; reproj_check = 0) on such a keyframe.  THE SEARCH HALF ONLY, under orbx_fuse_device's contract: the caller replays the tails on
+ * the host and searches the changed survivors again (above; INTEGRATION.md, "SearchInNeighbors", the two-camera loop).  What differs:
+ * FRAMES.  Rig keyframe r is device frames 2r (left eye: mvKeys, mGrid, the left rows of mDescriptors) and 2r + 1 (right eye: mvKeysRight,
+ * mGridRight, the right rows), the layout of orbx_frame_finish_two_eyes_device.  Pair p fuses list mp_first + p*mp_step into RIG
+ * kf_first + p*kf_step.  d_kps holds the RAW keypoints of both eyes: the reference reads mvKeys / mvKeysRight for position and octave
+ * (:1524-1528, src/KeyFrame.cc:801-803), not mvKeysUn.  d_poses[r*12] is one pose per rig, as orbx_frustum_requests_two_eyes_device takes it.
+ * POSES.  Left eye: Rcw | tcw of the pose, Ow = -Rcw.t()*tcw.  Right eye: KeyFrame's getters (src/KeyFrame.cc:1232-1262), which derive
+ * everything from mTlr ALONE (tlr12, 3x4 row-major; Frame's mTrl has no part here): Rrl = mTlr.R.t(); Rrw = Rrl*Rlw, a 3x3 product;
+ * trl = -Rrl*mTlr.t, one gemm with alpha = -1; trw = Rrl*tlw + trl, one gemm with the addend; twr = Rwl*mTlr.t + Ow, one gemm with the float Ow
+ * as addend.  cv::Mat products as everywhere here (products and sums in double, one rounding to float): parity unpinned, as Fuse's.
+ * CAMERAS.  uv = KannalaBrandt8::project with THAT EYE's camera (cam_left = mpCamera, cam_right = mpCamera2; :1409, :1416), libm's atan2f,
+ * sqrtf, sinf, cosf restated for the device (orbx_kb8_project_device).  z < 0.0f leaves (:1459); z == 0 does NOT leave by itself as it does
+ * under the pinhole model: atan2f(r, 0) is pi / 2, the projection is finite and the MapPoint goes on (z = -0.0f as well).
+ * FLAGS.  d_mp_flags[p*mp_capacity + i] is per pair, bit 0 as orbx_fuse_device, and serves BOTH eyes.  The reference's right call sees
+ * IsInKeyFrame after the left call's tail; that re-test belongs to the replay, as it does across keyframes.
+ * eyes: bit 0 = the left search, bit 1 = the right; 1, 2 or 3, anything else is ORBX_ERR_BAD_ARGUMENT.  reproj_check = 0 (the loop-closing
+ * overload) has no right-eye form and requires eyes == 1.  A call with eyes = 2 is the re-search between the eyes of one keyframe.
+ * THE REPROJECTION TEST is always the monocular one, (float)(e2 * invSigma2) promoted against 5.99: mvuRight of a two-camera keyframe has
+ * Nleft entries, all -1 (src/Frame.cc:1150), so ur, invz and mbf have no observable effect and are no arguments.  The reference indexes
+ * mvuRight with the right eye's OWN index (:1533, before :1559), out of bounds where Nright > Nleft: the entry takes -1 there.
+ *   d_mp_world .. d_mp_desc, d_n_mp (clamped to 0 .. mp_capacity, NULL = mp_capacity), the d_mp_dist triples, nlevels, th, th_low : as orbx_fuse_device
+ *   d_kps, d_desc, d_n_out, d_grid_off, d_grid_idx : of all device frames; bounds4 : Frame's FLOAT bounds, the same for both eyes, truncated for
+ *                 IsInImage and the window's subtraction, untruncated for the grid inverses, as orbx_fuse_device
+ *   d_best_idx[(p*2 + eye)*mp_capacity + i]  : out, bestIdx in the KEYFRAME's numbering (:1559) if bestDist <= th_low, else -1: a left keypoint i is
+ *                 i, a right keypoint i is NLeft + i with NLeft = d_n_out[2r] clamped to 0 .. capacity; GetMapPoint(bestIdx) and
+ *                 AddObservation(pKF, bestIdx) take it as it is.  The descriptor of right keypoint i is row i of device frame 2r + 1.
+ *   d_best_dist[(p*2 + eye)*mp_capacity + i] : out, bestDist; 256 where no candidate passed (in both modes)
+ *   d_exit[(p*2 + eye)*mp_capacity + i]      : out or NULL, an orbx_fuse_exit (the same eight codes)
+ *   d_n_fused[p*2 + eye]                     : out, the number of ORBX_FUSE_FUSED of that eye under the flags as passed
+ * All mp_capacity entries of every eye asked for are written; the entries of an eye not asked for are left untouched.  After (u, v) the
+ * arithmetic is orbx_fuse_device's, line by line: IsInImage, the distance and normal tests, PredictScale by breakpoints, radius =
+ * th * mvScaleFactors[level], KeyFrame::GetFeaturesInArea(u, v, r, bRight) on that eye's grid and raw keypoints (four early returns, ix outer /
+ * iy inner / CSR order), kpLevel in [level - 1, level] from the raw octave (-1 CLAMPED into the table), strict <: the FIRST of equal
+ * distances in visit order stays; fused when bestDist <= th_low.  No table lives in LDS: no capacity bound and no ORBX_ERR_UNSUPPORTED case.
+ * ORBX_ERR_BAD_ARGUMENT is returned before any launch.  Asynchronous on the handle's stream. */
+int orbx_fuse_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int mp_first, int mp_step, const float* d_mp_world,
+                              const float* d_mp_normal, const float* d_mp_dist, const uint8_t* d_mp_desc, const int* d_n_mp, int mp_capacity,
+                              const uint8_t* d_mp_flags, const float* d_poses, const float* tlr12, const orbx_camera_kb8* cam_left,
+                              const orbx_camera_kb8* cam_right, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
+                              int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4, int nlevels, float th,
+                              int th_low, int reproj_check, int eyes, int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused);
 
 /* ---- loop closing's matcher: the two Sim3 overloads of ORBmatcher::SearchByProjection ----------------------------------------------------
  * Where a MapPoint left the search (d_exit of orbx_search_by_projection_sim3_device); 0 .. 5 are orbx_fuse_exit's */
