@@ -36,6 +36,7 @@
 #include "k_camera_kb8.hpp"
 #include "k_keyframe_project.hpp"
 #include "k_match_helpers.hpp"
+#include "k_rig_two_eyes.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
 
@@ -45,33 +46,8 @@ namespace {
 enum { kFuse2ExitFlag = 0, kFuse2ExitNegDepth, kFuse2ExitNotInImage, kFuse2ExitDistance, kFuse2ExitNormal, kFuse2ExitEmptyWindow,
        kFuse2ExitAboveThLow, kFuse2ExitFused };      // == ORBX_FUSE_*
 constexpr int kFuse2Threads = 256;
-constexpr int kFuse2EyeFloats = 15;      // one eye of a rig keyframe: mR (row-major) at 0..8, mt at 9..11, the camera centre at 12..14
+constexpr int kFuse2EyeFloats = kRigEyeFloats;      // one eye of a rig keyframe (k_rig_two_eyes.hpp)
 }  // namespace
-
-// Element j = eye * kFuse2EyeFloats + k of the two records, from the rig's pose T (3x4 row-major, Rcw | tcw) and mTlr (3x4 row-major).
-// eye 0: GetRotation, GetTranslation, GetCameraCenter = -Rcw.t()*tcw (KeyFrame.cc:118).  eye 1: GetRightRotation, GetRightTranslation,
-// GetRightCameraCenter (KeyFrame.cc:1232-1262); row r of Rrl = mTlr.R.t() is column r of mTlr's rotation, row r of Rwl column r of Rcw.
-__device__ __forceinline__ float fuseTwoEyesRigElement(const float* T, const float* tlr, int j) {
-    const int eye = j >= kFuse2EyeFloats, k = j - eye * kFuse2EyeFloats;
-    const float tcw[3] = {T[3], T[7], T[11]};
-    const float tlr3[3] = {tlr[3], tlr[7], tlr[11]};
-    if (k < 9) {                                                                     // mR
-        const int r = k / 3, c = k - 3 * r;
-        if (!eye) return T[4 * r + c];
-        const float col[3] = {T[c], T[4 + c], T[8 + c]};
-        return gemmRow(tlr[r], tlr[4 + r], tlr[8 + r], col, 1.0, 0.f, false);       // Rrw = Rrl*Rlw (:1247)
-    }
-    if (k < 12) {                                                                    // mt
-        const int r = k - 9;
-        if (!eye) return tcw[r];
-        const float trl = gemmRow(tlr[r], tlr[4 + r], tlr[8 + r], tlr3, -1.0, 0.f, false);      // trl = -Rrl*mTlr.t (:1257)
-        return gemmRow(tlr[r], tlr[4 + r], tlr[8 + r], tcw, 1.0, trl, true);         // trw = Rrl*tlw + trl (:1259)
-    }
-    const int r = k - 12;                                                            // the centre
-    const float ow = gemmRow(T[r], T[4 + r], T[8 + r], tcw, -1.0, 0.f, false);
-    if (!eye) return ow;
-    return gemmRow(T[r], T[4 + r], T[8 + r], tlr3, 1.0, ow, true);                   // twr = Rwl*tlr + twl (:1238)
-}
 
 // before the barrier: thirty lanes compute the rig's invariants, sixteen others copy the two cameras.  sEye[2 * kFuse2EyeFloats], sCam[16]
 __device__ __forceinline__ void fuseTwoEyesStage(const float* __restrict__ poses, const FuseTwoEyesParams& p, float* sEye, float* sCam) {

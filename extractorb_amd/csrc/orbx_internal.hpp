@@ -36,6 +36,10 @@ size_t triMatchLdsBytes(int capacity, bool stage);
 void launchSearchTriangulation(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const float*, const uint8_t*, const int*, const float*, const float*, const TriMatchParams&, bool, int*, int*, int*, int);
 void launchFuse(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const float*, const uint8_t*, const int*, const int*, const int*, const FuseParams&, int*, int*, uint8_t*, int*, int);
 void launchFuseTwoEyes(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const FuseTwoEyesParams&, int*, int*, uint8_t*, int*, int);
+size_t triMatchTwoEyesLdsBytes(int capacity, bool stage);
+void launchSearchTriangulationTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const TriMatchTwoEyesParams&, bool, int*, int*, int*, int);
+void launchKb8Unproject(hipStream_t, const float*, const float*, int, float*);
+void launchKb8Triangulate(hipStream_t, const float*, const float*, const Kb8TriangulateParams&, float*, float*);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);

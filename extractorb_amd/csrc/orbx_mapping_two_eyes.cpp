@@ -1,8 +1,10 @@
 // orbx_mapping_two_eyes.cpp - the C ABI of the mapping thread's matchers on TWO-CAMERA keyframes (NLeft != -1; include/orbx.h): the search half
-// of ORBmatcher::Fuse with bRight false and true.  Thin, as the entries of orbx_rows.cpp are: argument checks, the parameter block, a memset of
-// the counters asked for and one launch (k_fuse_two_eyes.hip).  The checks and fills are orbx_entry.hpp's and orbx_internal.hpp's.  A file of
-// its own: tests/test_entry_rejections_gpu.py holds a table of exactly the *_device entries of orbx_rows.cpp, and the rejections of the entry
-// here are held by tests/test_fuse_two_eyes_gpu.py.  No CPU path.
+// of ORBmatcher::Fuse with bRight false and true (k_fuse_two_eyes.hip), SearchForTriangulation on such keyframes and the KannalaBrandt8
+// unprojection and triangulation it stands on (k_triangulate_match_two_eyes.hip).  Thin, as the entries of orbx_rows.cpp are: argument
+// checks, the parameter block, a memset of the counters asked for and one launch.  The checks and fills are orbx_entry.hpp's and
+// orbx_internal.hpp's.  A file of its own: tests/test_entry_rejections_gpu.py holds a table of exactly the *_device entries of orbx_rows.cpp,
+// and the rejections of the entries here are held by tests/test_fuse_two_eyes_gpu.py and tests/test_search_triangulation_two_eyes_gpu.py.
+// No CPU path.
 #include "orbx_internal.hpp"
 
 extern "C" {
@@ -42,6 +44,73 @@ int orbx_fuse_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_
         else HIP_TRY(h, hipMemset2DAsync(d_n_fused + (eyes - 1), 2 * sizeof(int), 0, sizeof(int), (size_t)n_pairs, h->stream));
         launchFuseTwoEyes(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps, d_desc,
                           d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs);
+    }
+    return finishLaunch(h);
+}
+
+int orbx_search_for_triangulation_two_eyes_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
+                                                  const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat,
+                                                  const uint8_t* d_kf1_mp_flags, const uint8_t* d_kf2_mp_flags, const float* d_poses,
+                                                  const float* tlr12, const orbx_camera_kb8* cam_left, const orbx_camera_kb8* cam_right,
+                                                  const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out, int capacity, int nlevels,
+                                                  int only_stereo, int coarse, int th_low, int check_orientation, int* d_matches12, int* d_pairs,
+                                                  int* d_n_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_feat_nodes || !d_feat_idx || !d_n_feat || !d_kf1_mp_flags || !d_kf2_mp_flags || !d_poses || !tlr12 || !cam_left || !cam_right ||
+        !d_kps || !d_desc || !d_n_out || !d_matches12 || !d_pairs || !d_n_matches || capacity < 1 || n_pairs < 1 ||
+        negativeWalk(kf1_first, kf1_step, n_pairs) || negativeWalk(kf2_first, kf2_step, n_pairs))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1 or a negative rig index");
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (!fitsLds(triMatchTwoEyesLdsBytes(capacity, false)))
+        return fail(h, ORBX_ERR_UNSUPPORTED, "capacity too large for the LDS-resident two-camera triangulation search (62 bytes per slot of the "
+                                             "per-eye capacity rounded up to 16, + 1024: 160 KB per CU)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    TriMatchTwoEyesParams p{};
+    fillKb8(p.cam[0], *cam_left);         // mpCamera, mpCamera2 of both keyframes (one rig)
+    fillKb8(p.cam[1], *cam_right);
+    levelsWholeTable(p.sigma2, h->tabs.sigma2);
+    for (int i = 0; i < 12; i++) p.tlr[i] = tlr12[i];
+    p.nlevels = std::max(1, std::min(h->nlevels, (int)kMaxLevels));
+    p.thLow = th_low; p.checkOrientation = check_orientation ? 1 : 0; p.onlyStereo = only_stereo ? 1 : 0; p.coarse = coarse ? 1 : 0;
+    p.capacity = capacity; p.kf1First = kf1_first; p.kf1Step = kf1_step; p.kf2First = kf2_first; p.kf2Step = kf2_step;
+    const bool stage = fitsLds(triMatchTwoEyesLdsBytes(capacity, true));
+    {
+        Prof pr(h, S_FRAME);
+        launchSearchTriangulationTwoEyes(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, d_poses, (const Keypoint*)d_kps,
+                                         d_desc, d_n_out, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs);
+    }
+    return finishLaunch(h);
+}
+
+int orbx_kb8_unproject_device(orbx_handle* h, int n, const float* d_uv, const orbx_camera_kb8* cam, float* d_rays) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_uv || !cam || !d_rays || n < 1) return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer or n < 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    float k[8];
+    fillKb8(k, *cam);
+    {
+        Prof pr(h, S_FRAME);
+        launchKb8Unproject(h->stream, d_uv, k, n, d_rays);
+    }
+    return finishLaunch(h);
+}
+
+int orbx_kb8_triangulate_device(orbx_handle* h, int n, const float* d_kp1, const float* d_kp2, const orbx_camera_kb8* cam1,
+                                const orbx_camera_kb8* cam2, const float* r12_9, const float* t12_3, float sigma1, float sigma2, float* d_z,
+                                float* d_x3d) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    if (!d_kp1 || !d_kp2 || !cam1 || !cam2 || !r12_9 || !t12_3 || !d_z || !d_x3d || n < 1)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer or n < 1");
+    HIP_TRY(h, hipSetDevice(h->device));
+    Kb8TriangulateParams p{};
+    fillKb8(p.cam1, *cam1);
+    fillKb8(p.cam2, *cam2);
+    for (int i = 0; i < 9; i++) p.R12[i] = r12_9[i];
+    for (int i = 0; i < 3; i++) p.t12[i] = t12_3[i];
+    p.sigma1 = sigma1; p.sigma2 = sigma2; p.n = n;
+    {
+        Prof pr(h, S_FRAME);
+        launchKb8Triangulate(h->stream, d_kp1, d_kp2, p, d_z, d_x3d);
     }
     return finishLaunch(h);
 }

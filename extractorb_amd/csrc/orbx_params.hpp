@@ -124,6 +124,22 @@ struct FuseTwoEyesParams {       // k_fuse_two_eyes.hip
     int kfFirst, kfStep, mpFirst, mpStep;                // kf: RIG keyframes (device frames 2r, 2r + 1; d_poses holds one pose per rig)
 };
 
+struct TriMatchTwoEyesParams {   // k_triangulate_match_two_eyes.hip
+    float cam[2][8];                                     // KannalaBrandt8::mvParameters of mpCamera (left eye) and mpCamera2 (right eye)
+    float sigma2[kMaxLevels];                            // mvLevelSigma2 of the handle
+    float tlr[12];                                       // KeyFrame::mTlr, 3x4 row-major
+    int nlevels, thLow, checkOrientation, onlyStereo, coarse, capacity;
+    int kf1First, kf1Step, kf2First, kf2Step;            // RIG keyframes (device frames 2X, 2X + 1; d_poses holds one pose per rig)
+    int countStats;                                      // orbx_debug_search_triangulation_two_eyes_enable: add this launch's counts to g_triTwoEyesStats
+};
+
+struct Kb8UnprojectParams { float k[8]; int n; };   // k_kb8_unproject: KannalaBrandt8::mvParameters by value
+
+struct Kb8TriangulateParams {    // k_kb8_triangulate
+    float cam1[8], cam2[8], R12[9], t12[3], sigma1, sigma2;
+    int n;
+};
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

@@ -193,6 +193,12 @@ def load_library():
                                    vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
     L.orbx_fuse_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                             vp, C.c_int, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.orbx_search_for_triangulation_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                                vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.orbx_kb8_unproject_device.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbx_kb8_triangulate_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp]
+    L.orbx_debug_search_triangulation_two_eyes_stats.argtypes = [ip]
+    L.orbx_debug_search_triangulation_two_eyes_enable.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -663,6 +669,43 @@ class ORBextractor:
             _dev(d_mp_flags), _dev(d_poses), _host_f32(tlr), _host_f32(cam_left), _host_f32(cam_right), _dev(d_kps), _dev(d_desc), _dev(d_n), capacity,
             _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), self.nlevels if nlevels is None else nlevels, th, th_low, int(reproj_check), int(eyes),
             _dev(d_best_idx), _dev(d_best_dist), _dev(d_exit), _dev(d_n_fused)))
+
+    def search_for_triangulation_two_eyes_device(self, n_pairs, kf1, kf2, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, d_poses,
+                                                 tlr, cam_left, cam_right, d_kps, d_desc, d_n, capacity, d_matches12, d_pairs, d_n_matches,
+                                                 only_stereo=False, coarse=False, th_low=50, check_orientation=True, nlevels=None):
+        """ORBmatcher::SearchForTriangulation for two-camera keyframes (NLeft != -1, a KannalaBrandt8 pair; reference src/ORBmatcher.cc:965-1206
+        with the branches :994-1004 and :1099-1129).  kf1 and kf2 = (first, step) of the RIG keyframes (device frames 2X, 2X + 1), step 0 = one
+        keyframe against many; the FeatureVectors are per eye (compute_bow_device); d_poses per rig; tlr = mTlr (3x4); cam_left / cam_right =
+        camera_kb8(...); d_kps the RAW keypoints.  Flags and d_matches12 are [(2p + eye)*capacity + i]; d_matches12 holds keyframe 2's
+        stacked index (right keypoint j = NLeft + j); d_pairs [(p*2*capacity + k)*2] holds d_n_matches[p] pairs in stacked numbering."""
+        self._check(self._L.orbx_search_for_triangulation_two_eyes_device(
+            self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], _dev(d_feat_nodes), _dev(d_feat_idx), _dev(d_n_feat), _dev(d_kf1_mp_flags),
+            _dev(d_kf2_mp_flags), _dev(d_poses), _host_f32(tlr), _host_f32(cam_left), _host_f32(cam_right), _dev(d_kps), _dev(d_desc), _dev(d_n),
+            capacity, self.nlevels if nlevels is None else nlevels, int(only_stereo), int(coarse), th_low, int(check_orientation),
+            _dev(d_matches12), _dev(d_pairs), _dev(d_n_matches)))
+
+    def search_triangulation_two_eyes_count(self, on=True):
+        """switches the debug counters of search_for_triangulation_two_eyes_device on or off (process-wide; off by default)"""
+        self._check(self._L.orbx_debug_search_triangulation_two_eyes_enable(int(on)))
+
+    def search_triangulation_two_eyes_stats(self):
+        """(kb8TriangulateMatches calls, candidates with dist <= th_low) of the last counted search_for_triangulation_two_eyes_device, all
+        pairs; waits for the whole device."""
+        out = (C.c_int * 2)()
+        self._check(self._L.orbx_debug_search_triangulation_two_eyes_stats(out))
+        return out[0], out[1]
+
+    def kb8_unproject_device(self, n, d_uv, cam, d_rays):
+        """KannalaBrandt8::unproject (reference src/CameraModels/KannalaBrandt8.cpp:103-130) over n device-resident pixels: d_uv [n*2] in,
+        d_rays [n*3] out (x, y, 1); cam = camera_kb8(...)."""
+        self._check(self._L.orbx_kb8_unproject_device(self._h, n, _dev(d_uv), _host_f32(cam), _dev(d_rays)))
+
+    def kb8_triangulate_device(self, n, d_kp1, d_kp2, cam1, cam2, r12, t12, sigma1, sigma2, d_z, d_x3d):
+        """KannalaBrandt8::TriangulateMatches (reference src/CameraModels/KannalaBrandt8.cpp:336-405) over n device-resident keypoint pairs:
+        d_kp1 / d_kp2 [n*2] pixels, r12 (3x3) and t12 (3) on the host, sigma1 / sigma2 = mvLevelSigma2 of the two octaves; d_z [n] is the
+        return value (z1, or -1), d_x3d [n*3] the point in camera 1 (zeros when the parallax test left)."""
+        self._check(self._L.orbx_kb8_triangulate_device(self._h, n, _dev(d_kp1), _dev(d_kp2), _host_f32(cam1), _host_f32(cam2), _host_f32(r12),
+                                                        _host_f32(t12), sigma1, sigma2, _dev(d_z), _dev(d_x3d)))
 
     def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,

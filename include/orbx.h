@@ -503,8 +503,9 @@ int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first
 /* ---- the mapping thread's matcher: ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) -----------
  * (src/ORBmatcher.cc:965-1206; LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:456-463, once per neighbour keyframe; src/Tracking.cc:3702-3706)
  * for keyframes with NLeft == -1 and no mpCamera2 on either side (monocular, rectified stereo, RGB-D) and the Pinhole model
- * (Pinhole::epipolarConstrain, src/CameraModels/Pinhole.cpp:122-144).  NOT covered: the two-camera branches (:994-1004, :1099-1129;
- * KannalaBrandt8) and the second overload (:1208-1397, matchAndtriangulate), which nothing in the reference calls.
+ * (Pinhole::epipolarConstrain, src/CameraModels/Pinhole.cpp:122-144).  The two-camera branches (:994-1004, :1099-1129;
+ * KannalaBrandt8) are orbx_search_for_triangulation_two_eyes_device below.  NOT covered: the second overload (:1208-1397,
+ * matchAndtriangulate), which nothing in the reference calls.
  * Pair p matches keyframe 1 = frame kf1_first + p*kf1_step against keyframe 2 = frame kf2_first + p*kf2_step of one device-resident batch;
  * kf1_step = 0 is LocalMapping's shape (one new keyframe against its neighbours), kf2_step = 0 is allowed as well.
  *   d_feat_nodes, d_feat_idx, d_n_feat : mFeatVec of all frames as written by orbx_compute_bow_device (same capacity)
@@ -675,6 +676,64 @@ int orbx_fuse_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_
                               const orbx_camera_kb8* cam_right, const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out,
                               int capacity, const int* d_grid_off, const int* d_grid_idx, const float* bounds4, int nlevels, float th,
                               int th_low, int reproj_check, int eyes, int* d_best_idx, int* d_best_dist, uint8_t* d_exit, int* d_n_fused);
+
+/* ---- ORBmatcher::SearchForTriangulation for TWO-CAMERA keyframes (src/ORBmatcher.cc:965-1206 with mpCamera2 on both sides: the branches
+ * :994-1004 and :1099-1129; a KannalaBrandt8 pair; LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:456-463) and the camera math it
+ * stands on, as entries of their own ------------------------------------------------------------------------------------------------------
+ * KannalaBrandt8::unproject(const cv::Point2f&) (src/CameraModels/KannalaBrandt8.cpp:103-130) over n device-resident pixels:
+ *   d_uv[i*2 + {0,1}] in, d_rays[i*3 + {0,1,2}] out (x, y, 1).
+ * Every operation is rounded in binary32 in the reference's order: the clamp of theta_d against (float)(CV_PI / 2), the compare with 1e-8 in
+ * double, ten Newton steps with the early exit at `const float precision` = 1e-6, std::tan as glibc 2.35's binary32 tanf.  Asynchronous on
+ * the handle's stream. */
+int orbx_kb8_unproject_device(orbx_handle* h, int n, const float* d_uv, const orbx_camera_kb8* cam, float* d_rays);
+
+/* KannalaBrandt8::TriangulateMatches(pCamera2, kp1, kp2, R12, t12, sigmaLevel, unc, p3D) (src/CameraModels/KannalaBrandt8.cpp:336-405, with
+ * Triangulate, :424-437) over n device-resident keypoint pairs under ONE relative pose:
+ *   d_kp1 / d_kp2[i*2 + {0,1}] : kp1.pt under cam1 (this), kp2.pt under cam2 (pCamera2)
+ *   r12_9, t12_3               : R12 (row-major) and t12, host pointers;  sigma1 = sigmaLevel, sigma2 = unc
+ *   d_z[i]                     : out, the return value: z1, or -1 (parallax above 0.9998, z1 <= 0, z2 <= 0, a reprojection error above
+ *                                5.991 * sigma); epipolarConstrain (:237-240) is d_z[i] > 0.0001f
+ *   d_x3d[i*3 + {0,1,2}]       : out, x3D in camera 1 (zeros when the parallax test left; the reference leaves p3D untouched on every -1)
+ * vt.row(3) of cv::SVD::compute is the library's own one-sided Jacobi in binary32 (cv::SVD is OpenCV's Jacobi or
+ * LAPACK's sgesdd by its build, parity unpinned), the cv::Mat / cv::MatExpr roundings are listed there.  A zero fourth component flows
+ * through as infinity or NaN, on which every test is false; NaN > 0.0001f rejects.  Asynchronous on the handle's stream. */
+int orbx_kb8_triangulate_device(orbx_handle* h, int n, const float* d_kp1, const float* d_kp2, const orbx_camera_kb8* cam1,
+                                const orbx_camera_kb8* cam2, const float* r12_9, const float* t12_3, float sigma1, float sigma2, float* d_z,
+                                float* d_x3d);
+
+/* The search.  Pair p matches rig keyframe K1 = kf1_first + p*kf1_step against K2 = kf2_first + p*kf2_step; a rig keyframe X is batch frames
+ * 2X (left eye: mvKeys, the first NLeft rows of mDescriptors) and 2X + 1 (right eye: mvKeysRight), NLeft = d_n_out[2X], as in
+ * orbx_search_by_bow_two_eyes_device.  kf1_step = 0 is LocalMapping's shape.
+ *   d_feat_nodes, d_feat_idx, d_n_feat : what orbx_compute_bow_device wrote PER EYE (same capacity); a node's list of the stacked mFeatVec
+ *                 is the left eye's list followed by the right eye's (+ NLeft), and the entry walks them so
+ *   d_kf1_mp_flags / d_kf2_mp_flags[(2p + eye)*capacity + i] : bit 0 = GetMapPoint of that keypoint of keyframe 1 / 2 of pair p is not NULL
+ *   d_poses[X*12] : Tcw of rig keyframe X (3x4 row-major);  tlr12 : mTlr (3x4, host);  cam_left / cam_right : mpCamera / mpCamera2 (host),
+ *                 as orbx_fuse_two_eyes_device takes them: the eyes' rotations and translations are KeyFrame's getters
+ *                 (src/KeyFrame.cc:1232-1262), the four (R12, t12) are :995-1003 as cv::gemm rows
+ *   d_kps[f*capacity + i] : the RAW keypoints of all frames (:1048-1050, :1083-1085: mvKeys / mvKeysRight, not mvKeysUn); .pt, .octave,
+ *                 .angle are read;  d_desc, d_n_out : descriptors and counts of all frames;  nlevels : the handle's
+ *   only_stereo = bOnlyStereo: bStereo1 is false on such keyframes (:1041), so 1 returns no match;  coarse = bCoarse: accepts without the
+ *                 geometric test (:1132);  th_low = TH_LOW (50);  check_orientation = mbCheckOrientation
+ *   d_matches12[(2p + eye)*capacity + i] : out, keyframe 2's keypoint chosen for keypoint i of that eye of keyframe 1 in the STACKED
+ *                 numbering (a right keypoint j is NLeft + j), -1 = none; all capacity entries of both eyes are written
+ *   d_pairs[(p*2*capacity + k)*2 + {0, 1}] : out, vMatchedPairs in stacked numbering, increasing; entries from d_n_matches[p] on are left
+ *   d_n_matches[p] : out, the return value
+ * As the reference: there is no stereo filter and no epipole disc on such keyframes (:1070, :1089), F12 and the epipole are not read; the
+ * geometric test is pCamera1->epipolarConstrain(pCamera2, kp1, kp2, R12, t12, mvLevelSigma2[kp1.octave], mvLevelSigma2[kp2.octave]) with the
+ * cameras and (R12, t12) of the candidate's eye combination; of the passing candidates within th_low the smallest distance wins and of
+ * equal distances the LAST in list order; vbMatched2 is never set.  An octave outside [0, nlevels) is CLAMPED into the table.
+ * Supported: the tables of a pair live in LDS, capacity counted over both eyes,
+ *   62 * ((capacity + 15) & ~15) + 1024 <= 163 328 bytes      (capacity <= 2608 per eye; 2 x 1302 of a 1200-feature extractor are inside)
+ * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched.  While 126 * ((capacity + 15) & ~15) + 1024 <= 163 328
+ * (capacity <= 1280 per eye) keyframe 2's descriptors are staged in LDS as well; above, they are read from L2.  Asynchronous on the
+ * handle's stream. */
+int orbx_search_for_triangulation_two_eyes_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
+                                                  const uint32_t* d_feat_nodes, const uint32_t* d_feat_idx, const int* d_n_feat,
+                                                  const uint8_t* d_kf1_mp_flags, const uint8_t* d_kf2_mp_flags, const float* d_poses,
+                                                  const float* tlr12, const orbx_camera_kb8* cam_left, const orbx_camera_kb8* cam_right,
+                                                  const orbx_keypoint* d_kps, const uint8_t* d_desc, const int* d_n_out, int capacity, int nlevels,
+                                                  int only_stereo, int coarse, int th_low, int check_orientation, int* d_matches12, int* d_pairs,
+                                                  int* d_n_matches);
 
 /* ---- loop closing's matcher: the two Sim3 overloads of ORBmatcher::SearchByProjection ----------------------------------------------------
  * Where a MapPoint left the search (d_exit of orbx_search_by_projection_sim3_device); 0 .. 5 are orbx_fuse_exit's */
@@ -903,6 +962,12 @@ int orbx_debug_two_eyes_search_stats(int* out4);
 /* the two-eye frame-to-frame search (orbx_search_last_frame_two_eyes_device), the last launch's pair 0: out4[0] rounds of the fixed point,
  * out4[1..3] 100 MHz ticks of staging, of the first scan and of the rounds */
 int orbx_debug_last_frame_two_eyes_stats(int* out4);
+/* the two-camera triangulation search (orbx_search_for_triangulation_two_eyes_device): counters are kept only after
+ * orbx_debug_search_triangulation_two_eyes_enable(1) (process-wide; off by default, a launch then pays nothing for them).  The last counted
+ * launch, all pairs: out2[0] calls of KannalaBrandt8::TriangulateMatches, out2[1] candidates without a MapPoint and with dist <= th_low.
+ * The read waits for the whole device (hipDeviceSynchronize), whatever stream the handle uses. */
+int orbx_debug_search_triangulation_two_eyes_enable(int on);
+int orbx_debug_search_triangulation_two_eyes_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
  * (the last one changes nothing), [1] requests of the last launch whose decision came from scanning the window again (every key of a

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Seeded soak of the matcher rows on the GPU box: the parity tests of tests/test_search_projection.py, tests/test_search_bow.py,
-tests/test_search_init.py, tests/test_search_init_edges.py, tests/test_stereo_edges.py, tests/test_search_triangulation.py, tests/test_fuse_gpu.py and tests/test_fuse_two_eyes_gpu.py bodies re-run with seeds outside the committed parametrisation.
+tests/test_search_init.py, tests/test_search_init_edges.py, tests/test_stereo_edges.py, tests/test_search_triangulation.py, tests/test_fuse_gpu.py, tests/test_fuse_two_eyes_gpu.py and tests/test_search_triangulation_two_eyes_gpu.py bodies re-run with seeds outside the committed parametrisation.
 usage: fuzz_matchers.py [n_seeds] [first_seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +18,7 @@ import test_stereo_edges as E
 import test_search_init_edges as IE
 import test_fuse_gpu as FU
 import test_fuse_two_eyes_gpu as FU2
+import test_search_triangulation_two_eyes_gpu as T2
 from extractorb_amd import synth
 t0 = time.time()
 done = 0
@@ -44,5 +45,7 @@ for k in range(n):
     FU.check_gpu_on_seed(seed, reproj_check=bool(trng.integers(0, 2)), th=float(trng.choice([3.0, 3.0, 5.0])))      # the search half of Fuse, one list into three keyframes
     frng = np.random.default_rng(seed + 177)     # (again a generator of its own)
     FU2.check_gpu_on_seed(seed, th=float(frng.choice([3.0, 3.0, 4.0])))      # Fuse on two-camera keyframes: one list into both eyes of three rigs
+    T2.check_gpu_on_seed(seed, coarse=bool(frng.random() < 0.2), th_low=int(frng.choice([50, 50, 30])),
+                         check_orientation=bool(frng.integers(0, 2)))      # SearchForTriangulation on two-camera keyframes: one rig against three
     done += 1
-print("matcher soak: %d seeds x 9 matcher parity bodies (+ SearchForInitialization every fifth seed) bit-exact, %.0f s" % (done, time.time() - t0))
+print("matcher soak: %d seeds x 10 matcher parity bodies (+ SearchForInitialization every fifth seed) bit-exact, %.0f s" % (done, time.time() - t0))
