@@ -39,18 +39,17 @@
 #include <stdint.h>
 
 #include "k_camera_kb8_unproject.hpp"
+#include "k_lds_vec.hpp"
 #include "k_match_helpers.hpp"
 #include "k_rig_two_eyes.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
 
 #ifdef ORBX_HOST_ROW
-#define ORBX_LDS
-namespace orbx { typedef uint4 TriU4; constexpr int kTriRowLanes = 1; }
+namespace orbx { typedef LdsU4 TriU4; constexpr int kTriRowLanes = 1; }
 #else
 #include "k_wave_min.hpp"
-#define ORBX_LDS __attribute__((address_space(3)))
-namespace orbx { typedef uint32_t TriU4 __attribute__((ext_vector_type(4))); constexpr int kTriRowLanes = 16; }
+namespace orbx { typedef LdsU4 TriU4; constexpr int kTriRowLanes = 16; }
 #endif
 
 namespace orbx {

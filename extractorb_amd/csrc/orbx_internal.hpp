@@ -40,6 +40,8 @@ size_t triMatchTwoEyesLdsBytes(int capacity, bool stage);
 void launchSearchTriangulationTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const TriMatchTwoEyesParams&, bool, int*, int*, int*, int);
 void launchKb8Unproject(hipStream_t, const float*, const float*, int, float*);
 void launchKb8Triangulate(hipStream_t, const float*, const float*, const Kb8TriangulateParams&, float*, float*);
+int stereoFisheyeTiles(int capacity);
+void launchStereoFisheye(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const StereoFisheyeParams&, int*, int*, float*, float*, int*, int*, int);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);

@@ -1,9 +1,11 @@
 // orbx_mapping_two_eyes.cpp - the C ABI of the mapping thread's matchers on TWO-CAMERA keyframes (NLeft != -1; include/orbx.h): the search half
 // of ORBmatcher::Fuse with bRight false and true (k_fuse_two_eyes.hip), SearchForTriangulation on such keyframes and the KannalaBrandt8
-// unprojection and triangulation it stands on (k_triangulate_match_two_eyes.hip).  Thin, as the entries of orbx_rows.cpp are: argument
+// unprojection and triangulation it stands on (k_triangulate_match_two_eyes.hip), and the two-camera Frame constructor's
+// ComputeStereoFishEyeMatches, which stands on the same camera header (k_stereo_fisheye.hip).  Thin, as the entries of orbx_rows.cpp are: argument
 // checks, the parameter block, a memset of the counters asked for and one launch.  The checks and fills are orbx_entry.hpp's and
 // orbx_internal.hpp's.  A file of its own: tests/test_entry_rejections_gpu.py holds a table of exactly the *_device entries of orbx_rows.cpp,
-// and the rejections of the entries here are held by tests/test_fuse_two_eyes_gpu.py and tests/test_search_triangulation_two_eyes_gpu.py.
+// and the rejections of the entries here are held by tests/test_fuse_two_eyes_gpu.py, tests/test_search_triangulation_two_eyes_gpu.py and
+// tests/test_stereo_fisheye_gpu.py.
 // No CPU path.
 #include "orbx_internal.hpp"
 
@@ -111,6 +113,36 @@ int orbx_kb8_triangulate_device(orbx_handle* h, int n, const float* d_kp1, const
     {
         Prof pr(h, S_FRAME);
         launchKb8Triangulate(h->stream, d_kp1, d_kp2, p, d_z, d_x3d);
+    }
+    return finishLaunch(h);
+}
+
+int orbx_stereo_fisheye_match_device(orbx_handle* h, int n_rigs, int rig_first, int rig_step, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                     const int* d_n_out, const int* d_mono_out, int capacity, const float* tlr12, const orbx_camera_kb8* cam_left,
+                                     const orbx_camera_kb8* cam_right, int nlevels, int* d_left_to_right, int* d_right_to_left, float* d_depth,
+                                     float* d_x3d, int* d_n_matches, int* d_n_desc_matches) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    // d_n_desc_matches may be NULL.  The grid folds the rigs into x: n_rigs times the workgroups of a rig has to fit a launch
+    if (!d_kps || !d_desc || !d_n_out || !d_mono_out || !tlr12 || !cam_left || !cam_right || !d_left_to_right || !d_right_to_left || !d_depth ||
+        !d_x3d || !d_n_matches || capacity < 1 || n_rigs < 1 || negativeWalk(rig_first, rig_step, n_rigs) ||
+        (long long)n_rigs * stereoFisheyeTiles(capacity) > 0x7fffffffLL)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_rigs < 1, a negative rig index or more than 2^31 - 1 workgroups");
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    StereoFisheyeParams p{};
+    fillKb8(p.cam[0], *cam_left);         // mpCamera, mpCamera2 (Frame.cc:1169)
+    fillKb8(p.cam[1], *cam_right);
+    levelsWholeTable(p.sigma2, h->tabs.sigma2);
+    for (int r = 0; r < 3; r++) {         // mRlr, mtlr (Frame.cc:1100-1101), handed to TriangulateMatches as they are
+        for (int c = 0; c < 3; c++) p.R12[3 * r + c] = tlr12[4 * r + c];
+        p.t12[r] = tlr12[4 * r + 3];
+    }
+    p.nlevels = std::max(1, std::min(h->nlevels, (int)kMaxLevels));
+    p.capacity = capacity; p.rigFirst = rig_first; p.rigStep = rig_step;
+    {
+        Prof pr(h, S_FRAME);
+        launchStereoFisheye(h->stream, (const Keypoint*)d_kps, d_desc, d_n_out, d_mono_out, p, d_left_to_right, d_right_to_left, d_depth, d_x3d,
+                            d_n_matches, d_n_desc_matches, n_rigs);
     }
     return finishLaunch(h);
 }

@@ -140,6 +140,15 @@ struct Kb8TriangulateParams {    // k_kb8_triangulate
     int n;
 };
 
+struct StereoFisheyeParams {     // k_stereo_fisheye.hip
+    float cam[2][8];                                     // KannalaBrandt8::mvParameters of mpCamera (left eye) and mpCamera2 (right eye)
+    float sigma2[kMaxLevels];                            // mvLevelSigma2 of the handle
+    float R12[9], t12[3];                                // Frame::mRlr (row-major) and mtlr: mTlr's rotation and last column, as they are
+    int nlevels, capacity, rigFirst, rigStep;            // RIG frames (device frames 2r, 2r + 1)
+    int tiles;                                           // workgroups per rig: ceil(capacity / rows per workgroup)
+    int countStats;                                      // orbx_debug_stereo_fisheye_enable: add this launch's triangulations to g_stereoFisheyeStats
+};
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

@@ -199,6 +199,9 @@ def load_library():
     L.orbx_kb8_triangulate_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp]
     L.orbx_debug_search_triangulation_two_eyes_stats.argtypes = [ip]
     L.orbx_debug_search_triangulation_two_eyes_enable.argtypes = [C.c_int]
+    L.orbx_stereo_fisheye_match_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.orbx_debug_stereo_fisheye_stats.argtypes = [ip]
+    L.orbx_debug_stereo_fisheye_enable.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -706,6 +709,30 @@ class ORBextractor:
         return value (z1, or -1), d_x3d [n*3] the point in camera 1 (zeros when the parallax test left)."""
         self._check(self._L.orbx_kb8_triangulate_device(self._h, n, _dev(d_kp1), _dev(d_kp2), _host_f32(cam1), _host_f32(cam2), _host_f32(r12),
                                                         _host_f32(t12), sigma1, sigma2, _dev(d_z), _dev(d_x3d)))
+
+    def stereo_fisheye_match_device(self, n_rigs, rigs, d_kps, d_desc, d_n, d_mono, capacity, tlr, cam_left, cam_right, d_left_to_right,
+                                    d_right_to_left, d_depth, d_x3d, d_n_matches, d_n_desc_matches=None, nlevels=None):
+        """Frame::ComputeStereoFishEyeMatches (reference src/Frame.cc:1139-1179) for n_rigs two-camera frames: rigs = (first, step) of the RIG
+        frames (device frames 2r, 2r + 1); d_kps / d_desc / d_n / d_mono as extract_batch_device wrote them (RAW keypoints, Nleft / Nright,
+        monoLeft / monoRight); tlr = mTlr (3x4); cam_left / cam_right = camera_kb8(...).  d_left_to_right [(2r)*capacity + i] holds the raw
+        right index, d_right_to_left [(2r + 1)*capacity + j] the raw left index (the largest accepted one: the arrays are not inverse),
+        d_depth [(2r)*capacity + i] and d_x3d [((2r)*capacity + i)*3] mvDepth and mvStereo3Dpoints (zeros where nothing matched);
+        d_n_matches [q] nMatches, d_n_desc_matches [q] (or None) the rows that passed the ratio test.  The layout is what
+        search_by_projection_two_eyes_device reads."""
+        self._check(self._L.orbx_stereo_fisheye_match_device(
+            self._h, n_rigs, rigs[0], rigs[1], _dev(d_kps), _dev(d_desc), _dev(d_n), _dev(d_mono), capacity, _host_f32(tlr), _host_f32(cam_left),
+            _host_f32(cam_right), self.nlevels if nlevels is None else nlevels, _dev(d_left_to_right), _dev(d_right_to_left), _dev(d_depth),
+            _dev(d_x3d), _dev(d_n_matches), _dev(d_n_desc_matches)))
+
+    def stereo_fisheye_count(self, on=True):
+        """switches the debug counter of stereo_fisheye_match_device on or off (process-wide; off by default)"""
+        self._check(self._L.orbx_debug_stereo_fisheye_enable(int(on)))
+
+    def stereo_fisheye_stats(self):
+        """kb8TriangulateMatches calls of the last counted stereo_fisheye_match_device, all rigs; waits for the whole device."""
+        out = (C.c_int * 1)()
+        self._check(self._L.orbx_debug_stereo_fisheye_stats(out))
+        return out[0]
 
     def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,

@@ -338,7 +338,8 @@ int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first,
  *   d_kps, d_desc, d_n_out : the extraction's RAW keypoints (mvKeys / mvKeysRight), descriptors and counts, [f*capacity + i]
  *   d_grid_off, d_grid_idx, bounds4 : as written by / passed to orbx_frame_finish_two_eyes_device
  *   d_left_to_right[fL*capacity + i], d_right_to_left[(fL + 1)*capacity + j] : mvLeftToRightMatch / mvRightToLeftMatch
- *            (ComputeStereoFishEyeMatches), each read on its own branch as the reference does, not assumed inverse; NULL = all -1; an entry
+ *            (ComputeStereoFishEyeMatches: orbx_stereo_fisheye_match_device writes them in this layout), each read on its own branch as
+ *            the reference does, not assumed inverse; NULL = all -1; an entry
  *            outside [0, N of the other eye) is taken as -1 (the reference would index out of bounds)
  *   d_occupied[(2q + eye)*capacity + i] : in/out or NULL (= all free): the keypoint holds a MapPoint with Observations() > 0
  *   nn_ratio : mfNNratio;  max_distance : TH_HIGH = 100
@@ -735,6 +736,43 @@ int orbx_search_for_triangulation_two_eyes_device(orbx_handle* h, int n_pairs, i
                                                   int only_stereo, int coarse, int th_low, int check_orientation, int* d_matches12, int* d_pairs,
                                                   int* d_n_matches);
 
+/* ---- Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1139-1179; the two-camera Frame constructor, :1108): the per-frame stereo matches of a
+ * fisheye rig, the counterpart of orbx_stereo_match_device (rectified stereo) --------------------------------------------------------------
+ * Rig r = rig_first + q*rig_step is batch frames 2r (left eye: mvKeys, mDescriptors) and 2r + 1 (right eye), as every two-eye entry numbers
+ * them.
+ *   d_kps, d_desc, d_n_out, d_mono_out : what orbx_extract_batch_device wrote: the RAW keypoints, descriptors, Nleft / Nright and monoLeft /
+ *                 monoRight of every batch frame.  N is clamped into [0, capacity] and mono into [0, N] (the reference would index out of
+ *                 bounds).  The lapping rows are [mono, N) of each eye.
+ *   tlr12       : mTlr (3x4 row-major, host): R12 = mRlr is its rotation and t12 = mtlr its last column, handed to TriangulateMatches as
+ *                 they are (:1169);  cam_left / cam_right : mpCamera / mpCamera2 (host);  nlevels : the handle's
+ *   d_left_to_right[(2r)*capacity + i]      : out, mvLeftToRightMatch: the RAW right index (trainIdx + monoRight), -1 = none
+ *   d_right_to_left[(2r + 1)*capacity + j]  : out, mvRightToLeftMatch: the raw left index, -1 = none
+ *   d_depth[(2r)*capacity + i]              : out, mvDepth (-1 = none)
+ *   d_x3d[((2r)*capacity + i)*3 + {0,1,2}]  : out, mvStereo3Dpoints[i] in the left camera.  The reference leaves an empty cv::Mat where
+ *                 nothing matched: here that is zeros, VALID ONLY where d_left_to_right >= 0
+ *   d_n_matches[q]      : out, nMatches;   d_n_desc_matches[q] : out or NULL, descMatches (the rows that passed the ratio test)
+ * All capacity entries of the rows a rig owns are written on every call (-1, -1, -1.0f, zeros); the rows of the other eye in each array
+ * (d_left_to_right of frame 2r + 1, d_right_to_left, d_depth and d_x3d of the other frame) are not touched.  The layout is what
+ * orbx_search_by_projection_two_eyes_device reads.  mvuRight stays all -1 on this path (:1150): the caller's constant, not an output.
+ * The definitions (OpenCV is not available to this project: parity unpinned, as the cv::SVD ones):
+ *   * BFMatcher(NORM_HAMMING).knnMatch(left lapping rows, right lapping rows, 2) is OpenCV's batchDistance insertion over the right rows in
+ *     increasing index: a candidate enters only if strictly smaller than the current second and moves in front only if strictly smaller
+ *     than the first.  [0] is the FIRST index of the smallest distance, [1] the smallest remaining distance, which may equal [0]'s.  With
+ *     fewer than two right lapping rows nothing matches (size() >= 2).
+ *   * (*it)[0].distance < (*it)[1].distance * 0.7 (a float times a double, compared in double) equals 10*d0 < 7*d1 on every pair of
+ *     distances 0 .. 256 (enumerated by tests/test_stereo_fisheye.py); equal distances never pass.
+ *   * accepted when KannalaBrandt8::TriangulateMatches(mpCamera2, mvKeys[i], mvKeysRight[j], mRlr, mtlr, mvLevelSigma2[octave_i],
+ *     mvLevelSigma2[octave_j]) > 0.0001f, as orbx_kb8_triangulate_device computes it on both RAW points; NaN and -1 reject, +inf accepts.
+ *     An octave outside [0, nlevels) is CLAMPED into the table.
+ *   * the reference walks the left rows in increasing index: mvRightToLeftMatch[j] ends as the LARGEST accepted left row that chose j,
+ *     while each of them keeps its own mvLeftToRightMatch = j.  The two arrays are NOT inverse.
+ * No table depends on the capacity: there is no ORBX_ERR_UNSUPPORTED case.  ORBX_ERR_BAD_ARGUMENT is returned before any launch.
+ * Asynchronous on the handle's stream; no CPU path. */
+int orbx_stereo_fisheye_match_device(orbx_handle* h, int n_rigs, int rig_first, int rig_step, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                     const int* d_n_out, const int* d_mono_out, int capacity, const float* tlr12, const orbx_camera_kb8* cam_left,
+                                     const orbx_camera_kb8* cam_right, int nlevels, int* d_left_to_right, int* d_right_to_left, float* d_depth,
+                                     float* d_x3d, int* d_n_matches, int* d_n_desc_matches);
+
 /* ---- loop closing's matcher: the two Sim3 overloads of ORBmatcher::SearchByProjection ----------------------------------------------------
  * Where a MapPoint left the search (d_exit of orbx_search_by_projection_sim3_device); 0 .. 5 are orbx_fuse_exit's */
 enum orbx_sim3_search_exit {
@@ -968,6 +1006,11 @@ int orbx_debug_last_frame_two_eyes_stats(int* out4);
  * The read waits for the whole device (hipDeviceSynchronize), whatever stream the handle uses. */
 int orbx_debug_search_triangulation_two_eyes_enable(int on);
 int orbx_debug_search_triangulation_two_eyes_stats(int* out2);
+/* orbx_stereo_fisheye_match_device: the counter is kept only after orbx_debug_stereo_fisheye_enable(1) (process-wide; off by default, a launch
+ * then pays nothing for it).  The last counted launch, all rigs: out1[0] calls of KannalaBrandt8::TriangulateMatches (= d_n_desc_matches
+ * summed).  The read waits for the whole device (hipDeviceSynchronize), whatever stream the handle uses. */
+int orbx_debug_stereo_fisheye_enable(int on);
+int orbx_debug_stereo_fisheye_stats(int* out1);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
  * (the last one changes nothing), [1] requests of the last launch whose decision came from scanning the window again (every key of a
