@@ -1,7 +1,7 @@
 // orbx_internal.hpp - what the host files of liborbx.so share: the launch wrappers the kernel files define, the handle, the error / profiling
 // helpers.  orbx_api.cpp holds the extraction path (create, geometry installation, the launch sequence, the extract entry points, the pyramid),
 // orbx_rows.cpp the rows behind it (stereo matching, Frame finishing, the window searches, the vocabulary and ComputeBoW / SearchByBoW),
-// orbx_mapping_two_eyes.cpp Fuse on two-camera keyframes, orbx_debug.cpp the introspection, profiling and test aids.  The entry points' plain statements (predicates, parameter fills, padding rules) are
+// orbx_mapping_two_eyes.cpp Fuse on two-camera keyframes, orbx_mapping.cpp CreateNewMapPoints' triangulation on one-camera keyframes, orbx_debug.cpp the introspection, profiling and test aids.  The entry points' plain statements (predicates, parameter fills, padding rules) are
 // in orbx_entry.hpp, which needs no HIP; what they need of the handle or the runtime is at the end of this file.  Not installed: callers see
 // include/orbx.h only.
 #pragma once
@@ -42,6 +42,8 @@ void launchKb8Unproject(hipStream_t, const float*, const float*, int, float*);
 void launchKb8Triangulate(hipStream_t, const float*, const float*, const Kb8TriangulateParams&, float*, float*);
 int stereoFisheyeTiles(int capacity);
 void launchStereoFisheye(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const StereoFisheyeParams&, int*, int*, float*, float*, int*, int*, int);
+int newMapPointsTiles(int listCapacity);
+void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*, const Keypoint*, const Keypoint*, const float*, const float*, const int*, const NewMapPointsParams&, uint8_t*, float*, int*, uint8_t*, uint8_t*, int);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);

@@ -1,7 +1,8 @@
 // orbx_mapping_two_eyes.cpp - the C ABI of the mapping thread's matchers on TWO-CAMERA keyframes (NLeft != -1; include/orbx.h): the search half
 // of ORBmatcher::Fuse with bRight false and true (k_fuse_two_eyes.hip), SearchForTriangulation on such keyframes and the KannalaBrandt8
 // unprojection and triangulation it stands on (k_triangulate_match_two_eyes.hip), and the two-camera Frame constructor's
-// ComputeStereoFishEyeMatches, which stands on the same camera header (k_stereo_fisheye.hip).  Thin, as the entries of orbx_rows.cpp are: argument
+// ComputeStereoFishEyeMatches, which stands on the same camera header (k_stereo_fisheye.hip), and the two-camera form of CreateNewMapPoints'
+// triangulation loop (k_new_map_points.hip; its one-camera form is orbx_mapping.cpp).  Thin, as the entries of orbx_rows.cpp are: argument
 // checks, the parameter block, a memset of the counters asked for and one launch.  The checks and fills are orbx_entry.hpp's and
 // orbx_internal.hpp's.  A file of its own: tests/test_entry_rejections_gpu.py holds a table of exactly the *_device entries of orbx_rows.cpp,
 // and the rejections of the entries here are held by tests/test_fuse_two_eyes_gpu.py, tests/test_search_triangulation_two_eyes_gpu.py and
@@ -143,6 +144,38 @@ int orbx_stereo_fisheye_match_device(orbx_handle* h, int n_rigs, int rig_first, 
         Prof pr(h, S_FRAME);
         launchStereoFisheye(h->stream, (const Keypoint*)d_kps, d_desc, d_n_out, d_mono_out, p, d_left_to_right, d_right_to_left, d_depth, d_x3d,
                             d_n_matches, d_n_desc_matches, n_rigs);
+    }
+    return finishLaunch(h);
+}
+
+int orbx_create_new_map_points_two_eyes_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
+                                               const int* d_pairs, const int* d_n_matches, const float* d_poses, const float* tlr12,
+                                               const orbx_camera_kb8* cam_left, const orbx_camera_kb8* cam_right, const orbx_keypoint* d_kps,
+                                               const int* d_n_out, int capacity, int nlevels, int far_points, float th_far_points,
+                                               uint8_t* d_exit, float* d_x3d, int* d_n_new, uint8_t* d_mark1, uint8_t* d_mark2) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    // d_mark1 and d_mark2 may be NULL.  The grid folds the pairs into x: n_pairs times the workgroups of a pair has to fit a launch
+    if (!d_pairs || !d_n_matches || !d_poses || !tlr12 || !cam_left || !cam_right || !d_kps || !d_n_out || !d_exit || !d_x3d || !d_n_new ||
+        capacity < 1 || capacity > 0x3fffffff || n_pairs < 1 || negativeWalk(kf1_first, kf1_step, n_pairs) ||
+        negativeWalk(kf2_first, kf2_step, n_pairs) || (long long)n_pairs * newMapPointsTiles(2 * capacity) > 0x7fffffffLL)
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_pairs < 1, a negative rig index or more than 2^31 - 1 workgroups");
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    NewMapPointsParams p{};
+    fillKb8(p.cam[0], *cam_left);         // mpCamera, mpCamera2 of both keyframes (one rig)
+    fillKb8(p.cam[1], *cam_right);
+    levelsWholeTable(p.scale, h->tabs.scale);
+    levelsWholeTable(p.sigma2, h->tabs.sigma2);
+    for (int i = 0; i < 12; i++) p.tlr[i] = tlr12[i];
+    p.ratioFactor = 1.5f * h->scaleFactor;      // LocalMapping.cc:424, a float product
+    p.thFarPoints = th_far_points; p.farPoints = far_points ? 1 : 0; p.mono = 1;      // bStereo1 = bStereo2 = false (:490, :499)
+    p.nlevels = std::max(1, std::min(h->nlevels, (int)kMaxLevels));
+    p.capacity = capacity; p.listCapacity = 2 * capacity;
+    p.kf1First = kf1_first; p.kf1Step = kf1_step; p.kf2First = kf2_first; p.kf2Step = kf2_step;
+    {
+        Prof pr(h, S_FRAME);
+        launchNewMapPoints(h->stream, true, d_pairs, d_n_matches, d_poses, (const Keypoint*)d_kps, nullptr, nullptr, nullptr, d_n_out, p, d_exit,
+                           d_x3d, d_n_new, d_mark1, d_mark2, n_pairs);
     }
     return finishLaunch(h);
 }

@@ -149,6 +149,20 @@ struct StereoFisheyeParams {     // k_stereo_fisheye.hip
     int countStats;                                      // orbx_debug_stereo_fisheye_enable: add this launch's triangulations to g_stereoFisheyeStats
 };
 
+struct NewMapPointsParams {      // k_new_map_points.hip / k_new_map_points.hpp
+    float cam[2][8];                                     // two eyes: KannalaBrandt8::mvParameters of mpCamera / mpCamera2; one camera: cam[0][0..3] = fx, fy, cx, cy (Pinhole)
+    float scale[kMaxLevels], sigma2[kMaxLevels];         // mvScaleFactors, mvLevelSigma2 of the handle
+    float tlr[12];                                       // KeyFrame::mTlr, 3x4 row-major (two eyes)
+    float mb, mbf, thFarPoints;                          // pKF2->mb / mpCurrentKeyFrame->mb, mpCurrentKeyFrame->mbf, mThFarPoints (one rig has one of each)
+    float ratioFactor;                                   // 1.5f * mfScaleFactor, a float product
+    int nlevels, farPoints, mono;                        // mono: d_u_right is NULL, no feature is stereo
+    int capacity;                                        // keypoints per batch frame (per eye)
+    int listCapacity;                                    // entries of a pair's row of d_pairs / d_exit / d_x3d: capacity, or 2 * capacity for two eyes
+    int kf1First, kf1Step, kf2First, kf2Step;            // batch frames (one camera) or RIG keyframes (two eyes: device frames 2X, 2X + 1; one pose per rig)
+    int tiles;                                           // workgroups per pair: ceil(listCapacity / matches per workgroup)
+    int countStats;                                      // orbx_debug_new_map_points_enable: add this launch's counts to g_newMapPointsStats
+};
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

@@ -202,6 +202,12 @@ def load_library():
     L.orbx_stereo_fisheye_match_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.orbx_debug_stereo_fisheye_stats.argtypes = [ip]
     L.orbx_debug_stereo_fisheye_enable.argtypes = [C.c_int]
+    L.orbx_create_new_map_points_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
+                                                    C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, vp, vp, vp, vp, vp]
+    L.orbx_create_new_map_points_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                             C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
+    L.orbx_debug_new_map_points_stats.argtypes = [ip]
+    L.orbx_debug_new_map_points_enable.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -733,6 +739,42 @@ class ORBextractor:
         out = (C.c_int * 1)()
         self._check(self._L.orbx_debug_stereo_fisheye_stats(out))
         return out[0]
+
+    def create_new_map_points_device(self, n_pairs, kf1, kf2, d_pairs, d_n_matches, d_poses, cam, d_kps_un, d_kps, d_u_right, d_depth, d_n, capacity,
+                                     mb, mbf, d_exit, d_x3d, d_n_new, d_mark1=None, d_mark2=None, far_points=False, th_far_points=0.0,
+                                     nlevels=None):
+        """The triangulation loop of LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:481-707) for one-camera keyframes with the
+        Pinhole model, on the d_pairs / d_n_matches search_for_triangulation_device wrote; kf1 and kf2 = (first, step).  d_poses [f*12] per
+        batch frame; cam = camera(...) (fx, fy, cx, cy are read); d_u_right None = monocular (d_kps and d_depth may be None then).  d_exit
+        [p*capacity + k] holds the orbx_new_point_exit of match k, d_x3d [(p*capacity + k)*3] the world point (zeros on a rejection),
+        d_n_new [p] the accepted count; d_mark1 / d_mark2 (or None): flag rows [p*capacity + i] in which bit 0 of every accepted match's
+        keypoint is set."""
+        self._check(self._L.orbx_create_new_map_points_device(
+            self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], _dev(d_pairs), _dev(d_n_matches), _dev(d_poses), _host_f32(cam), _dev(d_kps_un),
+            _dev(d_kps), _dev(d_u_right), _dev(d_depth), _dev(d_n), capacity, self.nlevels if nlevels is None else nlevels, mb, mbf,
+            int(far_points), th_far_points, _dev(d_exit), _dev(d_x3d), _dev(d_n_new), _dev(d_mark1), _dev(d_mark2)))
+
+    def create_new_map_points_two_eyes_device(self, n_pairs, kf1, kf2, d_pairs, d_n_matches, d_poses, tlr, cam_left, cam_right, d_kps, d_n, capacity,
+                                              d_exit, d_x3d, d_n_new, d_mark1=None, d_mark2=None, far_points=False, th_far_points=0.0,
+                                              nlevels=None):
+        """The same loop for two-camera keyframes (NLeft != -1, a KannalaBrandt8 pair), on the stacked d_pairs / d_n_matches
+        search_for_triangulation_two_eyes_device wrote; kf1 and kf2 = (first, step) of the RIG keyframes.  The lists are 2 * capacity long:
+        d_exit [p*2*capacity + k], d_x3d [(p*2*capacity + k)*3]; the marks are [(2p + eye)*capacity + i]."""
+        self._check(self._L.orbx_create_new_map_points_two_eyes_device(
+            self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], _dev(d_pairs), _dev(d_n_matches), _dev(d_poses), _host_f32(tlr), _host_f32(cam_left),
+            _host_f32(cam_right), _dev(d_kps), _dev(d_n), capacity, self.nlevels if nlevels is None else nlevels, int(far_points), th_far_points,
+            _dev(d_exit), _dev(d_x3d), _dev(d_n_new), _dev(d_mark1), _dev(d_mark2)))
+
+    def new_map_points_count(self, on=True):
+        """switches the debug counters of the two create_new_map_points entries on or off (process-wide; off by default)"""
+        self._check(self._L.orbx_debug_new_map_points_enable(int(on)))
+
+    def new_map_points_stats(self):
+        """(matches that took the SVD branch, matches that took an UnprojectStereo branch) of the last counted launch, all pairs; waits
+        for the whole device."""
+        out = (C.c_int * 2)()
+        self._check(self._L.orbx_debug_new_map_points_stats(out))
+        return out[0], out[1]
 
     def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,

@@ -773,6 +773,102 @@ int orbx_stereo_fisheye_match_device(orbx_handle* h, int n_rigs, int rig_first, 
                                      const orbx_camera_kb8* cam_right, int nlevels, int* d_left_to_right, int* d_right_to_left, float* d_depth,
                                      float* d_x3d, int* d_n_matches, int* d_n_desc_matches);
 
+/* ---- the mapping thread's triangulation: the loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:481-707) --------------------------
+ * Between orbx_search_for_triangulation_device / orbx_search_for_triangulation_two_eyes_device, which write vMatchedIndices (d_pairs,
+ * d_n_matches), and orbx_fuse_device / orbx_fuse_two_eyes_device, which read MapPoint positions: every matched pair becomes a world point
+ * or is rejected, from reading vMatchedIndices[ikp] (:483) to the last `continue` of the scale-consistency test (:707).  The map-changing
+ * tail (:709-723: new MapPoint, AddObservation, ComputeDistinctiveDescriptors, UpdateNormalAndDepth) stays with the caller, as for Fuse, and
+ * so does the per-neighbour prelude (:436-456: baseline, median depth, ComputeF12): the caller passes only the pairs it wants.
+ * How a match left the loop (d_exit): three accepting codes name the branch that made the point, every `continue` has its own. */
+enum orbx_new_point_exit {
+    ORBX_NEW_POINT_TRIANGULATED = 0,     /* accepted; the linear triangulation (:593-611) */
+    ORBX_NEW_POINT_STEREO_1 = 1,         /* accepted; mpCurrentKeyFrame->UnprojectStereo(idx1) (:614) */
+    ORBX_NEW_POINT_STEREO_2 = 2,         /* accepted; pKF2->UnprojectStereo(idx2) (:618) */
+    ORBX_NEW_POINT_ZERO_W = 3,           /* x3D.at<float>(3) == 0 (:605) */
+    ORBX_NEW_POINT_LOW_PARALLAX = 4,     /* no stereo and very low parallax (:622); a NaN pose ends here */
+    ORBX_NEW_POINT_EMPTY_STEREO = 5,     /* x3Dt.empty() (:627): UnprojectStereo with mvDepth <= 0 */
+    ORBX_NEW_POINT_BEHIND_1 = 6,         /* z1 <= 0 (:630) */
+    ORBX_NEW_POINT_BEHIND_2 = 7,         /* z2 <= 0 (:634) */
+    ORBX_NEW_POINT_REPROJ_1 = 8,         /* the reprojection error in the first keyframe (:649 / :661) */
+    ORBX_NEW_POINT_REPROJ_2 = 9,         /* ... in the second (:675 / :686) */
+    ORBX_NEW_POINT_ZERO_DIST = 10,       /* dist1 == 0 || dist2 == 0 (:697) */
+    ORBX_NEW_POINT_FAR = 11,             /* mbFarPoints && a distance >= mThFarPoints (:700) */
+    ORBX_NEW_POINT_SCALE = 12,           /* the scale-consistency test (:706) */
+    ORBX_NEW_POINT_BAD_INDEX = 13        /* an index outside its keyframe's [0, N): nothing is read (the reference would index out of bounds) */
+};
+
+/* One-camera keyframes (NLeft == -1, no mpCamera2; monocular, rectified stereo, RGB-D) with the Pinhole model.  Pair p triangulates the
+ * matches of keyframe 1 = frame kf1_first + p*kf1_step and keyframe 2 = frame kf2_first + p*kf2_step, numbered as
+ * orbx_search_for_triangulation_device numbers them; kf1_step = 0 is LocalMapping's shape.
+ *   d_pairs[(p*capacity + k)*2 + {0, 1}], d_n_matches[p] : exactly what the search wrote; d_n_matches[p] is clamped into [0, capacity]
+ *   d_poses[f*12]   : Tcw of batch frame f, 3x4 row-major.  Rwc = Rcw.t(), Ow = -Rwc*tcw and Twc = [Rwc | Ow] are derived on the device
+ *                     (src/KeyFrame.cc:111-125) as cv::gemm rows
+ *   cam             : fx, fy, cx, cy (host); Pinhole::unproject / project are src/CameraModels/Pinhole.cpp:59-62, :30-33.  The distortion
+ *                     fields are not read: mvKeysUn are undistorted
+ *   d_kps_un[f*capacity + i] : mvKeysUn of all frames; .pt and .octave are read
+ *   d_kps[f*capacity + i]    : the RAW mvKeys; read only by UnprojectStereo (src/KeyFrame.cc:821-834, which uses mvKeys, not mvKeysUn)
+ *   d_u_right, d_depth [f*capacity + i] : mvuRight, mvDepth as orbx_stereo_match_device / orbx_stereo_from_rgbd_device write them.  NULL
+ *                     d_u_right = monocular: no feature is stereo, and d_kps / d_depth may be NULL then (and only then)
+ *   d_n_out[f]      : N of all frames, clamped into [0, capacity]
+ *   mb, mbf         : the reference reads pKF2->mb for the second keyframe and mpCurrentKeyFrame->mb / ->mbf for the first and for BOTH
+ *                     gates (:583, :585, :656, :681); the keyframes of one call are one rig's, which has one of each
+ *   far_points, th_far_points : mbFarPoints, mThFarPoints;  nlevels : the handle's.  mvScaleFactors / mvLevelSigma2 are the handle's,
+ *                     ratioFactor = 1.5f * the handle's scale factor in binary32 (:424); an octave outside [0, nlevels) is CLAMPED
+ *   d_exit[p*capacity + k]              : out, orbx_new_point_exit of match k < d_n_matches[p], in the order of d_pairs
+ *   d_x3d[(p*capacity + k)*3 + {0,1,2}] : out, the world point; ZEROS on every rejecting exit
+ *   d_n_new[p]      : out, the accepted matches of pair p (a pair named twice in one call gives the same count twice)
+ *   d_mark1 / d_mark2 : NULL, or flag rows laid out like d_kf1_mp_flags / d_kf2_mp_flags of the search ([p*capacity + i]): for every
+ *                     accepted match bit 0 of the entry of idx1 / idx2 is SET; nothing is ever cleared.  The bit is set with an atomic OR
+ *                     on the containing 32-bit word: the arrays start 4-byte aligned and their length is a multiple of 4 bytes
+ * Entries of d_exit / d_x3d from d_n_matches[p] on are left as they were, as d_pairs is.
+ * The marks serve the reference's walk over the neighbours: a keypoint that received a MapPoint from neighbour i is skipped by the search
+ * of neighbour i + 1 (src/ORBmatcher.cc:1033-1039).  A caller that wants exactly that runs search and triangulation with n_pairs = 1 per
+ * neighbour on the handle's stream and passes the flag row the next search reads as d_mark1; a batched call
+ * (n_pairs > 1) is the approximation in which all neighbours see the flags of before.
+ * What is kept of the reference, each asserted by tests/test_new_map_points.py against the sequential walk:
+ *   * bStereo1 = mvuRight[idx1] >= 0, bStereo2 likewise (:490, :499); pose and camera are the keyframes' own for every match;
+ *   * cosParallaxRays = ray1.dot(ray2) / (norm(ray1)*norm(ray2)) in double, rounded to float once; ray = Rwc*xn one cv::gemm row each;
+ *   * cosParallaxStereo = cosParallaxRays + 1 in float; cosParallaxStereo1 is replaced if bStereo1, ELSE IF bStereo2
+ *     cosParallaxStereo2: with both stereo only the first is (:582-585).  cos(2*atan2(mb/2, depth)) is binary32 throughout (`using namespace
+ *     std` is in scope through TemplatedVocabulary.h:36: the float overloads), as glibc's atan2f and cosf evaluate it;
+ *   * the branch test (:590-591): cosParallaxRays < cosParallaxStereo compares floats, > 0 an int, < 0.9998 compares in double; mbInertial
+ *     changes nothing, both alternatives are the same test;
+ *   * A's rows are xn.x*Tcw.row(2) - Tcw.row(0) etc., each product and difference rounded in float; vt.row(3) is the library's own Jacobi
+ *     (orbx_kb8_triangulate_device); x3D[3] == 0 is an explicit exit here; x3D = v[0..2] / v[3] a float division per element;
+ *   * UnprojectStereo: (u - cx)*z*invfx rounded per operation in float with invfx = 1.0f / fx, Twc.R*x3Dc + Twc.t one cv::gemm row per element;
+ *   * z1, x1, y1 ... = Rcw.row(r).dot(x3Dt) + tcw[r]: products and sums in double, rounded to float once; invz = 1.0 / z in double, rounded;
+ *   * the monocular gate is > 5.991*sigma2, the stereo gate > 7.8*sigma2 with the third error u - mbf*invz - kp_ur; both compare in double;
+ *   * dist = (float)cv::norm(x3D - Ow), the difference in float, the norm in double; dist == 0 rejects;
+ *   * ratioDist*ratioFactor < ratioOctave || ratioDist > ratioOctave*ratioFactor, all in float.
+ * The cv::Mat roundings are the library's definitions (parity unpinned).  No table depends on the capacity: there is
+ * no ORBX_ERR_UNSUPPORTED case; ORBX_ERR_BAD_ARGUMENT is returned before any launch.  Asynchronous on the handle's stream; no CPU path. */
+int orbx_create_new_map_points_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step, const int* d_pairs,
+                                      const int* d_n_matches, const float* d_poses, const orbx_camera* cam, const orbx_keypoint* d_kps_un,
+                                      const orbx_keypoint* d_kps, const float* d_u_right, const float* d_depth, const int* d_n_out,
+                                      int capacity, int nlevels, float mb, float mbf, int far_points, float th_far_points, uint8_t* d_exit,
+                                      float* d_x3d, int* d_n_new, uint8_t* d_mark1, uint8_t* d_mark2);
+
+/* Two-camera keyframes (NLeft != -1, mpCamera2 on both sides, a KannalaBrandt8 pair).  Rig keyframes, batch frames 2X / 2X + 1 and the
+ * stacked numbering (a right keypoint j is NLeft + j, NLeft = d_n_out[2X]) as orbx_search_for_triangulation_two_eyes_device.
+ *   d_pairs[(p*2*capacity + k)*2 + {0, 1}], d_n_matches[p] : exactly what that search wrote; d_n_matches[p] is clamped into [0, 2*capacity]
+ *   d_poses[X*12], tlr12, cam_left, cam_right, d_kps (the RAW keypoints of both eyes; .pt and .octave are read), d_n_out : as there
+ *   d_exit[p*2*capacity + k], d_x3d[(p*2*capacity + k)*3 + {0,1,2}], d_n_new[p] : out, as above
+ *   d_mark1 / d_mark2 : NULL, or flag rows laid out like that search's d_kf1_mp_flags / d_kf2_mp_flags ([(2p + eye)*capacity + i])
+ * What differs from the one-camera form:
+ *   * pose and camera are RE-PICKED PER MATCH from bRight1 = idx1 >= NLeft1 and bRight2 (:503-568): GetRotation / GetTranslation / GetPose /
+ *     GetCameraCenter and mpCamera, or GetRightRotation / GetRightTranslation / GetRightPose / GetRightCameraCenter
+ *     (src/KeyFrame.cc:1232-1262, from mTlr alone, as orbx_fuse_two_eyes_device derives them) and mpCamera2.  All four branches assign
+ *     everything, so nothing carries over from the match before;
+ *   * bStereo1 = bStereo2 = false always (:490, :499: mpCamera2 is set): no stereo branch, no stereo gate, STEREO_1 / STEREO_2 /
+ *     EMPTY_STEREO never appear; mb and mbf are not inputs;
+ *   * unproject / project are KannalaBrandt8's (orbx_kb8_unproject_device, orbx_kb8_project_device).
+ * Asynchronous on the handle's stream; no CPU path. */
+int orbx_create_new_map_points_two_eyes_device(orbx_handle* h, int n_pairs, int kf1_first, int kf1_step, int kf2_first, int kf2_step,
+                                               const int* d_pairs, const int* d_n_matches, const float* d_poses, const float* tlr12,
+                                               const orbx_camera_kb8* cam_left, const orbx_camera_kb8* cam_right, const orbx_keypoint* d_kps,
+                                               const int* d_n_out, int capacity, int nlevels, int far_points, float th_far_points,
+                                               uint8_t* d_exit, float* d_x3d, int* d_n_new, uint8_t* d_mark1, uint8_t* d_mark2);
+
 /* ---- loop closing's matcher: the two Sim3 overloads of ORBmatcher::SearchByProjection ----------------------------------------------------
  * Where a MapPoint left the search (d_exit of orbx_search_by_projection_sim3_device); 0 .. 5 are orbx_fuse_exit's */
 enum orbx_sim3_search_exit {
@@ -1011,6 +1107,11 @@ int orbx_debug_search_triangulation_two_eyes_stats(int* out2);
  * summed).  The read waits for the whole device (hipDeviceSynchronize), whatever stream the handle uses. */
 int orbx_debug_stereo_fisheye_enable(int on);
 int orbx_debug_stereo_fisheye_stats(int* out1);
+/* orbx_create_new_map_points_device / _two_eyes_device: the counters are kept only after orbx_debug_new_map_points_enable(1) (process-wide;
+ * off by default, a launch then pays nothing for them).  The last counted launch, all pairs: out2[0] matches that took the SVD branch
+ * (:590-611), out2[1] matches that took an UnprojectStereo branch (:612-619).  The read waits for the whole device. */
+int orbx_debug_new_map_points_enable(int on);
+int orbx_debug_new_map_points_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
  * (the last one changes nothing), [1] requests of the last launch whose decision came from scanning the window again (every key of a
