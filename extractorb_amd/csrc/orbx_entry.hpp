@@ -25,6 +25,9 @@ inline bool negativeFirstOrStep(int first, int step) { return first < 0 || step 
 // orbx_fuse_two_eyes_device's `eyes`: bit 0 the left search, bit 1 the right; the loop-closing overload (reproj_check = 0) has no right-eye form
 inline bool badFuseEyes(int eyes, int reprojCheck) { return eyes < 1 || eyes > 3 || (!reprojCheck && eyes != 1); }
 
+// orbx_update_map_points*_device's `what`: bit 0 the descriptor, bit 1 normal and depth; one of them at least, nothing else
+inline bool badUpdateWhat(int what) { return what < 1 || what > 3; }
+
 // ---- limits -----------------------------------------------------------------------------------------------------------------------
 constexpr size_t kLdsBudget = 160 * 1024 - 512;      // dynamic + static LDS a workgroup of the LDS-resident searches may ask for (160 KB per CU)
 inline bool fitsLds(size_t bytes) { return bytes <= kLdsBudget; }

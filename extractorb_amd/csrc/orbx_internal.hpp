@@ -44,6 +44,7 @@ int stereoFisheyeTiles(int capacity);
 void launchStereoFisheye(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const StereoFisheyeParams&, int*, int*, float*, float*, int*, int*, int);
 int newMapPointsTiles(int listCapacity);
 void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*, const Keypoint*, const Keypoint*, const float*, const float*, const int*, const NewMapPointsParams&, uint8_t*, float*, int*, uint8_t*, uint8_t*, int);
+void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const MapPointUpdateParams&);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);

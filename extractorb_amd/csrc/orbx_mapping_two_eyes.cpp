@@ -2,7 +2,8 @@
 // of ORBmatcher::Fuse with bRight false and true (k_fuse_two_eyes.hip), SearchForTriangulation on such keyframes and the KannalaBrandt8
 // unprojection and triangulation it stands on (k_triangulate_match_two_eyes.hip), and the two-camera Frame constructor's
 // ComputeStereoFishEyeMatches, which stands on the same camera header (k_stereo_fisheye.hip), and the two-camera form of CreateNewMapPoints'
-// triangulation loop (k_new_map_points.hip; its one-camera form is orbx_mapping.cpp).  Thin, as the entries of orbx_rows.cpp are: argument
+// triangulation loop (k_new_map_points.hip; its one-camera form is orbx_mapping.cpp), and the two-camera form of the MapPoint update
+// (k_map_point_update.hip; tests/test_map_point_update_gpu.py holds its rejections).  Thin, as the entries of orbx_rows.cpp are: argument
 // checks, the parameter block, a memset of the counters asked for and one launch.  The checks and fills are orbx_entry.hpp's and
 // orbx_internal.hpp's.  A file of its own: tests/test_entry_rejections_gpu.py holds a table of exactly the *_device entries of orbx_rows.cpp,
 // and the rejections of the entries here are held by tests/test_fuse_two_eyes_gpu.py, tests/test_search_triangulation_two_eyes_gpu.py and
@@ -176,6 +177,33 @@ int orbx_create_new_map_points_two_eyes_device(orbx_handle* h, int n_pairs, int 
         Prof pr(h, S_FRAME);
         launchNewMapPoints(h->stream, true, d_pairs, d_n_matches, d_poses, (const Keypoint*)d_kps, nullptr, nullptr, nullptr, d_n_out, p, d_exit,
                            d_x3d, d_n_new, d_mark1, d_mark2, n_pairs);
+    }
+    return finishLaunch(h);
+}
+
+int orbx_update_map_points_two_eyes_device(orbx_handle* h, int n_points, const int* d_obs_off, const int* d_obs, const uint8_t* d_obs_flags,
+                                           const int* d_ref, const int* d_slot, const float* d_mp_world, const float* d_poses,
+                                           const float* tlr12, int n_rigs, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                           const int* d_n_out, int capacity, int nlevels, int what, uint8_t* d_mp_desc, float* d_mp_normal,
+                                           float* d_mp_dist, int* d_best, int* d_best_median, uint8_t* d_status) {
+    if (!h) return ORBX_ERR_BAD_ARGUMENT;
+    // d_obs_flags and d_slot may be NULL
+    if (!d_obs_off || !d_obs || !d_ref || !d_mp_world || !d_poses || !tlr12 || !d_kps || !d_desc || !d_n_out || !d_mp_desc || !d_mp_normal ||
+        !d_mp_dist || !d_best || !d_best_median || !d_status || capacity < 1 || n_rigs < 1 || n_rigs > 0x3fffffff || n_points < 0 ||
+        badUpdateWhat(what))
+        return fail(h, ORBX_ERR_BAD_ARGUMENT, "null pointer, capacity/n_rigs < 1, negative n_points or what outside 1 .. 3");
+    if (int rc = sameLevels(h, nlevels)) return rc;
+    if (n_points == 0) return ORBX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    MapPointUpdateParams p{};
+    levelsOnly(p.scale, h->tabs.scale, h->nlevels);
+    for (int i = 0; i < 12; i++) p.tlr[i] = tlr12[i];
+    p.nlevels = h->nlevels; p.capacity = capacity; p.nFrames = 2 * n_rigs; p.nPoints = n_points; p.what = what;
+    const MapPointUpdateArrays a{d_obs_off, d_obs, d_obs_flags, d_ref, d_slot, d_mp_world, d_poses, (const Keypoint*)d_kps, d_desc, d_n_out,
+                                 d_mp_desc, d_mp_normal, d_mp_dist, d_best, d_best_median, d_status};
+    {
+        Prof pr(h, S_FRAME);
+        launchMapPointUpdate(h->stream, true, a, p);
     }
     return finishLaunch(h);
 }

@@ -163,6 +163,19 @@ struct NewMapPointsParams {      // k_new_map_points.hip / k_new_map_points.hpp
     int countStats;                                      // orbx_debug_new_map_points_enable: add this launch's counts to g_newMapPointsStats
 };
 
+struct MapPointUpdateParams {    // k_map_point_update.hip / k_map_point_update.hpp
+    float scale[kMaxLevels];                             // mvScaleFactors of the handle
+    float tlr[12];                                       // KeyFrame::mTlr, 3x4 row-major (two eyes)
+    int nlevels, capacity;                               // capacity: keypoints per batch frame (per eye)
+    int nFrames;                                         // device frames of the batch (two eyes: 2 * rigs); an observation outside is BAD_INDEX
+    int nPoints, what;                                   // what: bit 0 the descriptor, bit 1 normal and depth
+};
+struct MapPointUpdateArrays {    // the arrays of orbx_update_map_points*_device, as the entry was given them
+    const int* obsOff; const int* obs; const uint8_t* obsFlags; const int* ref; const int* slot;
+    const float* mpWorld; const float* poses; const Keypoint* kps; const uint8_t* desc; const int* nOut;
+    uint8_t* mpDesc; float* mpNormal; float* mpDist; int* best; int* bestMedian; uint8_t* status;
+};
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

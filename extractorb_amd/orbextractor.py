@@ -207,6 +207,10 @@ def load_library():
     L.orbx_create_new_map_points_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                                              C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     L.orbx_debug_new_map_points_stats.argtypes = [ip]
+    L.orbx_update_map_points_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp,
+                                                vp, vp, vp, vp]
+    L.orbx_update_map_points_two_eyes_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int,
+                                                         C.c_int, vp, vp, vp, vp, vp, vp]
     L.orbx_debug_new_map_points_enable.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
@@ -764,6 +768,33 @@ class ORBextractor:
             self._h, n_pairs, kf1[0], kf1[1], kf2[0], kf2[1], _dev(d_pairs), _dev(d_n_matches), _dev(d_poses), _host_f32(tlr), _host_f32(cam_left),
             _host_f32(cam_right), _dev(d_kps), _dev(d_n), capacity, self.nlevels if nlevels is None else nlevels, int(far_points), th_far_points,
             _dev(d_exit), _dev(d_x3d), _dev(d_n_new), _dev(d_mark1), _dev(d_mark2)))
+
+    def update_map_points_device(self, n_points, d_obs_off, d_obs, d_obs_flags, d_ref, d_slot, d_mp_world, d_poses, n_frames, d_kps_un, d_desc,
+                                 d_n, capacity, d_mp_desc, d_mp_normal, d_mp_dist, d_best, d_best_median, d_status, what=3, nlevels=None):
+        """MapPoint::ComputeDistinctiveDescriptors (what bit 0) and MapPoint::UpdateNormalAndDepth (what bit 1; reference src/MapPoint.cc:330-403,
+        :427-494) for n_points listed MapPoints over one-camera keyframes.  d_obs_off [n_points + 1] is a CSR over d_obs [o*2] = (device frame,
+        keypoint row), one entry per descriptor in the reference's iteration order of mObservations; d_obs_flags (or None) bit 0 =
+        pKF->isBad(), left out of the descriptor but counted in the normal; d_ref [m] the position of mpRefKF's entry in the list; d_slot
+        (or None = m) the row of the MapPoint tables the point reads (d_mp_world) and writes (d_mp_desc [slot*32], d_mp_normal [slot*3],
+        d_mp_dist [slot*3] = fuse_device's triple).  d_poses [f*12] of the n_frames batch frames; d_kps_un: only the octave is read.
+        d_best [m] holds BestIdx among the entries that took part (-1: none), d_best_median [m] its median, d_status [m] an
+        orbx_map_point_update (0 OK, 1 EMPTY, 2 NO_DESCRIPTOR, 3 BAD_INDEX, 4 TOO_LONG: more than MAX_OBSERVATIONS entries)."""
+        self._check(self._L.orbx_update_map_points_device(
+            self._h, n_points, _dev(d_obs_off), _dev(d_obs), _dev(d_obs_flags), _dev(d_ref), _dev(d_slot), _dev(d_mp_world), _dev(d_poses), n_frames,
+            _dev(d_kps_un), _dev(d_desc), _dev(d_n), capacity, self.nlevels if nlevels is None else nlevels, int(what), _dev(d_mp_desc),
+            _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_best), _dev(d_best_median), _dev(d_status)))
+
+    def update_map_points_two_eyes_device(self, n_points, d_obs_off, d_obs, d_obs_flags, d_ref, d_slot, d_mp_world, d_poses, tlr, n_rigs, d_kps,
+                                          d_desc, d_n, capacity, d_mp_desc, d_mp_normal, d_mp_dist, d_best, d_best_median, d_status, what=3,
+                                          nlevels=None):
+        """The same update for two-camera keyframes (NLeft != -1): rig keyframe r is device frames 2r, 2r + 1 (fuse_two_eyes_device's
+        layout), d_poses [r*12] per rig, tlr = mTlr (3x4), d_kps the RAW keypoints.  A right keypoint NLeft + j is the entry (2r + 1, j);
+        a keyframe with both indices gives its left entry, then its right entry.  d_ref names the left entry of mpRefKF if it has one, else
+        the right; the reference centre is the rig's LEFT centre either way."""
+        self._check(self._L.orbx_update_map_points_two_eyes_device(
+            self._h, n_points, _dev(d_obs_off), _dev(d_obs), _dev(d_obs_flags), _dev(d_ref), _dev(d_slot), _dev(d_mp_world), _dev(d_poses),
+            _host_f32(tlr), n_rigs, _dev(d_kps), _dev(d_desc), _dev(d_n), capacity, self.nlevels if nlevels is None else nlevels, int(what),
+            _dev(d_mp_desc), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_best), _dev(d_best_median), _dev(d_status)))
 
     def new_map_points_count(self, on=True):
         """switches the debug counters of the two create_new_map_points entries on or off (process-wide; off by default)"""

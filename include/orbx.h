@@ -869,6 +869,86 @@ int orbx_create_new_map_points_two_eyes_device(orbx_handle* h, int n_pairs, int 
                                                const int* d_n_out, int capacity, int nlevels, int far_points, float th_far_points,
                                                uint8_t* d_exit, float* d_x3d, int* d_n_new, uint8_t* d_mark1, uint8_t* d_mark2);
 
+/* ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:330-403) and MapPoint::UpdateNormalAndDepth (:427-494) on observation lists:
+ * the last link between "a point was made or fused" and "the next search reads it".  The mapping thread calls both on every new point
+ * (src/LocalMapping.cc:718-720), on every tracked point of a new keyframe (:317-318), on every point of the current keyframe after fusing
+ * (:829-830) and on the survivor of every Replace (src/MapPoint.cc:298); the optimizer calls the second alone after every bundle
+ * adjustment.  Both are pure functions of the observation list, the observing keyframes' descriptors, poses and one keypoint octave, all of
+ * which live on the device; what they write are exactly the rows orbx_fuse*_device, orbx_frustum_requests*_device and the projection
+ * searches read.  The bookkeeping (who observes what, who survived, mpRefKF) stays with the caller, who supplies it as lists.
+ * The longest list the entries take.  1024 descriptors are 32 KB of LDS, so that several workgroups fit on a CU: a CHOICE, not a
+ * measurement.  A longer list is refused per point (ORBX_MAP_POINT_TOO_LONG) and stays with the host. */
+#define ORBX_MAX_OBSERVATIONS 1024
+
+/* How a listed MapPoint left the update (d_status) */
+enum orbx_map_point_update {
+    ORBX_MAP_POINT_OK = 0,
+    ORBX_MAP_POINT_EMPTY = 1,          /* N == 0: the early returns of :344 / :442.  No table row is written */
+    ORBX_MAP_POINT_NO_DESCRIPTOR = 2,  /* every entry's keyframe isBad() (:366): the descriptor row is untouched; normal and depth ARE written */
+    ORBX_MAP_POINT_BAD_INDEX = 3,      /* a frame outside the batch, a row outside [0, N_f), d_ref[m] outside the list, a negative d_obs_off[m]
+                                          or d_slot[m]: the reference would index out of bounds.  No table row is written */
+    ORBX_MAP_POINT_TOO_LONG = 4        /* N > ORBX_MAX_OBSERVATIONS.  No table row is written */
+};
+
+/* One-camera keyframes (NLeft == -1).  For n_points MapPoints:
+ *   d_obs_off[n_points + 1] : a CSR over observations; MapPoint m owns the entries [d_obs_off[m], d_obs_off[m+1]) of d_obs; its length N is
+ *                 clamped at 0 from below
+ *   d_obs[o*2 + {0,1}]      : (device frame, keypoint row in that frame), ONE ENTRY PER DESCRIPTOR, in the reference's iteration order of
+ *                 mObservations - the order of std::map<KeyFrame*, ...>, which is the caller's to supply.  BestIdx' tie rule and the
+ *                 rounding of the normal's sum depend on it
+ *   d_obs_flags[o]          : or NULL (no flag set); bit 0 = pKF->isBad().  Such an entry is left out of the descriptor selection (:353) but IS
+ *                 counted in the normal: UpdateNormalAndDepth has no such test
+ *   d_ref[m]                : the position within MapPoint m's list of the observation in mpRefKF, whose keypoint gives `level` (:471-482)
+ *   d_slot[m]               : or NULL (= m); the row of the MapPoint tables this point reads (d_mp_world) and writes, so that only changed points
+ *                 need to be listed.  Rows no listed point names are never touched.  Two listed points must not name one row
+ *   d_mp_world[slot*3]      : GetWorldPos(), as orbx_fuse_device takes it
+ *   d_poses[f*12], n_frames : Tcw (3x4 row-major) of the n_frames frames of the batch; Ow = -Rcw.t()*tcw is computed here
+ *   d_kps_un[f*capacity + i]: mvKeysUn; only the octave of the reference entry's keypoint is read (:475)
+ *   d_desc, d_n_out, capacity : mDescriptors and N of all frames; d_n_out[f] is clamped into [0, capacity]
+ *   nlevels                 : must equal orbx_get_levels(h): mvScaleFactors are the handle's
+ *   what                    : bit 0 = the descriptor, bit 1 = normal and depth; 1, 2 or 3, anything else is ORBX_ERR_BAD_ARGUMENT.  The rows of a
+ *                 half not asked for are not touched
+ *   d_mp_desc[slot*32]      : out, mDescriptor (16-byte aligned)
+ *   d_mp_normal[slot*3]     : out, mNormalVector
+ *   d_mp_dist[slot*3]       : out, orbx_fuse_device's triple: 0.8f*mfMinDistance, 1.2f*mfMaxDistance, mfMaxDistance
+ *   d_best[m]               : out, BestIdx as a position in the list counting only the entries that took part; -1 where no descriptor was
+ *                 chosen (what without bit 0 included)
+ *   d_best_median[m]        : out, BestMedian; -1 beside d_best = -1
+ *   d_status[m]             : out, an orbx_map_point_update.  d_best, d_best_median and d_status are written for EVERY listed point
+ * Every entry of a list is checked (flagged ones as well, and whatever `what` asks for) before anything of the point is written.  What the
+ * entry cannot check is the caller's: d_obs holds d_obs_off[n_points] entries and the tables hold every row d_slot names.
+ * THE DESCRIPTOR HALF is integers, bit-exact against the reference: Distances[i][i] = 0, DescriptorDistance elsewhere; median =
+ * sorted(row)[int(0.5*(N-1))], the element of rank (N-1)/2 of the N values with the row's own 0 among them (N = 1 and N = 2 give 0); BestIdx
+ * the FIRST row with the smallest median (strict <, :393); the output is a copy of that row's 32 bytes.
+ * THE NORMAL AND DEPTH HALF is cv::Mat arithmetic, the library's definitions (parity unpinned): normali = Pos - Owi a
+ * float subtraction per element; cv::norm the sum of squares and the root in double; normal + normali/norm is cv::scaleAdd, normal[c] =
+ * normali[c]*(float)(1.0/norm) + normal[c] with both operations rounded in float, accumulated SEQUENTIALLY in list order; normal/n =
+ * normal[c]*(float)(1.0/(double)n); dist = (float)cv::norm(Pos - Ow_ref); mfMaxDistance = dist*mvScaleFactors[level], mfMinDistance =
+ * mfMaxDistance/mvScaleFactors[nlevels-1], the invariance bounds their products with 0.8f and 1.2f, all float operations.  An octave outside
+ * [0, nlevels) is CLAMPED into the table.
+ * ORBX_ERR_BAD_ARGUMENT (a NULL pointer other than d_obs_flags / d_slot, capacity or n_frames < 1, negative n_points, `what`, nlevels) is
+ * returned before any launch; n_points = 0 does nothing.  Asynchronous on the handle's stream; no CPU path. */
+int orbx_update_map_points_device(orbx_handle* h, int n_points, const int* d_obs_off, const int* d_obs, const uint8_t* d_obs_flags,
+                                  const int* d_ref, const int* d_slot, const float* d_mp_world, const float* d_poses, int n_frames,
+                                  const orbx_keypoint* d_kps_un, const uint8_t* d_desc, const int* d_n_out, int capacity, int nlevels, int what,
+                                  uint8_t* d_mp_desc, float* d_mp_normal, float* d_mp_dist, int* d_best, int* d_best_median, uint8_t* d_status);
+
+/* Two-camera keyframes (NLeft != -1).  Rig keyframe r is device frames 2r (left eye) and 2r + 1 (right eye), d_poses[r*12] holds one pose
+ * per rig and tlr12 is mTlr, exactly as orbx_fuse_two_eyes_device lays them out; n_rigs rigs make 2*n_rigs device frames.  What differs:
+ *   d_obs     : a right keypoint NLeft + j is (2r + 1, j).  For a rig keyframe with both indices set the caller writes the left entry and
+ *               then the right entry (:357-362, :454-465)
+ *   centres   : an entry of frame 2r counts GetCameraCenter(), one of frame 2r + 1 GetRightCameraCenter() = Rwl*mTlr.t + Ow (one cv::gemm
+ *               row with the float Ow as addend, src/KeyFrame.cc:1232-1240), as orbx_fuse_two_eyes_device derives it
+ *   d_ref[m]  : the left entry of mpRefKF if leftIndex != -1, otherwise its right entry (:477-482).  The reference centre is ALWAYS
+ *               GetCameraCenter(), the LEFT centre of that entry's rig (:468), also for a right entry
+ *   d_kps     : the RAW keypoints of both eyes (mvKeys / mvKeysRight, :478, :481); only the reference entry's octave is read
+ * Everything else as above. */
+int orbx_update_map_points_two_eyes_device(orbx_handle* h, int n_points, const int* d_obs_off, const int* d_obs, const uint8_t* d_obs_flags,
+                                           const int* d_ref, const int* d_slot, const float* d_mp_world, const float* d_poses,
+                                           const float* tlr12, int n_rigs, const orbx_keypoint* d_kps, const uint8_t* d_desc,
+                                           const int* d_n_out, int capacity, int nlevels, int what, uint8_t* d_mp_desc, float* d_mp_normal,
+                                           float* d_mp_dist, int* d_best, int* d_best_median, uint8_t* d_status);
+
 /* ---- loop closing's matcher: the two Sim3 overloads of ORBmatcher::SearchByProjection ----------------------------------------------------
  * Where a MapPoint left the search (d_exit of orbx_search_by_projection_sim3_device); 0 .. 5 are orbx_fuse_exit's */
 enum orbx_sim3_search_exit {
