@@ -17,13 +17,6 @@ const char* const kSlotNames[ORBX_NUM_KERNELS] = {"k_pyr_first", "k_resize", "k_
 thread_local std::string g_createError;
 
 namespace {
-// The automatic split level of the per-keypoint blur (installGeometry): k_blur takes the levels whose patches hold more than kSplitRatioNum /
-// kSplitRatioDen of the level's pixels.  Measured (round 6, A/B in one call, us per step): 512 x 640x480 x 1000 - no split 1696-1699, split at level
-// 2 (patches 1.36 of the level) 1667-1668, at 3 (1.63) 1656-1666, at 4 (1.96) 1664-1674, at 5 1674-1680, k_blur for every level 1707-1710; 128 x
-// 1080p x 2000, where the coarsest level's patches reach 0.99 of it: no split 2290, at 7 2316-2321, at 6 2318-2331, at 4 2355-2367 - so the
-// levels past 1.5.
-constexpr int kSplitRatioNum = 3, kSplitRatioDen = 2;
-
 void freeAll(orbx_handle* h) {
     void* dev[] = {h->d_input, h->d_pyr, h->d_blur, h->d_candPos, h->d_candSeg, h->d_cellCount, h->d_cellOff, h->d_nodeOf, h->d_candCount, h->d_sink, h->d_sel, h->d_levelCount,
                    h->d_levelLap, h->d_lap, h->d_lv, h->d_cells, h->d_rx, h->d_ry, h->d_xq, h->d_cols, h->d_colLevels, h->d_colCoef, h->d_foot, h->d_tiles, h->d_laneItem, h->d_out,
@@ -92,7 +85,7 @@ int installGeometry(orbx_handle* h, int rows, int cols) {
             qo += g.xq[l].size();
         }
     }
-    if (h->leafFrames) {      // x / y path codes of every level the quad-tree's dense phase covers (k_octree_body.inc: `dense`)
+    if (h->launch.leafFrames) {      // x / y path codes of every level the quad-tree's dense phase covers (k_octree_body.inc: `dense`)
         std::vector<uint8_t> code((size_t)2 * g.nlevels * h->octXT, 0);
         for (int l = 0; l < g.nlevels; l++) {
             LevelGeom& L = g.lv[l];
@@ -133,45 +126,14 @@ int installGeometry(orbx_handle* h, int rows, int cols) {
         }
         stage(h->d_colLevels, &c, sizeof(c));
     }
-    // The blur split by level (round 6): where the blur is done per keypoint (k_describe<PB>), the patches of a coarse level hold more pixels than the
-    // level itself - quota x 37 x 36 (the disc of the 43 x 37 horizontal pass + the 37 x 37 vertical one) against w x h; 640x480 x 1000: 0.94 of the
-    // level's pixels at level 0, 1.63 at level 3, 3.4 at level 7 - so from the first level whose patches exceed kSplitRatio x its pixels on, k_blur
-    // blurs the level (table [2] below) and k_describe reads the blurred level.  ORBX_BLUR_SPLIT=L pins the level, 0 turns the split off.
-    int splitLevel = 0;
-    if (h->blurSplit > 0) splitLevel = h->blurSplit;
-    else if (h->blurSplit < 0 && kSplitRatioNum > 0) {
-        for (int l = 1; l < g.nlevels && !splitLevel; l++)
-            if ((long long)g.lv[l].quota * 37 * 36 * kSplitRatioDen > (long long)kSplitRatioNum * g.lv[l].w * g.lv[l].h) splitLevel = l;
-        // ... if those levels hold a quarter of the features: two more launches for the coarsest level alone cost more than its patches (128 x
-        // 1280x720 x 1500, where only level 7 - 6 % of the features - is past 1.5: 1146 us per step split, 1128 unsplit)
-        int tail = 0;
-        for (int l = splitLevel; splitLevel && l < g.nlevels; l++) tail += g.lv[l].quota;
-        if (4 * tail < h->nfeatures) splitLevel = 0;
-    }
-    if (splitLevel >= g.nlevels) splitLevel = 0;
-    int nBlurLanes[3] = {0, 0, 0};
-    size_t blurItemOff[3] = {0, 0, 0}, blurLaneOff[3] = {0, 0, 0};
-    {   // blur tables for both row-block sizes, and the 32-row blocks of the levels from splitLevel on
+    // the launch policy's view of the geometry (orbx_batch_plan.hpp): the blur's split level, the quad-tree size, the blur tables of both row-block
+    // sizes and of the levels from the split level on
+    const GeometryPlan gp = planGeometry(g, h->launch);
+    {
         std::vector<BlurItem> tiles;
         std::vector<unsigned short> laneItem;
-        const int blockRows[3] = {kBlurBlockRows, kBlurBlockRowsSmall, kBlurBlockRows};
-        for (int v = 0; v < 3; v++) {
-            const size_t t0 = tiles.size(), l0 = laneItem.size();
-            int lanes = 0;
-            if (v == 2 && splitLevel == 0) { nBlurLanes[v] = 0; blurItemOff[v] = t0; blurLaneOff[v] = l0; continue; }
-            for (int l = 0; l < g.nlevels; l++) {
-                if (v == 2 && l < splitLevel) continue;               // the finest levels are blurred per keypoint
-                for (int y0 = 0; y0 < g.lv[l].h; y0 += blockRows[v]) {
-                    laneItem.insert(laneItem.end(), (size_t)(g.lv[l].w + 3) / 4, (unsigned short)(tiles.size() - t0));
-                    tiles.push_back(BlurItem{lanes, 0, (short)l, (short)y0});
-                    lanes += (g.lv[l].w + 3) / 4;
-                }
-            }
-            tiles[t0].count = (int)(tiles.size() - t0);
-            if (tiles.size() - t0 > 65535) return fail(h, ORBX_ERR_IMAGE_TOO_LARGE, "blur item table does not fit");
-            nBlurLanes[v] = lanes; blurItemOff[v] = t0; blurLaneOff[v] = l0;
-        }
-        if (tiles.size() > h->tileCap || laneItem.size() > h->laneCap) return fail(h, ORBX_ERR_IMAGE_TOO_LARGE, "blur item table does not fit");
+        if (!buildBlurTables(g, gp, tiles, laneItem) || tiles.size() > h->tileCap || laneItem.size() > h->laneCap)
+            return fail(h, ORBX_ERR_IMAGE_TOO_LARGE, "blur item table does not fit");
         stage(h->d_tiles, tiles.data(), sizeof(BlurItem) * tiles.size());
         stage(h->d_laneItem, laneItem.data(), sizeof(unsigned short) * laneItem.size());
     }
@@ -191,14 +153,7 @@ int installGeometry(orbx_handle* h, int rows, int cols) {
     for (const Upload& u : ups) HIP_TRY(h, hipMemcpyAsync(u.dst, h->h_tab + u.at, u.bytes, hipMemcpyHostToDevice, h->stream));
     for (int l = 0; l < kMaxLevels; l++) { h->rxOff[l] = rxOff[l]; h->ryOff[l] = ryOff[l]; h->xqOff[l] = xqOff[l]; h->footOff[l] = footOff[l]; }
     for (int i = 0; i < 4; i++) { h->colsOff[i] = colsOff[i]; h->colCoefOff[i] = colCoefOff[i]; }
-    h->splitLevel = splitLevel;
-    for (int v = 0; v < 3; v++) { h->nBlurLanes[v] = nBlurLanes[v]; h->blurItemOff[v] = blurItemOff[v]; h->blurLaneOff[v] = blurLaneOff[v]; }
-    {
-        const long long px = (long long)g.lv[0].w * g.lv[0].h;
-        int T = px <= 500000 ? 256 : (px <= 1200000 ? 512 : 1024);   // measured: 640x480 -> 256, 1280x720 -> 512, 1920x1080 -> 1024 (512 equal)
-        if (h->octThreadsForced == 256 || h->octThreadsForced == 512 || h->octThreadsForced == 1024) T = h->octThreadsForced;
-        for (int l = 0; l < g.nlevels; l++) h->octThreads[l] = T;
-    }
+    h->geomPlan = gp;
     h->geom = g;
     return ORBX_OK;
 }
@@ -210,8 +165,27 @@ int checkFrameArgs(orbx_handle* h, int n_frames, int rows, int cols) {
     return ORBX_OK;
 }
 
-// The launch sequence of one batch.  Everything is enqueued on h->stream; nothing synchronises.
-enum { kStageFront = 1, kStageBack = 2 };      // front: pyramid (+ blur) = ComputePyramid; back: FAST, quad-tree, orientation, descriptors
+// lapping areas: upload only when they change (they are per-camera constants in the reference)
+int uploadLapping(orbx_handle* h, int B, const int* lap) {
+    std::vector<int> want(2 * B);
+    for (int f = 0; f < B; f++) {
+        want[2 * f] = lap ? lap[2 * f] : 0;
+        want[2 * f + 1] = lap ? lap[2 * f + 1] : 1000;   // Frame.cc:307 passes {0,1000}
+    }
+    bool same = h->lapCached.size() >= want.size();
+    for (size_t i = 0; same && i < want.size(); i++) same = h->lapCached[i] == want[i];
+    if (!same) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // previous async copy out of h_lap is done
+        std::memcpy(h->h_lap, want.data(), want.size() * sizeof(int));
+        HIP_TRY(h, hipMemcpyAsync(h->d_lap, h->h_lap, want.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        h->lapCached = want;
+    }
+    return ORBX_OK;
+}
+
+// The launch sequence of one batch.  Everything is enqueued on h->stream; nothing synchronises.  WHICH forms the call takes is decided in
+// orbx_batch_plan.hpp (planBatch per call, planFront / planBack per part, with the measurements behind every rule); this function enqueues them
+// and records what ran (orbx_debug_last_forms, orbx_profile_kernel_name_of).
 int enqueueBatch(orbx_handle* h, int B, const uint8_t* d_imgs, int rows, int cols, long long stride,
                  long long frameStride, const int* lap, Keypoint* d_kps, uint8_t* d_desc, int capacity, int* d_nOut,
                  int* d_monoOut, Keypoint* d_levelK, int* d_levelCounts, int stages = kStageFront | kStageBack) {
@@ -221,221 +195,109 @@ int enqueueBatch(orbx_handle* h, int B, const uint8_t* d_imgs, int rows, int col
         if (rc != ORBX_OK) return rc;
     }
     const FrameGeom& g = h->geom;
+    const GeometryPlan& gp = h->geomPlan;
+    const LaunchPolicy& lp = h->launch;
     hipStream_t st = h->stream;
     if (h->leafDirty) {      // an earlier call returned between k_fast and k_octree: the leaf tables still hold its counts
-        const size_t n = (size_t)h->leafFrames * h->nlevels * h->octR * kOctLeaves;
+        const size_t n = (size_t)lp.leafFrames * h->nlevels * h->octR * kOctLeaves;
         HIP_TRY(h, hipMemsetAsync(h->d_leafHist, 0, n * sizeof(int), st));
         HIP_TRY(h, hipMemsetAsync(h->d_leafBest, 0, n * sizeof(unsigned), st));
         h->leafDirty = false;
     }
     Prof total(h, S_TOTAL);
-    // lapping areas: upload only when they change (they are per-camera constants in the reference)
-    {
-        std::vector<int> want(2 * B);
-        for (int f = 0; f < B; f++) {
-            want[2 * f] = lap ? lap[2 * f] : 0;
-            want[2 * f + 1] = lap ? lap[2 * f + 1] : 1000;   // Frame.cc:307 passes {0,1000}
-        }
-        bool same = h->lapCached.size() >= want.size();
-        for (size_t i = 0; same && i < want.size(); i++) same = h->lapCached[i] == want[i];
-        if (!same) {
-            HIP_TRY(h, hipStreamSynchronize(st));   // previous async copy out of h_lap is done
-            std::memcpy(h->h_lap, want.data(), want.size() * sizeof(int));
-            HIP_TRY(h, hipMemcpyAsync(h->d_lap, h->h_lap, want.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            h->lapCached = want;
-        }
-    }
-    // the launch sequence of frames [f0, f0 + Bn) on stream st, in two parts: front = pyramid + blur (HBM / latency bound),
-    // back = FAST (vector-issue bound) + quad-tree (barrier-latency bound) + description
-    auto blurVariant = [&](int Bn) { return (long long)h->nBlurLanes[0] * Bn >= 64LL * 2 * 4 * h->numCUs ? 0 : 1; };   // two waves per SIMD of 32-row lanes
-    auto blurRidesWithFast = [&](int Bn) { return blurVariant(Bn) == 1 && !h->profiling && h->fuseSmall && fastCanCarryBlur(g.maxRoiW, g.maxRoiH) && !g.big; };
-    // Patch blur (k_describe<PB>): no blurred levels at all - every keypoint's 37 x 37 patch is blurred out of its raw 43 x 43 tile.  It pays where
-    // the keypoints' patches are not a much larger job than the whole pyramid (nfeatures x 43 x 37 pixels of horizontal pass against the pyramid's
-    // pixels) and the blur would be a launch of its own (not the small-batch form that rides in the FAST launch) - k_describe is bound by its sparse
-    // patch reads at large frames, and the one raw tile is fewer bytes than a raw + a blurred one.  Measured (us per step, k_blur beside FAST ->
-    // patch blur): 128 x 1920x1080 x 2000 (ratio 0.50) 3041-3052 -> 2717-2723; 128 x 1280x720 x 1500 (0.84) 1448-1455 -> 1358-1364; 512 x 640x480 x
-    // 1000 (1.67) 1929-1937 -> 1993-2000: taken up to a ratio of 1.25.  ORBX_PATCH_BLUR=1 / 0 forces / forbids it.
-    // Round 5: ... and up to a ratio of 1.75 once the batch is large (>= 240 Mpx of pyramid: 256 frames of 640x480 x 1000).  Since round 4's
-    // instruction work the two forms are level there (512 x 640x480 x 1000: 1725-1729 us with k_blur beside FAST, 1735 with the patch blur, A/B in
-    // one gpurun call, -0.4 ... -0.6 %; 256 / 1024 frames the same; 64 frames -1.5 %, 1200 features per frame -3.5 %: not taken there), and the
-    // patch blur moves 4.75 MB per frame through HBM instead of 8.0 (no blurred level is written or re-read) and leaves the
-    // blurred arena (1 MB per frame) untouched: where the clock says "equal", the bytes decide.
-    // A back-only pass (orbx_compute_keypoints_octree) describes from what the front part of the EARLIER call left: if that call blurred per
-    // keypoint (form 3) no blurred level exists and this pass must do the same, whatever its own frame count would choose; otherwise the blurred
-    // levels exist (or are owed to the FAST launch: blurOwed) and are used.
-    // (round 6: "big" from ORBX_SPLIT_MIN_MPX = 120 Mpx of pyramid per call, the same threshold as the per-keypoint blur below - rounds 4-5: twice
-    // that -: 128 x 640x480 with the coarse levels' blur aside and staggered tails 457 -> 450 us)
-    const bool bigBatch = (long long)g.sumPixels * B >= h->splitMinPixels;
-    const long long patchPx4 = (long long)h->nfeatures * 43 * 37 * 4;      // 4 x the patches' pixels of horizontal pass
-    // Round 6: with the coarse levels split off to k_blur (installGeometry: splitLevel) the per-keypoint form also wins earlier and further - from
-    // 120 Mpx of pyramid per call (128 x 640x480: 468 -> 459 us; 64 frames: 232 -> 248, not taken) and up to a ratio of 2.25 (512 x 640x480 x 1200
-    // features, the stereo stream, 2.0: 1758 -> 1743 us).
-    const bool midBatch = (long long)g.sumPixels * B >= h->splitMinPixels;
-    const bool patchBlur = !(stages & kStageFront) ? (h->lastBlurForm == 3 || h->lastBlurForm == 5)
-                         : (h->patchBlur > 0 || (h->patchBlur < 0 && !blurRidesWithFast(B) && (patchPx4 <= 5LL * g.sumPixels || (midBatch && patchPx4 <= 9LL * g.sumPixels))));
-    // ... split by level: levels >= splitL are blurred by k_blur and described from the blurred level (installGeometry: splitLevel)
-    const int splitL = !patchBlur ? 0 : (!(stages & kStageFront) ? (h->lastBlurForm == 5 ? h->lastSplitLevel : 0)
-                                                                   : (h->splitLevel > 0 && h->splitLevel < g.nlevels && h->nBlurLanes[2] > 0 ? h->splitLevel : 0));
-    auto pollute = [&](hipStream_t st) { if (h->ldsPollute >= 0) launchLdsPollute(st, h->numCUs, h->ldsPollute, h->d_sink); };
-    // Overlap inside one call (round 4): the blurred levels are read by k_description only, the LAST launch, so the blur of a large batch runs on
-    // a side stream beside FAST and the quad-tree: pyramid -> {blur | FAST -> quad-tree} -> description.  k_blur is the one HBM-bound kernel of the
-    // path (0.53 of the issue rate), k_fast sits at the issue ceiling with idle memory pipes: 512 x 640x480 2016-2040 us unsplit, 1981-1988 as two
-    // halves side by side (round 2's form), 1915-1933 with the blur aside (two halves AND the blur aside: 1932-1937); 256 frames 1035-1055 / 1001-1014 /
-    // 999-1007; 128 x 1080p 3094-3136 (halves) -> 3021-3029; 128 frames of 640x480 and fewer: no difference.  A low-priority side stream only starts
-    // the blur when everything else is done (2022-2030).  ORBX_SPLIT=0: no overlap of any kind (profiling runs: one kernel at a time).  (Round 2's two
-    // half-batches side by side - removed in round 4 - are the "halves" figures above; profiles/r02_split_sweep.md.)
-    const bool blurSide = h->splitMode != 0 && bigBatch && !h->profiling && (stages & kStageFront) && (stages & kStageBack);
+    if (int rc = uploadLapping(h, B, lap)) return rc;
+    const CallState state{h->lastBlurForm, h->lastSplitLevel, h->blurOwed, h->profiling};
+    const BatchPlan bp = planBatch(g, gp, lp, state, B, stages);
+    auto pollute = [&](hipStream_t st) { if (h->ldsPollute >= 0) launchLdsPollute(st, lp.numCUs, h->ldsPollute, h->d_sink); };
+    auto blurTable = [&](hipStream_t st, int v, int blockRows, int f0, int Bn) {
+        launchBlur(st, h->d_tiles + gp.blurItemOff[v], h->d_laneItem + gp.blurLaneOff[v], gp.nBlurLanes[v], blockRows, h->d_lv, h->d_pyr, h->d_blur, f0, Bn);
+    };
     bool blurJoin[2] = {false, false};
     int blurF0[2] = {0, 0}, blurBn[2] = {0, 0};
+    // the launch sequence of frames [f0, f0 + Bn) on stream st, in two parts: front = pyramid + blur (HBM / latency bound),
+    // back = FAST (vector-issue bound) + quad-tree (barrier-latency bound) + description
     auto front = [&](hipStream_t st, int f0, int Bn) {
-        // The pyramid region by region: one workgroup takes a region of the image through every level (k_pyr_cols; the coarsest cut that still
-        // gives the chip ~3/4 workgroup per CU, else the finest).  Frames up to half a megapixel: for every batch size (512 frames of 640x480:
-        // 2016 -> 1979 us per call against one launch per level, whose tiles are poorly filled on such small levels); larger frames: while the
-        // coarsest cut stays below ~12 workgroups per CU - 1280x720: 16 frames 236 -> 226 us, 32: equal, 64: 767 vs 788; 1920x1080: 16 frames
-        // 431 -> 422, 64: 1530 vs 1582, 128: 3119 vs 3222.  (Round 2's per-tile chains, k_pyr_chain, lost to it at every size and were removed in
-        // round 4; a geometry whose regions do not fit the kernel's staging - none of the tested ones - takes one launch per level.)
-        const FrameGeom::ColumnSet* cs = nullptr;
-        auto pickCut = [&](const std::vector<FrameGeom::ColumnSet>& sets) {
-            const FrameGeom::ColumnSet* best = nullptr;
-            for (const FrameGeom::ColumnSet& c : sets) {
-                if (!c.fit || c.ldsBytes > 60 * 1024) continue;
-                if (!best || (long long)c.columns.size() * Bn >= 3LL * h->numCUs / 4) best = &c;
-            }
-            return best;
-        };
-        if (h->pyrCols != 0 && g.colsPacked && !h->resizeBytewise) {     // (its steps are the packed ones: the regions carry quad records)
-            cs = pickCut(g.colSets);
-        }
-        const bool smallFrame = (long long)g.rows * g.cols <= 512 * 1024;
-        if (cs && h->pyrCols < 0 && !smallFrame && (long long)cs->columns.size() * Bn > 12LL * h->numCUs) cs = nullptr;
-        h->lastPyrCut = cs ? cs->px : 0;
-        h->lastPyrForm = cs ? 0 : 1;
-        if (cs) {
-            // workgroup shape (launchPyrCols): while every workgroup has a CU to itself, more threads shorten its levels - 1024 (512 derive, 512
-            // write) for the fine cuts, 768 (256 + 512) for the coarse ones, whose levels write more than they derive; else 512 (256 + 256).
-            // One frame 40.9 -> 39.8 us, two 45.8 -> 44.6, four 58.3 -> 55.7, eight 71.5 -> 67.1; from 32 frames on the small shape wins
-            const int colsShape = h->colsShape > 0 ? h->colsShape : ((long long)cs->columns.size() * Bn <= h->numCUs ? (cs->px <= 56 ? 6 : 4) : 1);
+        const FrontPlan fp = planFront(g, gp, lp, state, bp, Bn);
+        h->lastPyrCut = fp.cut >= 0 ? g.colSets[fp.cut].px : 0;
+        h->lastPyrForm = fp.pyrForm();
+        if (fp.cut >= 0) {      // the pyramid region by region: one workgroup takes a region of the image through every level
+            const FrameGeom::ColumnSet& cs = g.colSets[fp.cut];
             Prof p(h, S_RESIZE, st);
-            h->lastKernel[S_RESIZE] = "k_pyr_cols";
+            h->lastKernel[S_RESIZE] = fp.resizeKernel;
             pollute(st);
-            const size_t slot = cs - g.colSets.data();
-            launchPyrCols(st, d_imgs, stride, frameStride, g.lv[0].w, h->d_cols + h->colsOff[slot], (int)cs->columns.size(), h->d_colLevels, g.nlevels,
-                          h->d_colCoef + h->colCoefOff[slot], cs->coefSlot, h->d_pyr, cs->ldsBytes, cs->evenBytes,
-                          g.colsPacked && !h->resizeBytewise, colsShape, f0, Bn);
+            launchPyrCols(st, d_imgs, stride, frameStride, g.lv[0].w, h->d_cols + h->colsOff[fp.cut], (int)cs.columns.size(), h->d_colLevels, g.nlevels,
+                          h->d_colCoef + h->colCoefOff[fp.cut], cs.coefSlot, h->d_pyr, cs.ldsBytes, cs.evenBytes,
+                          g.colsPacked && !lp.resizeBytewise, fp.colsShape, f0, Bn);
         } else {
             {   // level 0 (bordered copy) and level 1 (resized straight from the caller's image) in one launch
                 Prof p(h, S_LEVEL0, st);
                 pollute(st);
                 launchPyrFirst(st, d_imgs, stride, frameStride, g.lv[0], g.nlevels > 1 ? &g.lv[1] : nullptr, g.tilesX[0], g.tilesY[0],
                                g.tilesX[1], g.tilesY[1], h->d_rx + h->rxOff[1], h->d_xq + h->xqOff[1], h->d_ry + h->ryOff[1], h->d_foot + h->footOff[1], h->d_pyr,
-                               g.tileLdsStride, g.tileLdsRows, g.packedTaps[1] && !h->resizeBytewise, f0, Bn);
+                               g.tileLdsStride, g.tileLdsRows, g.packedTaps[1] && !lp.resizeBytewise, f0, Bn);
             }
             for (int l = 2; l < g.nlevels; l++) {      // levels 2..: one launch per level (each level is resized from the rounded pixels of the one above)
                 Prof p(h, S_RESIZE, st);
-                h->lastKernel[S_RESIZE] = "k_resize";
+                h->lastKernel[S_RESIZE] = fp.resizeKernel;
                 pollute(st);
                 launchResize(st, g.lv[l - 1], g.lv[l], g.tilesX[l], g.tilesY[l], h->d_rx + h->rxOff[l], h->d_xq + h->xqOff[l], h->d_ry + h->ryOff[l],
-                             h->d_foot + h->footOff[l], h->d_pyr, g.tileLdsStride, g.tileLdsRows, g.packedTaps[l] && !h->resizeBytewise, f0, Bn);
+                             h->d_foot + h->footOff[l], h->d_pyr, g.tileLdsStride, g.tileLdsRows, g.packedTaps[l] && !lp.resizeBytewise, f0, Bn);
             }
         }
-        // blur: throughput form (32-row blocks) once the grid fills the chip, else the short-chain form (8-row blocks), which in
-        // unprofiled small batches rides in the FAST launch (back) instead of being a launch of its own
-        h->lastBlurForm = patchBlur ? (splitL ? 5 : 3) : (blurRidesWithFast(Bn) ? 1 : 0);
-        h->lastSplitLevel = splitL;
-        h->blurOwed = !patchBlur && blurRidesWithFast(Bn);      // (the back part of this call - or orbx_compute_keypoints_octree later - brings the blur)
-        // the blurred levels are only read by k_describe, the last launch: a big batch blurs on the internal stream, beside k_fast and the
-        // quad-tree (pyramid -> {blur, FAST -> quad-tree} -> description)
-        auto blurLaunch = [&](int v, int blockRows) {
+        h->lastBlurForm = fp.blurForm;
+        h->lastSplitLevel = bp.splitL;
+        h->blurOwed = fp.blurOwed;
+        if (fp.blurTable >= 0) {
+            // the blurred levels are only read by k_describe, the last launch: a big batch blurs on the internal stream, beside k_fast and the
+            // quad-tree (pyramid -> {blur, FAST -> quad-tree} -> description)
             Prof p(h, S_BLUR, st);
             pollute(st);
             hipStream_t bs = st;
             const int half = f0 ? 1 : 0;
-            if (blurSide) {
+            if (bp.blurSide) {
                 (void)hipEventRecord(h->evPyr[half], st);
                 (void)hipStreamWaitEvent(h->aux2, h->evPyr[half], 0);
                 bs = h->aux2;
             }
-            launchBlur(bs, h->d_tiles + h->blurItemOff[v], h->d_laneItem + h->blurLaneOff[v], h->nBlurLanes[v], blockRows, h->d_lv, h->d_pyr, h->d_blur, f0, Bn);
-            if (blurSide) { (void)hipEventRecord(h->evBlur[half], h->aux2); blurJoin[half] = true; blurF0[half] = f0; blurBn[half] = Bn; }
-        };
-        if (patchBlur) {
-            if (splitL) blurLaunch(2, kBlurBlockRows);      // the coarse levels; levels < splitL: k_describe blurs per keypoint, no blurred level is written
-        } else if (!blurRidesWithFast(Bn)) {
-            // throughput form (32-row blocks) once the grid fills the chip, else the short-chain form (8-row blocks)
-            const int v = blurVariant(Bn);
-            blurLaunch(v, v == 1 ? kBlurBlockRowsSmall : kBlurBlockRows);
+            blurTable(bs, fp.blurTable, fp.blurBlockRows, f0, Bn);
+            if (bp.blurSide) { (void)hipEventRecord(h->evBlur[half], h->aux2); blurJoin[half] = true; blurF0[half] = f0; blurBn[half] = Bn; }
         }
     };
     bool injected = false;
-    // small batches: k_fast's emit does the quad-tree's first sweep (leaf counters and best keys in L2); k_octree loads and clears them
-    auto leafTables = [&](int f0, int Bn) {
+    BackPlan parts[2];      // the plan of each half's back part: backFast makes it, backTail of the same half reads it
+    auto leafTables = [&](const BackPlan& k) {
         LeafTables lt{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-        if (h->leafFrames && f0 + Bn <= h->leafFrames && !g.big)
-            lt = LeafTables{h->d_leafHist, h->d_leafBest, h->d_leafCode, h->d_leafCode + (size_t)g.nlevels * h->octXT, h->octR, h->octXT, g.nlevels, h->leafFrames};
+        if (k.leafTables)
+            lt = LeafTables{h->d_leafHist, h->d_leafBest, h->d_leafCode, h->d_leafCode + (size_t)g.nlevels * h->octXT, h->octR, h->octXT, g.nlevels, lp.leafFrames};
         return lt;
     };
     auto backFast = [&](hipStream_t st, int f0, int Bn) {
-        const LeafTables lt = leafTables(f0, Bn);
+        const BackPlan& k = parts[f0 ? 1 : 0] = planBack(g, gp, lp, state, f0, Bn, h->blurOwed);
+        const LeafTables lt = leafTables(k);
         {
             Prof p(h, S_FAST, st);
-            const bool carry = h->blurOwed && blurRidesWithFast(Bn);
-            if (h->blurOwed && !carry) {      // (a front part that counted on this launch, and a back part that cannot carry the blur: event profiling switched on in between)
-                launchBlur(st, h->d_tiles + h->blurItemOff[1], h->d_laneItem + h->blurLaneOff[1], h->nBlurLanes[1], kBlurBlockRowsSmall, h->d_lv, h->d_pyr, h->d_blur, f0, Bn);
-            }
+            if (k.blurFirst) blurTable(st, 1, kBlurBlockRowsSmall, f0, Bn);
             h->blurOwed = false;
             pollute(st);
             if (lt.hist) h->leafDirty = true;
             if (h->testFailAfterFast && lt.hist) { injected = true; h->testFailAfterFast = false; }      // (test aid: a call that dies between k_fast and k_octree)
-            const bool wide = !g.big && (h->fastWide > 0 || (h->fastWide < 0 && (long long)g.cells.size() * Bn <= 4LL * h->numCUs));
-            h->lastKernel[S_FAST] = wide && g.maxRoiW <= 45 && g.maxRoiH <= 45 ? "k_fast_wide" : "k_fast";
+            h->lastKernel[S_FAST] = k.fastKernel;
             launchFast(st, h->d_cells, (int)g.cells.size(), h->d_lv, g.nlevels, h->d_pyr, h->iniTh, h->minTh, h->d_candSeg,
-                       h->d_cellCount, g.maxRoiW, g.maxRoiH, f0, Bn, carry ? h->d_tiles + h->blurItemOff[1] : nullptr,
-                       h->d_laneItem + h->blurLaneOff[1], h->nBlurLanes[1], h->d_blur, lt, wide, g.big);
+                       h->d_cellCount, g.maxRoiW, g.maxRoiH, f0, Bn, k.carry ? h->d_tiles + gp.blurItemOff[1] : nullptr,
+                       h->d_laneItem + gp.blurLaneOff[1], gp.nBlurLanes[1], h->d_blur, lt, k.wide, g.big);
         }
     };
     auto backTail = [&](hipStream_t st, int f0, int Bn) {
         if (injected) return;
-        const LeafTables lt = leafTables(f0, Bn);
+        const BackPlan& k = parts[f0 ? 1 : 0];
+        const LeafTables lt = leafTables(k);
         {
             Prof p(h, S_OCTREE, st);
-            // small batches: while every (frame, level) workgroup is resident at once, the largest workgroup that still lets
-            // them all be resident finishes a level soonest (640x480, one frame: 73 us with 1024 threads, 104 us with 256)
-            int octT[kMaxLevels];
-            // (the "resident" variants are compiled for 4 waves per SIMD = 128 VGPRs, no scratch: 1024 threads per CU-SIMD set)
-            // (... the 1024-thread one; the 512- and 256-thread resident variants are compiled for 3 waves per SIMD - no scratch -: a CU then holds
-            // THREE 256-thread workgroups (one wave per SIMD each) but only ONE of 512 threads (two waves per SIMD each: a second would need four) -
-            // counted as 768 threads per CU, a third of the "resident" 512-thread workgroups queued)
-            const long long wgs = (long long)Bn * g.nlevels;
-            // one 1024-thread workgroup per CU (the 512-thread build is reached from here through `need` below, also one per CU), else three of 256
-            int residentT = wgs <= h->numCUs ? 1024 : (wgs * 256 <= 768LL * h->numCUs ? 256 : 0);
-            if (residentT < h->octThreads[0] || h->octThreadsForced) residentT = 0;   // never fewer threads than the image size asks for
-            if (g.big) residentT = wgs <= h->numCUs ? 1024 : 0;      // (frames beyond 4096 px: the 1024-thread builds are the ones that read two-dword candidates)
-            // ... but with the first sweep done by k_fast (leaf tables) what is left of a level is a chain of barriers over a list of at most
-            // quota + 3 nodes: when 256 threads still give every node of the list its own thread (the short pass forms) the small workgroup
-            // has the cheapest barriers (one frame: 1024 threads 16.7 us, 256 threads 13.6)
-            if (residentT && lt.hist) {
-                int q = 0;
-                for (int l = 0; l < g.nlevels; l++) q = g.lv[l].quota > q ? g.lv[l].quota : q;
-                // (nfeatures 1200, level-0 quota 261: 512 threads 14.1 us, 1024 threads 15.1 - its last pass ranks up to 256 multi-key nodes
-                // against each other, one packed key per node; before the packed key the larger workgroup won, 18.0 vs 19.3)
-                int need = q + 4 <= 256 ? 256 : (q + 4 <= 512 ? 512 : residentT);
-                if (need < residentT) residentT = need;
-            }
-            // queued launches whose first sweep k_fast has done: the same chain of barriers, and the 256-thread workgroup wins at every frame size
-            // (128 x 1080p: 87 us with 1024 threads, 57 with 512, 50 with 256; 64 x 1080p: 49 / 34 / 28; 128 x 720p: 87 / 57 / 46) - the sizes by
-            // image area were measured with the sweep inside the kernel, where a level-0 workgroup reads ~60 k candidates
-            const int queuedT = lt.hist && !h->octThreadsForced ? 256 : 0;
-            for (int l = 0; l < g.nlevels; l++) octT[l] = g.big ? 1024 : (residentT ? residentT : (queuedT ? queuedT : h->octThreads[l]));
-            // ... in its scratch-free build (three workgroups per CU instead of six) while the launch is at most four workgroups per CU: little queues
-            // behind the first round, and no spilled register is touched.  Round 6, A/B in one call (k_octree_256 -> _256r, us per launch; step): 128 x
-            // 1080p 51 -> 33 (2291-2294 -> 2271-2278), 64 x 1080p 28 -> 20, 128 x 720p 47 -> 32 (1167-1171 -> 1151-1157), 128 x 640x480 30 -> 28.5
-            // (472-473 -> 468); 256 x 640x480 equal; 512 x 640x480 112 -> 118 (1663 -> 1699: the spilling build keeps its place there, six per CU)
-            const bool roomy = residentT != 0 || h->octRoomyForced || (queuedT == 256 && wgs <= 4LL * h->numCUs);
             pollute(st);
-            h->lastKernel[S_OCTREE] = (h->d_octArena ? "k_octree_1024g" : "k_octree_" + std::to_string(octT[0]) + (roomy ? "r" : "")) + (g.big ? "b" : "");
+            h->lastKernel[S_OCTREE] = k.octKernel;
             launchOctree(st, h->d_lv, g.nlevels, h->d_cells, (int)g.cells.size(), h->d_candSeg, h->d_cellCount, h->d_cellOff,
                          h->d_candPos, h->d_candCount, h->d_nodeOf, h->d_sel, g.selPerFrame,
-                         h->d_levelCount, h->d_levelLap, h->d_lap, h->octM, h->octP, h->octR, h->octXT, octT, roomy, f0, Bn, h->d_octArena, lt, g.big);
+                         h->d_levelCount, h->d_levelLap, h->d_lap, h->octM, h->octP, h->octR, h->octXT, k.octT, k.roomy, f0, Bn, h->d_octArena, lt, g.big);
             h->leafDirty = false;
         }
         auto joinBlur = [&]() {
@@ -450,52 +312,39 @@ int enqueueBatch(orbx_handle* h, int B, const uint8_t* d_imgs, int rows, int col
                                h->d_levelLap, d_kps, d_desc, capacity, d_nOut, d_monoOut, d_levelK, d_levelCounts, pb, l0, l1,
                                g.lv[l0].selOff, l1 < g.nlevels ? g.lv[l1].selOff : g.selPerFrame, f0, Bn);
             };
-            if (splitL) {
+            if (bp.splitL) {
                 // (side by side on two streams - the plain launch behind the blur on ITS stream, starting together with the per-keypoint one - measured
                 // slower: 1673-1677 vs 1656-1659 us per 512 frames, the stereo stream 1740 vs 1721; docs/history/r06.md)
-                describe(true, 0, splitL);      // (needs no blurred level: in front of the join)
+                describe(true, 0, bp.splitL);      // (needs no blurred level: in front of the join)
                 joinBlur();
-                describe(false, splitL, g.nlevels);
+                describe(false, bp.splitL, g.nlevels);
             } else {
                 joinBlur();
-                describe(patchBlur, 0, g.nlevels);
+                describe(bp.patchBlur, 0, g.nlevels);
             }
         }
     };
-    auto back = [&](hipStream_t st, int f0, int Bn) { backFast(st, f0, Bn); backTail(st, f0, Bn); };
     struct BlurJoin {      // a blur left on the side stream by an early return is still joined into the caller's stream
         orbx_handle* h; hipStream_t st; bool* pending;
         ~BlurJoin() { for (int i = 0; i < 2; i++) if (pending[i]) (void)hipStreamWaitEvent(st, h->evBlur[i], 0); }
     } blurGuard{h, st, blurJoin};
     const bool doFront = (stages & kStageFront) != 0, doBack = (stages & kStageBack) != 0;
-    // Staggered tails (the largest batches: 1.5 x the pixels of `bigBatch` - round 5: 384 x 640x480 1315-1324 -> 1301-1308 us, 256 frames no difference;
-    // rounds 3-4: twice; ORBX_SPLIT=3: every big batch): FAST in two halves back to back on the
-    // caller's stream; the first half's quad-tree and description (barrier- and latency-bound: 0.4-0.6 of the issue rate) run on the internal
-    // stream under the second half's FAST.  512 x 640x480: 1913-1914 -> 1888-1894 us; 256 frames and 128 x 1080p: no difference (k_fast fills the chip;
-    // what runs beside it mostly adds its own issue time)
-    // (never with the blur riding in the FAST launch, the form of SMALL batches, which an ORBX_SPLIT_MIN_MPX=0 test run also counts as big: the
-    // whole-batch pyramid would leave the blur to the FIRST half's FAST launch only — found by the batch-shape fuzz)
-    // (round 6, with the blur split by level: every big batch of small frames - 256 x 640x480 880 -> 870 us, 320 frames 1085 -> 1063-1069; the stereo
-    // stream at 256 frames equal; rounds 3-5 started at 1.5-2 x the pixels of `bigBatch`)
-    const bool stagger = (h->splitMode == 3 || (h->splitMode == 1 && bigBatch && (long long)g.rows * g.cols <= 512 * 1024)) &&
-                         !h->profiling && B >= 2 && bigBatch && doFront && doBack && !blurRidesWithFast(B);
-    if (stagger) {
+    if (bp.stagger) {      // FAST in two halves back to back on the caller's stream; the first half's quad-tree and description on the internal stream
         struct Join {
             orbx_handle* h; hipStream_t st; bool armed = false;
             ~Join() { if (armed) { (void)hipEventRecord(h->evJoin, h->aux); (void)hipStreamWaitEvent(st, h->evJoin, 0); } }
         } join{h, st};
-        const int B0 = (B + 1) / 2;
         front(st, 0, B);
-        backFast(st, 0, B0);
+        backFast(st, 0, bp.B0);
         HIP_TRY(h, hipEventRecord(h->evFork, st));
         HIP_TRY(h, hipStreamWaitEvent(h->aux, h->evFork, 0));
         join.armed = true;
-        backTail(h->aux, 0, B0);
-        backFast(st, B0, B - B0);
-        backTail(st, B0, B - B0);
+        backTail(h->aux, 0, bp.B0);
+        backFast(st, bp.B0, B - bp.B0);
+        backTail(st, bp.B0, B - bp.B0);
     } else {
         if (doFront) front(st, 0, B);
-        if (doBack) back(st, 0, B);
+        if (doBack) { backFast(st, 0, B); backTail(st, 0, B); }
     }
     if (injected) return fail(h, ORBX_ERR_HIP, "injected failure (test aid fail_after_fast): returned between k_fast and k_octree");
     HIP_TRY(h, hipGetLastError());
@@ -656,7 +505,7 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     } while (0)
     h->device = device;
     CREATE_TRY(hipSetDevice(device));
-    h->nfeatures = nfeatures; h->nlevels = nlevels; h->iniTh = ini_th; h->minTh = min_th; h->scaleFactor = scale_factor;
+    h->launch.nfeatures = nfeatures; h->nlevels = nlevels; h->iniTh = ini_th; h->minTh = min_th; h->scaleFactor = scale_factor;
     h->maxW = max_width; h->maxH = max_height; h->maxB = max_batch;
     h->tabs = makeScaleTables(nfeatures, scale_factor, nlevels);
     // Launch-policy switches: read ONCE, here, and kept as a string (orbx_debug_policy; bench.py prints it as config.policy).  They choose between
@@ -722,15 +571,16 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     CREATE_ALLOC(h->d_sink, 64);
     CREATE_ALLOC(h->d_sel, h->selEntries * sizeof(uint2));
     if (h->octArenaSlice) CREATE_ALLOC(h->d_octArena, h->octArenaSlice * max_batch * nlevels);
+    h->launch.octArena = h->d_octArena != nullptr;
     // (k_fast pays ~6 % for the tables, k_octree loses its first sweep: 640x480, us per call without -> with: 12 frames 110 -> 101, 32: 169 -> 163,
     // 64: 306 -> 296, 128: 562 -> 556, 256: 1040 -> 1046, 512: 2040 -> 2053; 1920x1080: 16 frames 519 -> 431, 32: 904 -> 827, 128: 3108 -> 3092)
-    h->leafFrames = envInt("ORBX_LEAF_FRAMES", 128);
-    if (h->leafFrames > max_batch) h->leafFrames = max_batch;
-    if (h->octR < 1 || h->octArenaSlice || h->leafFrames < 0) h->leafFrames = 0;      // no dense phase, or node arrays in HBM: the first sweep stays in k_octree
+    h->launch.leafFrames = envInt("ORBX_LEAF_FRAMES", 128);
+    if (h->launch.leafFrames > max_batch) h->launch.leafFrames = max_batch;
+    if (h->octR < 1 || h->octArenaSlice || h->launch.leafFrames < 0) h->launch.leafFrames = 0;      // no dense phase, or node arrays in HBM: the first sweep stays in k_octree
     // (k_fast indexes the tables with 32 bits: cap the frames so that frames x levels x roots x 1024 stays below 2^30 entries)
-    if (h->leafFrames && (size_t)h->leafFrames * nlevels * h->octR * kOctLeaves >= ((size_t)1 << 30)) h->leafFrames = (int)((((size_t)1 << 30) - 1) / ((size_t)nlevels * h->octR * kOctLeaves));
-    if (h->leafFrames) {
-        const size_t n = (size_t)h->leafFrames * nlevels * h->octR * kOctLeaves;
+    if (h->launch.leafFrames && (size_t)h->launch.leafFrames * nlevels * h->octR * kOctLeaves >= ((size_t)1 << 30)) h->launch.leafFrames = (int)((((size_t)1 << 30) - 1) / ((size_t)nlevels * h->octR * kOctLeaves));
+    if (h->launch.leafFrames) {
+        const size_t n = (size_t)h->launch.leafFrames * nlevels * h->octR * kOctLeaves;
         CREATE_ALLOC(h->d_leafHist, n * sizeof(int));
         CREATE_ALLOC(h->d_leafBest, n * sizeof(unsigned));
         CREATE_TRY(hipMemsetAsync(h->d_leafHist, 0, n * sizeof(int), h->stream));          // the tables are zero between calls (also under the poison aid)
@@ -748,15 +598,15 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     CREATE_ALLOC(h->d_xq, sizeof(QuadRec) * h->xqCap);
     CREATE_ALLOC(h->d_tiles, sizeof(BlurItem) * h->tileCap);
     CREATE_ALLOC(h->d_laneItem, sizeof(unsigned short) * h->laneCap);
-    h->pyrCols = envInt("ORBX_PYR_COLS", -1);
+    h->launch.pyrCols = envInt("ORBX_PYR_COLS", -1);
     h->colPx = envInt("ORBX_PYR_COL_PX", 0);
-    h->fastWide = envInt("ORBX_FAST_WIDE", -1);
-    h->patchBlur = envInt("ORBX_PATCH_BLUR", -1);
-    h->blurSplit = envInt("ORBX_BLUR_SPLIT", -1);
+    h->launch.fastWide = envInt("ORBX_FAST_WIDE", -1);
+    h->launch.patchBlur = envInt("ORBX_PATCH_BLUR", -1);
+    h->launch.blurSplit = envInt("ORBX_BLUR_SPLIT", -1);
     h->sharedUploadBytes = g_aids.sharedUploadBytes;
     h->twoEyesWalk = g_aids.twoEyesWalk == 1;
     h->twoEyesBowStage = g_aids.twoEyesBowStage != 0;
-    h->colsShape = g_aids.colsShape == 1 || g_aids.colsShape == 4 || g_aids.colsShape == 6 ? g_aids.colsShape : -1;
+    h->launch.colsShape = g_aids.colsShape == 1 || g_aids.colsShape == 4 || g_aids.colsShape == 6 ? g_aids.colsShape : -1;
     h->colsCap = 0;
     for (int px : kColPx) h->colsCap += (size_t)((max_width + px / 2) / px + 1) * ((max_height + px / 2) / px + 1);
     h->colCoefCap = (h->colsCap + h->colsCap / 8 + 16) * (size_t)kChainCoefMax * 5 / 8;      // (a region's list is 0.4 - 0.8 of the kernel's limit; a geometry past this keeps the tile forms)
@@ -778,24 +628,24 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     for (int i = 0; i < 2; i++) CREATE_TRY(hipEventCreateWithFlags(&h->evUp[i], hipEventDisableTiming));
     CREATE_TRY(hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming));
     CREATE_TRY(hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming));
-    h->splitMode = envInt("ORBX_SPLIT", 1);
-    h->fuseSmall = envInt("ORBX_FUSE_SMALL", 1) != 0;
+    h->launch.splitMode = envInt("ORBX_SPLIT", 1);
+    h->launch.fuseSmall = envInt("ORBX_FUSE_SMALL", 1) != 0;
     {
         const char* e = getenv("ORBX_SPLIT_MIN_MPX");
-        h->splitMinPixels = (long long)((e ? atof(e) : 120.0) * 1e6);
+        h->launch.splitMinPixels = (long long)((e ? atof(e) : 120.0) * 1e6);
         h->policy += std::string(" SPLIT_MIN_MPX=") + (e ? e : "120") + (e ? "(env)" : "");
     }
-    h->resizeBytewise = getenv("ORBX_RESIZE_BYTEWISE") != nullptr;      // diagnostic: the byte-gather form of k_resize
-    h->octRoomyForced = getenv("ORBX_OCT_ROOMY") != nullptr;
-    h->policy += std::string(" RESIZE_BYTEWISE=") + (h->resizeBytewise ? "1(env)" : "0") + " OCT_ROOMY=" + (h->octRoomyForced ? "1(env)" : "0");
-    h->octThreadsForced = envInt("ORBX_OCT_THREADS", 0);   // tuning switch: 256, 512 or 1024
+    h->launch.resizeBytewise = getenv("ORBX_RESIZE_BYTEWISE") != nullptr;      // diagnostic: the byte-gather form of k_resize
+    h->launch.octRoomyForced = getenv("ORBX_OCT_ROOMY") != nullptr;
+    h->policy += std::string(" RESIZE_BYTEWISE=") + (h->launch.resizeBytewise ? "1(env)" : "0") + " OCT_ROOMY=" + (h->launch.octRoomyForced ? "1(env)" : "0");
+    h->launch.octThreadsForced = envInt("ORBX_OCT_THREADS", 0);   // tuning switch: 256, 512 or 1024
     if (g_aids.ldsPollute >= 0) h->ldsPollute = g_aids.ldsPollute & 255;
-    if (poison >= 0 || h->ldsPollute >= 0 || h->testFailAfterFast || h->colsShape > 0 || h->sharedUploadBytes >= 0)
+    if (poison >= 0 || h->ldsPollute >= 0 || h->testFailAfterFast || h->launch.colsShape > 0 || h->sharedUploadBytes >= 0)
         h->policy += " test_aids=poison:" + std::to_string(poison) + ",lds_pollute:" + std::to_string(h->ldsPollute) + ",fail_after_fast:" + std::to_string((int)h->testFailAfterFast) +
-                     ",pyr_cols_shape:" + std::to_string(h->colsShape) + ",shared_upload_bytes:" + std::to_string(h->sharedUploadBytes);
+                     ",pyr_cols_shape:" + std::to_string(h->launch.colsShape) + ",shared_upload_bytes:" + std::to_string(h->sharedUploadBytes);
     {
         int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->numCUs = cus;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->launch.numCUs = cus;
     }
     CREATE_TRY(hipHostMalloc(&h->h_out, h->outBytes));
     std::memset(h->h_out, 0, h->outBytes);
@@ -835,7 +685,7 @@ int orbx_get_levels(const orbx_handle* h) { return h ? h->nlevels : 0; }
 float orbx_get_scale_factor(const orbx_handle* h) { return h ? h->scaleFactor : 0.f; }
 int orbx_get_tables(const orbx_handle* h, float* sf, float* isf, float* s2, float* is2, int* quota, int* umax16) {
     if (!h) return ORBX_ERR_BAD_ARGUMENT;
-    return orbx_compute_tables(h->nfeatures, h->scaleFactor, h->nlevels, sf, isf, s2, is2, quota, umax16);
+    return orbx_compute_tables(h->launch.nfeatures, h->scaleFactor, h->nlevels, sf, isf, s2, is2, quota, umax16);
 }
 int orbx_max_keypoints(const orbx_handle* h) { return h ? h->outCap : 0; }
 
@@ -898,7 +748,7 @@ int orbx_extract_batch_begin(orbx_handle* h, int n_frames, const uint8_t* imgs, 
         const size_t bytes = want_levels ? lo.all : lo.noLevels;
         if (usesSharedUpload(h, B, rows, cols)) HIP_TRY(h, hipMemcpyAsync(h->h_out, h->d_out, bytes, hipMemcpyDeviceToHost, st));
         else {
-            launchCopyOut(st, h->d_out, h->h_out, bytes, h->numCUs);
+            launchCopyOut(st, h->d_out, h->h_out, bytes, h->launch.numCUs);
             HIP_TRY(h, hipGetLastError());      // (a launch reports nothing by itself: a refused one would leave the slab of the last batch)
         }
     }

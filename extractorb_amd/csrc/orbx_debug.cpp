@@ -42,10 +42,10 @@ int orbx_debug_clock_probe(orbx_handle* h, int slot) {
     HIP_TRY(h, hipSetDevice(h->device));
     if (!h->probeStream) {
         HIP_TRY(h, hipStreamCreateWithFlags(&h->probeStream, hipStreamNonBlocking));
-        HIP_TRY(h, hipMalloc(&h->d_clock, sizeof(unsigned long long) * 2 * kClockSlots * h->numCUs));
-        HIP_TRY(h, hipMemsetAsync(h->d_clock, 0, sizeof(unsigned long long) * 2 * kClockSlots * h->numCUs, h->probeStream));
+        HIP_TRY(h, hipMalloc(&h->d_clock, sizeof(unsigned long long) * 2 * kClockSlots * h->launch.numCUs));
+        HIP_TRY(h, hipMemsetAsync(h->d_clock, 0, sizeof(unsigned long long) * 2 * kClockSlots * h->launch.numCUs, h->probeStream));
     }
-    launchClockProbe(h->probeStream, h->d_clock, slot, h->numCUs, kClockTicks);
+    launchClockProbe(h->probeStream, h->d_clock, slot, h->launch.numCUs, kClockTicks);
     HIP_TRY(h, hipGetLastError());
     return ORBX_OK;
 }
@@ -53,12 +53,12 @@ int orbx_debug_clock_read(orbx_handle* h, int n_slots, double* ghz) {
     if (!h || !ghz || n_slots < 1 || n_slots > kClockSlots) return ORBX_ERR_BAD_ARGUMENT;
     if (!h->probeStream) return fail(h, ORBX_ERR_BAD_ARGUMENT, "orbx_debug_clock_read: no probe was launched");
     HIP_TRY(h, hipSetDevice(h->device));
-    std::vector<unsigned long long> v((size_t)2 * n_slots * h->numCUs);
+    std::vector<unsigned long long> v((size_t)2 * n_slots * h->launch.numCUs);
     HIP_TRY(h, hipMemcpyAsync(v.data(), h->d_clock, v.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->probeStream));
     HIP_TRY(h, hipStreamSynchronize(h->probeStream));
     for (int s = 0; s < n_slots; s++) {
         double dt = 0, dr = 0;
-        for (int w = 0; w < h->numCUs; w++) { dt += (double)v[2 * ((size_t)s * h->numCUs + w)]; dr += (double)v[2 * ((size_t)s * h->numCUs + w) + 1]; }
+        for (int w = 0; w < h->launch.numCUs; w++) { dt += (double)v[2 * ((size_t)s * h->launch.numCUs + w)]; dr += (double)v[2 * ((size_t)s * h->launch.numCUs + w) + 1]; }
         ghz[s] = dr > 0 ? 0.1 * dt / dr : 0.0;      // cycles per 10-ns tick -> GHz
     }
     return ORBX_OK;
@@ -72,7 +72,7 @@ int orbx_debug_last_forms(const orbx_handle* h, int* pyramid_form, int* pyramid_
     return ORBX_OK;
 }
 
-int orbx_debug_last_split_level(const orbx_handle* h) { return h && h->lastBlurForm == 5 ? h->lastSplitLevel : 0; }
+int orbx_debug_last_split_level(const orbx_handle* h) { return h && h->lastBlurForm == kBlurSplitByLevel ? h->lastSplitLevel : 0; }
 
 int orbx_debug_num_candidates(orbx_handle* h, int frame, int level, int* n) {
     if (!h || !n) return ORBX_ERR_BAD_ARGUMENT;
@@ -132,7 +132,7 @@ int orbx_debug_get_blurred(orbx_handle* h, int frame, int level, uint8_t* dst, p
     HIP_TRY(h, hipSetDevice(h->device));
     const LevelGeom& L = h->geom.lv[level];
     if (dst_stride < L.w) return fail(h, ORBX_ERR_BAD_ARGUMENT, "dst_stride too small");
-    if (h->lastBlurForm == 3 || (h->lastBlurForm == 5 && level < h->lastSplitLevel))
+    if (h->lastBlurForm == kBlurPerKeypoint || (h->lastBlurForm == kBlurSplitByLevel && level < h->lastSplitLevel))
         return fail(h, ORBX_ERR_UNSUPPORTED, "the last call blurred this level per keypoint inside k_describe: no blurred level exists (ORBX_PATCH_BLUR=0 keeps k_blur)");
     HIP_TRY(h, hipMemcpy2DAsync(dst, dst_stride, h->d_blur + L.blurOff + (long long)frame * L.blurFrameBytes, L.blurStride, L.w,
                                 L.h, hipMemcpyDeviceToHost, h->stream));

@@ -2,7 +2,8 @@
 // helpers.  orbx_api.cpp holds the extraction path (create, geometry installation, the launch sequence, the extract entry points, the pyramid),
 // orbx_rows.cpp the rows behind it (stereo matching, Frame finishing, the window searches, the vocabulary and ComputeBoW / SearchByBoW),
 // orbx_mapping_two_eyes.cpp Fuse on two-camera keyframes, orbx_mapping.cpp CreateNewMapPoints' triangulation on one-camera keyframes, orbx_debug.cpp the introspection, profiling and test aids.  The entry points' plain statements (predicates, parameter fills, padding rules) are
-// in orbx_entry.hpp, which needs no HIP; what they need of the handle or the runtime is at the end of this file.  Not installed: callers see
+// in orbx_entry.hpp, which needs no HIP; what they need of the handle or the runtime is at the end of this file.  The extraction path's launch
+// policy - which forms a geometry, a call and each part of a call take - is orbx_batch_plan.hpp, host only as well.  Not installed: callers see
 // include/orbx.h only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +21,7 @@
 #include "orbx.h"
 #include "orbx_entry.hpp"
 #include "orbx_geometry.hpp"
+#include "orbx_batch_plan.hpp"
 #include "orbx_params.hpp"
 
 namespace orbx {
@@ -122,11 +124,13 @@ struct EventPair { hipEvent_t a, b; int slot; };
 
 struct orbx_handle {
     int device = 0;
-    int nfeatures = 0, nlevels = 0, iniTh = 0, minTh = 0;
+    int nlevels = 0, iniTh = 0, minTh = 0;
+    LaunchPolicy launch;   // the launch-policy switches as orbx_create read them, nfeatures and the facts of the device (orbx_batch_plan.hpp)
     float scaleFactor = 0;
     int maxW = 0, maxH = 0, maxB = 0;
     ScaleTables tabs;
     FrameGeom geom;        // geometry of the image size of the last call
+    GeometryPlan geomPlan; // ... and what the launch policy makes of it (installGeometry: split level, quad-tree size, blur tables)
     FrameGeom maxGeom;     // geometry of max_width x max_height (sizes the arenas)
     hipStream_t stream = nullptr;
     bool ownStream = false;
@@ -153,28 +157,18 @@ struct orbx_handle {
     ResizeX* d_colCoef = nullptr;       // the regions' coefficient lists, cut after cut
     size_t colCoefCap = 0, colCoefOff[4] = {};
     ColLevels* d_colLevels = nullptr;
-    int pyrCols = -1;                   // ORBX_PYR_COLS: 1 = the region-major pyramid for every batch it fits, 0 = never, default: the smallest batches
     int colPx = 0;                      // ORBX_PYR_COL_PX: side of its regions in level-0 pixels (0: default)
-    int fastWide = -1;                  // ORBX_FAST_WIDE: 1 = a workgroup per FAST cell (k_fast_wide) whatever the batch, 0 = never, default: while a call holds few cells
-    int patchBlur = -1;                 // ORBX_PATCH_BLUR: 1 = k_describe blurs each keypoint's patch itself (no blurred levels), 0 = never, default: by features per pixel (enqueueBatch)
-    int blurSplit = -1;                 // ORBX_BLUR_SPLIT=L: where the blur is per keypoint, only levels < L are (k_describe<PB>); levels >= L are blurred by k_blur and
-                                        // described from the blurred level (the patches of the coarse levels hold more pixels than the levels); 0 = no split; default: enqueueBatch
-    int colsShape = -1;                 // test aid "pyr_cols_shape": workgroup shape of k_pyr_cols (launchPyrCols: 1, 4 or 6; default: by the grid size)
     TileFoot* d_foot = nullptr;
     size_t footCap = 0, footOff[kMaxLevels] = {};
     BlurItem* d_tiles = nullptr;   // row-block items of the blur kernel: [0] blocks of kBlurBlockRows rows, [1] of kBlurBlockRowsSmall rows
     unsigned short* d_laneItem = nullptr;   // item of every lane of the blur grid, both tables
     size_t laneCap = 0;
-    int nBlurLanes[3] = {0, 0, 0};     // [0]: 32-row blocks of every level, [1]: 8-row blocks (small batches), [2]: 32-row blocks of the levels >= splitLevel (the blur split by level)
-    size_t blurItemOff[3] = {0, 0, 0}, blurLaneOff[3] = {0, 0, 0};
-    int splitLevel = 0;                // the level table [2] starts at (installGeometry; 0: no such table)
     size_t rxOff[kMaxLevels] = {}, ryOff[kMaxLevels] = {};
     size_t octArenaSlice = 0;      // > 0: node arrays of the quad-tree live in d_octArena (too large for LDS)
     uint8_t* d_octArena = nullptr;
     int octM = 0, octP = 0, octR = 0, octXT = 0;   // quad-tree LDS: max nodes, sort size, roots covered by the dense phase
     // small batches: per-(frame, level, root) leaf counters / best keys filled by k_fast's emit, consumed and cleared by k_octree
     // (orbx_device.hpp: LeafTables); d_leafCode = [2][nlevels][octXT] host-built x / y path codes of the current geometry
-    int leafFrames = 0;            // frames covered (ORBX_LEAF_FRAMES, default 128; 0 = off)
     int* d_leafHist = nullptr;
     unsigned* d_leafBest = nullptr;
     uint8_t* d_leafCode = nullptr;
@@ -208,14 +202,8 @@ struct orbx_handle {
     int lastHostB = 0;           // frames whose results the handle itself holds (the result slab: h->dev / h->host): set by the host-buffer path only
     int pendingB = 0;            // frames of the batch begun with orbx_extract_batch_begin and not yet ended
     bool pendingLevels = false;
-    int octThreads[kMaxLevels] = {};   // quad-tree workgroup size per level (installGeometry: one size for all levels,
-                                       // chosen by the image area — separate launches per size measured slower)
-    int octThreadsForced = 0;          // ORBX_OCT_THREADS
     int ldsPollute = -1;               // test aid "lds_pollute" (orbx_debug_set_option): every CU's LDS is filled with the byte in front of every kernel
     std::string policy;                // the launch-policy switches as read at orbx_create (orbx_debug_policy)
-    bool octRoomyForced = false;       // ORBX_OCT_ROOMY: the 128-VGPR variants whatever the batch (tests reach every variant with it)
-    int numCUs = 256;
-    bool resizeBytewise = false;    // ORBX_RESIZE_BYTEWISE: force the byte-gather resize (diagnostic)
     // the internal stream and the events of the two-half overlap (enqueueBatch)
     hipStream_t aux = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr;
@@ -225,10 +213,6 @@ struct orbx_handle {
     hipEvent_t evUp[2] = {nullptr, nullptr};      // uploadFrames: the handle's stream -> the device's shared input-copy queue -> back
     hipStream_t aux2 = nullptr;        // the blur's side stream (pyramid -> {blur, FAST -> quad-tree} -> description), events per half-batch
     hipEvent_t evPyr[2] = {nullptr, nullptr}, evBlur[2] = {nullptr, nullptr};
-    int splitMode = 1;                 // ORBX_SPLIT: 1 (default) = large batches overlap their blur with FAST + quad-tree on a side stream (the largest also stagger
-                                       // their tails: enqueueBatch); 0 = no overlap of any kind; 3 = staggered tails for every large batch
-    bool fuseSmall = true;             // ORBX_FUSE_SMALL=0: small batches keep the blur as a launch of its own
-    long long splitMinPixels = 0;      // ORBX_SPLIT_MIN_MPX: smallest half (pyramid pixels) worth its own kernels
     // ComputeBoW scratch (allocated on first use): per-feature word id / weight / node
     size_t bowEntries = 0;
     uint32_t *d_bowWord = nullptr, *d_bowNode = nullptr;
