@@ -47,6 +47,7 @@ void launchStereoFisheye(hipStream_t, const Keypoint*, const uint8_t*, const int
 int newMapPointsTiles(int listCapacity);
 void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*, const Keypoint*, const Keypoint*, const float*, const float*, const int*, const NewMapPointsParams&, uint8_t*, float*, int*, uint8_t*, uint8_t*, int);
 void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const MapPointUpdateParams&);
+void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const int*, const TwoViewParams&, const TvWork&, void*, float*, uint8_t*, int);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
@@ -226,6 +227,9 @@ struct orbx_handle {
     // the two-eye frustum requests' workspace (allocated on first use): a (slot count, in-view count) pair per workgroup of k_frustum_two_eyes_check
     size_t frustumCountEntries = 0;
     int* d_frustumCounts = nullptr;
+    // the two-view reconstruction's workspace (allocated on first use): what TvWork names, sized for (pairs, capacity, iterations)
+    struct TwoViewShape { size_t pairs = 0, cap = 0, iters = 0; } twoView;
+    TvWork twoViewWork = {};
     // stereo matching (allocated on first use)
     struct StereoShape { int pairs = 0, cap = 0, rows = 0; } stereo;      // what the six buffers below are sized for
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;

@@ -176,6 +176,20 @@ struct MapPointUpdateArrays {    // the arrays of orbx_update_map_points*_device
     uint8_t* mpDesc; float* mpNormal; float* mpDist; int* best; int* bestMedian; uint8_t* status;
 };
 
+struct TwoViewParams {           // k_two_view.hip / k_two_view.hpp
+    float fx, fy, cx, cy;                                // Pinhole::toK()
+    float sigma, minParallax, rhThreshold;
+    int iterations, minTriangulated, prune, capacity;
+    int f1First, f1Step, f2First, f2Step;
+};
+
+constexpr int kTvMaxIterations = 4096;                    // the cap on orbx_reconstruct_two_views_device's `iterations` (include/orbx.h)
+// what the first kernel leaves for the other two, per pair: norm = meanX, sX, meanY, sY of frame 1, then of frame 2
+struct TvPrep { int status, n, n1, n2; float norm[8]; float T1[9], T2[9], T2inv[9], T2t[9]; };
+// the workspace: prep[pair]; first / second [pair*capacity + k] the compacted matches; score [(pair*2 + model)*iterations + it] and mats
+// [.. * 9] (model 0 = H, 1 = F); inl / counted / cosv [pair*capacity + k]
+struct TvWork { TvPrep* prep; int* first; int* second; float* score; float* mats; uint8_t* inl; uint8_t* counted; float* cosv; };
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

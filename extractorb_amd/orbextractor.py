@@ -26,6 +26,13 @@ PROJ_QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("radius
 TRACK_RECORD_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"),
                                ("level", "<i4"), ("exit", "<i4")])
 assert PROJ_QUERY_DTYPE.itemsize == 32 and TRACK_RECORD_DTYPE.itemsize == 28
+# == orbx_two_view_result / enum orbx_two_view_status
+TWO_VIEW_RESULT_DTYPE = np.dtype([("status", "<i4"), ("model", "<i4"), ("n_matches", "<i4"), ("best_it_h", "<i4"), ("best_it_f", "<i4"),
+                                  ("n_inliers", "<i4"), ("chosen", "<i4"), ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"), ("H21", "<f4", 9),
+                                  ("F21", "<f4", 9), ("R21", "<f4", 9), ("t21", "<f4", 3), ("n_good", "<i4", 8), ("parallax", "<f4", 8)])
+assert TWO_VIEW_RESULT_DTYPE.itemsize == 224
+TWO_VIEW_STATUS = ("ACCEPTED_H", "ACCEPTED_F", "TOO_FEW_MATCHES", "BAD_INDEX", "ZERO_SCORES", "H_DEGENERATE", "H_AMBIGUOUS", "H_LOW_PARALLAX",
+                   "H_FEW_POINTS", "H_BELOW_INLIER_SHARE", "F_FEW_POINTS", "F_AMBIGUOUS", "F_LOW_PARALLAX")
 FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION = 0, 1      # orbx_frustum_mode
 (FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH, FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR,
  FRUSTUM_REQUEST) = range(7)                           # orbx_frustum_exit
@@ -207,11 +214,14 @@ def load_library():
     L.orbx_create_new_map_points_two_eyes_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
                                                              C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp]
     L.orbx_debug_new_map_points_stats.argtypes = [ip]
+    L.orbx_reconstruct_two_views_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_float,
+                                                    C.c_int, C.c_float, C.c_int, C.c_float, vp, C.c_int, vp, vp, vp]
     L.orbx_update_map_points_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp,
                                                 vp, vp, vp, vp]
     L.orbx_update_map_points_two_eyes_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int,
                                                          C.c_int, vp, vp, vp, vp, vp, vp]
     L.orbx_debug_new_map_points_enable.argtypes = [C.c_int]
+    L.orbx_debug_two_view_shape.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -563,6 +573,18 @@ class ORBextractor:
             _dev(d_grid_off), _dev(d_grid_idx), _host_f32(bounds), _dev(d_prev_matched), window, nnratio, int(check_orientation),
             _dev(d_matches12), _dev(d_n_matches)))
 
+    def reconstruct_two_views_device(self, n_pairs, frames1, frames2, d_kps_un, d_n, capacity, d_matches12, d_n_matches, cam, d_rand,
+                                     d_result, d_p3d, d_triangulated, sigma=1.0, iterations=200, min_parallax=1.0, min_triangulated=50,
+                                     rh_threshold=0.5, prune=False):
+        """TwoViewReconstruction::Reconstruct (reference src/TwoViewReconstruction.cc:39-125) on the tables search_for_initialization_device
+        wrote; frames1 / frames2 = (first, step).  d_rand [(p*iterations + it)*8 + j] holds the caller's raw rand() values (int32); d_result
+        one TWO_VIEW_RESULT_DTYPE row per pair; d_p3d [(p*capacity + i)*3] and d_triangulated [p*capacity + i] are vP3D and vbTriangulated.
+        prune: the tracker's next statement (src/Tracking.cc:2083-2090) on d_matches12 / d_n_matches of an accepted pair."""
+        self._check(self._L.orbx_reconstruct_two_views_device(
+            self._h, n_pairs, frames1[0], frames1[1], frames2[0], frames2[1], _dev(d_kps_un), _dev(d_n), capacity, _dev(d_matches12),
+            _dev(d_n_matches), _host_f32(cam), sigma, iterations, min_parallax, min_triangulated, rh_threshold, _dev(d_rand), int(prune),
+            _dev(d_result), _dev(d_p3d), _dev(d_triangulated)))
+
     def project_last_frame_device(self, n_pairs, last, cur, d_kps, d_kps_un, d_n, capacity, d_mp_flags, d_world, d_poses, cam, bounds,
                                   mbf, mb, th, mono, d_queries):
         """Front half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (reference src/ORBmatcher.cc:1961-2023);
@@ -795,6 +817,10 @@ class ORBextractor:
             self._h, n_points, _dev(d_obs_off), _dev(d_obs), _dev(d_obs_flags), _dev(d_ref), _dev(d_slot), _dev(d_mp_world), _dev(d_poses),
             _host_f32(tlr), n_rigs, _dev(d_kps), _dev(d_desc), _dev(d_n), capacity, self.nlevels if nlevels is None else nlevels, int(what),
             _dev(d_mp_desc), _dev(d_mp_normal), _dev(d_mp_dist), _dev(d_best), _dev(d_best_median), _dev(d_status)))
+
+    def two_view_shape(self, shape=1):
+        """which hypothesis kernel reconstruct_two_views_device launches (process-wide): 1 rows over the lanes (default), 0 one lane out of LDS"""
+        self._check(self._L.orbx_debug_two_view_shape(int(shape)))
 
     def new_map_points_count(self, on=True):
         """switches the debug counters of the two create_new_map_points entries on or off (process-wide; off by default)"""

@@ -271,6 +271,69 @@ int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame
                                           const float* bounds4, float* d_prev_matched, int window_size, float nn_ratio,
                                           int check_orientation, int* d_matches12, int* d_n_matches);
 
+/* ---- monocular initialisation, second half: TwoViewReconstruction::Reconstruct ---------------------------------------
+ * The statement behind SearchForInitialization in the tracker: mpCamera->ReconstructWithTwoViews (src/Tracking.cc:2081 ->
+ * src/CameraModels/Pinhole.cpp:105-113 -> src/TwoViewReconstruction.cc:39-125) on the d_matches12 the search left on the device, and,
+ * with prune != 0, the statement after it (src/Tracking.cc:2083-2090).  Pairs and arrays are numbered and shaped as
+ * orbx_search_for_initialization_device's, so that entry's outputs go in unchanged.
+ * How a pair left Reconstruct; every way out has a name: */
+enum orbx_two_view_status {
+    ORBX_TWO_VIEW_ACCEPTED_H = 0,            /* ReconstructH returned true (:724-732) */
+    ORBX_TWO_VIEW_ACCEPTED_F = 1,            /* ReconstructF returned true (:526-571) */
+    ORBX_TWO_VIEW_TOO_FEW_MATCHES = 2,       /* N < 8: the reference would call RandomInt(0, -1) */
+    ORBX_TWO_VIEW_BAD_INDEX = 3,             /* a d_matches12[i] >= n of frame 2: nothing else is read; decides before TOO_FEW_MATCHES */
+    ORBX_TWO_VIEW_ZERO_SCORES = 4,           /* SH + SF == 0 (:111) */
+    ORBX_TWO_VIEW_H_DEGENERATE = 5,          /* d1/d2 < 1.00001 || d2/d3 < 1.00001 (:600) */
+    ORBX_TWO_VIEW_H_AMBIGUOUS = 6,           /* the four conjuncts of :724, named by the first that fails in source order */
+    ORBX_TWO_VIEW_H_LOW_PARALLAX = 7,
+    ORBX_TWO_VIEW_H_FEW_POINTS = 8,
+    ORBX_TWO_VIEW_H_BELOW_INLIER_SHARE = 9,
+    ORBX_TWO_VIEW_F_FEW_POINTS = 10,         /* maxGood < nMinGood (:520) */
+    ORBX_TWO_VIEW_F_AMBIGUOUS = 11,          /* nsimilar > 1 (:520) */
+    ORBX_TWO_VIEW_F_LOW_PARALLAX = 12        /* the best motion's parallax is not above min_parallax (:526-571) */
+};
+/* One row per pair.  Every field computed before the exit holds its value, the rest is zero (best_it_* and chosen: -1). */
+typedef struct orbx_two_view_result {
+    int32_t status;                /* orbx_two_view_status */
+    int32_t model;                 /* the model taken: 0 = H, 1 = F; -1 before the branch */
+    int32_t n_matches;             /* N = the d_matches12[i] >= 0 of the pair */
+    int32_t best_it_h, best_it_f;  /* the winning iteration of each model: the first with a strictly greater score (-1: no score above 0) */
+    int32_t n_inliers;             /* vbMatchesInliers of the model taken */
+    int32_t chosen;                /* the motion taken, an index into n_good / parallax */
+    float SH, SF, RH;
+    float H21[9], F21[9];          /* the winners, row-major */
+    float R21[9], t21[3];          /* the accepted motion */
+    int32_t n_good[8];             /* CheckRT of the motion hypotheses in the reference's order: eight for H, four for F (the rest zero) */
+    float parallax[8];
+} orbx_two_view_result;
+
+/*   d_kps_un[f*capacity + i] : mvKeysUn of batch frame f; only .pt is read.  d_n_out[f] is clamped into [0, capacity].
+ *   d_matches12[p*capacity + i], d_n_matches[p] : exactly what the search wrote.  With prune != 0 an ACCEPTED pair's entries
+ *                     d_matches12[i] >= 0 with d_triangulated[i] == 0 become -1 and d_n_matches[p] is lowered by their number;
+ *                     a rejected pair's table is left as it is.  prune == 0 writes neither.
+ *   cam             : fx, fy, cx, cy, read as Pinhole::toK(); the distortion fields are not read.
+ *   sigma, iterations : TwoViewReconstruction's constructor arguments (1.0f, 200: inc/TwoViewReconstruction.h:37); sigma > 0,
+ *                     1 <= iterations <= 4096.  min_parallax, min_triangulated: 1.0f, 50 (:114-123).
+ *   rh_threshold    : RH > rh_threshold takes the homography, compared in binary32; the reference has 0.50f (:117), its own comment
+ *                     0.40-0.45.  Must lie in (0, 1): with SF == 0 and SH > 0, RH is 1 and H must be taken, as the F inliers are empty.
+ *   d_rand[(p*iterations + it)*8 + j] : the raw rand() values, ints of [0, 2^31 - 1], that the reference's set loop (:79-96) would
+ *                     draw: DUtils::Random::SeedRandOnce seeds once per PROCESS, so what the second Reconstruct call draws depends on
+ *                     every rand() before it; the caller draws.  The device applies DUtils/Random.cpp:47-50 and the swap-remove of
+ *                     :83-95 itself; a value outside the range is clamped onto the list.
+ *   d_result[p]     : see above.  d_p3d[(p*capacity + i)*3] = vP3D and d_triangulated[p*capacity + i] = vbTriangulated, indexed by
+ *                     the keypoint of frame 1 (CheckRT :811-812, :892-896): vP3D is written for every counted point, one with
+ *                     cosParallax >= 0.99998 included, whose flag stays 0.  Both are zero for i < n of frame 1 on a rejecting status;
+ *                     entries from n on are not touched.
+ * cv::SVD and the cv::Mat kernels are the library's own definitions: the sign and order freedom of an SVD can
+ * permute the 8 or 4 motion hypotheses against OpenCV's.  Asynchronous on the handle's stream; the workspace belongs to the handle.
+ * Out of scope: KannalaBrandt8::ReconstructWithTwoViews' cv::fisheye::undistortPoints prelude (KannalaBrandt8.cpp:211-226) - a fisheye
+ * caller passes undistorted points and the pinhole K of that prelude - and CreateInitialMapMonocular. */
+int orbx_reconstruct_two_views_device(orbx_handle* h, int n_pairs, int frame1_first, int frame1_step, int frame2_first, int frame2_step,
+                                      const orbx_keypoint* d_kps_un, const int* d_n_out, int capacity, int* d_matches12,
+                                      int* d_n_matches, const orbx_camera* cam, float sigma, int iterations, float min_parallax,
+                                      int min_triangulated, float rh_threshold, const int* d_rand, int prune,
+                                      orbx_two_view_result* d_result, float* d_p3d, uint8_t* d_triangulated);
+
 /* ---- next row (second half): ORBmatcher::SearchByProjection ---------------------------------------
  * For Nleft == -1 frames (monocular, rectified stereo, RGB-D).  MapPoints, poses and frustum tests belong to the tracker and
  * the map (out of scope), so they enter as plain arrays.  One search request per MapPoint: */
@@ -1191,6 +1254,9 @@ int orbx_debug_stereo_fisheye_stats(int* out1);
  * off by default, a launch then pays nothing for them).  The last counted launch, all pairs: out2[0] matches that took the SVD branch
  * (:590-611), out2[1] matches that took an UnprojectStereo branch (:612-619).  The read waits for the whole device. */
 int orbx_debug_new_map_points_enable(int on);
+/* orbx_reconstruct_two_views_device: which of its two hypothesis kernels the next launches take (process-wide): 1 = the rows of the 16x9 /
+ * 8x9 system over the lanes of the wave (the default), 0 = one lane out of LDS.  The results are the same bit for bit. */
+int orbx_debug_two_view_shape(int shape);
 int orbx_debug_new_map_points_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
