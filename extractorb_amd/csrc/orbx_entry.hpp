@@ -36,6 +36,17 @@ inline bool fitsLds(size_t bytes) { return bytes <= kLdsBudget; }
 constexpr size_t kBowMatchLdsBudget = 150 * 1024;
 inline int clampDistance(int d) { return d < 255 ? d : 255; }      // no descriptor distance exceeds 255: a larger bound accepts the same matches
 
+// Sim3Solver::SetRansacParameters' nIterations for N correspondences, before max(1, min(., maxIterations)) (reference src/Sim3Solver.cc:
+// 137-147): epsilon is a FLOAT, pow / log / ceil run in double, minInliers == N gives 1.  The reference assigns the double to an int: a value
+// outside the int range (epsilon^3 below 2^-53 gives log(1) = 0 and an infinite quotient) converts as its x86-64 build does, to INT_MIN.
+// N < 1 has no epsilon; such a problem never iterates and the entry stores 1.
+inline int sim3RansacIterations(double probability, int minInliers, int N) {
+    if (N < 1 || minInliers == N) return 1;
+    const float epsilon = (float)minInliers / N;
+    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow(epsilon, 3)));
+    return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : (-2147483647 - 1);
+}
+
 // ---- fills of a parameter block ---------------------------------------------------------------------------------------------------
 template <class P> inline void fillGridInverses(P& p, const float* bounds4) {
     p.wInv = (float)kGridCols / (bounds4[1] - bounds4[0]);      // mfGridElementWidthInv  (Frame.cc:339)

@@ -48,6 +48,7 @@ int newMapPointsTiles(int listCapacity);
 void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*, const Keypoint*, const Keypoint*, const float*, const float*, const int*, const NewMapPointsParams&, uint8_t*, float*, int*, uint8_t*, uint8_t*, int);
 void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const MapPointUpdateParams&);
 void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const int*, const TwoViewParams&, const TvWork&, void*, float*, uint8_t*, int);
+void launchSim3Solve(hipStream_t, const void*, const float*, const float*, const int*, const int*, const int*, const Sim3SolveParams&, const SsWork&, void*, uint8_t*, int, int);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
@@ -230,6 +231,13 @@ struct orbx_handle {
     // the two-view reconstruction's workspace (allocated on first use): what TvWork names, sized for (pairs, capacity, iterations)
     struct TwoViewShape { size_t pairs = 0, cap = 0, iters = 0; } twoView;
     TvWork twoViewWork = {};
+    // the Sim3 solver's workspace (allocated on first use): what SsWork names, sized for (problems, capacity, max_iterations); sim3Its is
+    // the table its[N] as last uploaded, for (sim3ItsProb, sim3ItsMin)
+    struct Sim3SolveShape { size_t problems = 0, cap = 0, iters = 0; } sim3Solve;
+    SsWork sim3SolveWork = {};
+    std::vector<int> sim3Its;
+    double sim3ItsProb = 0.0;
+    int sim3ItsMin = 0;
     // stereo matching (allocated on first use)
     struct StereoShape { int pairs = 0, cap = 0, rows = 0; } stereo;      // what the six buffers below are sized for
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;

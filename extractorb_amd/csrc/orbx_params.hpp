@@ -190,6 +190,15 @@ struct TvPrep { int status, n, n1, n2; float norm[8]; float T1[9], T2[9], T2inv[
 // [.. * 9] (model 0 = H, 1 = F); inl / counted / cosv [pair*capacity + k]
 struct TvWork { TvPrep* prep; int* first; int* second; float* score; float* mats; uint8_t* inl; uint8_t* counted; float* cosv; };
 
+struct Sim3SolveParams { int capacity, maxIterations, minInliers, nlevels; };      // k_sim3_solver.hip / k_sim3_solver.hpp
+constexpr int kSsMaxIterations = 4096;                    // the cap on orbx_sim3_solve_device's `max_iterations` (include/orbx.h)
+constexpr int kSsPointFloats = 12;                        // per correspondence: X3Dc1[3] X3Dc2[3] P1im1[2] P2im2[2] max1 max2, component-major
+// what the first kernel leaves for the other two, per problem
+struct SsPrep { int status, n, maxIts, n1; };
+// the workspace: prep[problem]; idx1 [problem*capacity + k] = mvnIndices1; pts [(problem*12 + c)*capacity + k] the twelve floats of
+// correspondence k (k_sim3_solver.hpp); counts [problem*maxIterations + it]; its [N], N = 0 .. capacity (SetRansacParameters' iterations)
+struct SsWork { SsPrep* prep; int* idx1; float* pts; int* counts; int* its; };
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

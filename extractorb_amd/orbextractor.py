@@ -33,6 +33,13 @@ TWO_VIEW_RESULT_DTYPE = np.dtype([("status", "<i4"), ("model", "<i4"), ("n_match
 assert TWO_VIEW_RESULT_DTYPE.itemsize == 224
 TWO_VIEW_STATUS = ("ACCEPTED_H", "ACCEPTED_F", "TOO_FEW_MATCHES", "BAD_INDEX", "ZERO_SCORES", "H_DEGENERATE", "H_AMBIGUOUS", "H_LOW_PARALLAX",
                    "H_FEW_POINTS", "H_BELOW_INLIER_SHARE", "F_FEW_POINTS", "F_AMBIGUOUS", "F_LOW_PARALLAX")
+# == orbx_sim3_problem / orbx_sim3_result / enum orbx_sim3_solve_status
+SIM3_PROBLEM_DTYPE = np.dtype([("n1", "<i4"), ("fix_scale", "<i4"), ("model1", "<i4"), ("model2", "<i4"), ("cam1", "<f4", 8), ("cam2", "<f4", 8),
+                               ("Tcw1", "<f4", 12), ("Tcw2", "<f4", 12), ("level_sigma2", "<f4", 16)])
+SIM3_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n", "<i4"), ("max_its", "<i4"), ("iterations", "<i4"), ("best_it", "<i4"), ("n_inliers", "<i4"),
+                              ("best_inliers", "<i4"), ("scale", "<f4"), ("R", "<f4", 9), ("t", "<f4", 3), ("T12", "<f4", 16)])
+assert SIM3_PROBLEM_DTYPE.itemsize == 240 and SIM3_RESULT_DTYPE.itemsize == 144
+SIM3_STATUS = ("CONVERGED", "NO_MORE", "TOO_FEW", "BAD_ARGUMENT")
 FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION = 0, 1      # orbx_frustum_mode
 (FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH, FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR,
  FRUSTUM_REQUEST) = range(7)                           # orbx_frustum_exit
@@ -222,6 +229,8 @@ def load_library():
                                                          C.c_int, vp, vp, vp, vp, vp, vp]
     L.orbx_debug_new_map_points_enable.argtypes = [C.c_int]
     L.orbx_debug_two_view_shape.argtypes = [C.c_int]
+    L.orbx_sim3_solve_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp]
+    L.orbx_debug_sim3_solve_steps.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -585,6 +594,17 @@ class ORBextractor:
             _dev(d_n_matches), _host_f32(cam), sigma, iterations, min_parallax, min_triangulated, rh_threshold, _dev(d_rand), int(prune),
             _dev(d_result), _dev(d_p3d), _dev(d_triangulated)))
 
+    def sim3_solve_device(self, n_problems, d_problems, capacity, d_x1w, d_x2w, d_octave1, d_octave2, d_rand, d_result, d_inliers,
+                          probability=0.99, min_inliers=15, max_iterations=300):
+        """Sim3Solver's constructor, SetRansacParameters and the iterate(20, ..) loop (reference src/Sim3Solver.cc, call site
+        src/LoopClosing.cc:673-684) for n_problems problems.  d_problems: SIM3_PROBLEM_DTYPE rows; d_x1w / d_x2w [(p*capacity + i)*3] the world
+        positions of pMP1 / pMP2 of slot i1 = i, d_octave1 / d_octave2 [p*capacity + i] the octaves of kp1 / kp2 (-1: the slot is absent);
+        d_rand [(p*max_iterations + it)*3 + j] the caller's raw rand() values (int32); d_result one SIM3_RESULT_DTYPE row per problem;
+        d_inliers [p*capacity + i] = vbInliers, all zero unless CONVERGED."""
+        self._check(self._L.orbx_sim3_solve_device(self._h, n_problems, _dev(d_problems), capacity, _dev(d_x1w), _dev(d_x2w), _dev(d_octave1),
+                                                   _dev(d_octave2), probability, min_inliers, max_iterations, _dev(d_rand), _dev(d_result),
+                                                   _dev(d_inliers)))
+
     def project_last_frame_device(self, n_pairs, last, cur, d_kps, d_kps_un, d_n, capacity, d_mp_flags, d_world, d_poses, cam, bounds,
                                   mbf, mb, th, mono, d_queries):
         """Front half of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (reference src/ORBmatcher.cc:1961-2023);
@@ -832,6 +852,10 @@ class ORBextractor:
         out = (C.c_int * 2)()
         self._check(self._L.orbx_debug_new_map_points_stats(out))
         return out[0], out[1]
+
+    def sim3_solve_steps(self, mask=7):
+        """which kernels sim3_solve_device launches (process-wide; tools/sim3_solver_rate.py): 1 prepare, 3 + hypotheses, 7 all (default)"""
+        self._check(self._L.orbx_debug_sim3_solve_steps(int(mask)))
 
     def search_by_projection_sim3_device(self, n_pairs, kf, mp, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, mp_capacity, d_mp_flags,
                                          d_poses, d_kps_un, d_desc, d_n, capacity, d_grid_off, d_grid_idx, bounds, cam, d_occupied, d_matches,

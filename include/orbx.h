@@ -334,6 +334,68 @@ int orbx_reconstruct_two_views_device(orbx_handle* h, int n_pairs, int frame1_fi
                                       int min_triangulated, float rh_threshold, const int* d_rand, int prune,
                                       orbx_two_view_result* d_result, float* d_p3d, uint8_t* d_triangulated);
 
+/* ---- loop closing, between SearchByBoW and SearchByProjection(pKF, Scw, ..): Sim3Solver ------------------------------------------
+ * Per loop candidate the reference runs SearchByBoW (orbx_search_by_bow_*), Sim3Solver, SearchByProjection(pKF, Scw, ..)
+ * (orbx_search_by_projection_sim3_device): src/LoopClosing.cc:595-760.  This entry is the middle link: Sim3Solver's constructor,
+ * SetRansacParameters(probability, min_inliers, max_iterations) and the iterate(20, bNoMore, vbInliers, nInliers, bConverge) loop until it
+ * converges or reports no more iterations (src/Sim3Solver.cc, call site LoopClosing.cc:673-684), for n_problems independent problems.
+ * How a problem left the solver; every way out has a name: */
+enum orbx_sim3_solve_status {
+    ORBX_SIM3_SOLVE_CONVERGED = 0,                 /* an iteration counted more than min_inliers inliers (:277-285) */
+    ORBX_SIM3_SOLVE_NO_MORE = 1,                   /* mRansacMaxIts iterations used up: the best Sim3 so far is returned, as the second overload does (:288-296) */
+    ORBX_SIM3_SOLVE_TOO_FEW = 2,                   /* N < min_inliers (:228) */
+    ORBX_SIM3_SOLVE_BAD_ARGUMENT = 3               /* what the reference would index out of bounds on: n1 outside [0, capacity], a model that is
+                                              * neither, an octave outside [-1, nlevels), N >= min_inliers with fewer than 3 correspondences */
+};
+/* One row per problem, in device memory: what the caller reads off pKF1 and pKF2. */
+typedef struct orbx_sim3_problem {
+    int32_t n1;                    /* vpMatched12.size(): the slots of this problem, <= capacity */
+    int32_t fix_scale;             /* bFixScale */
+    int32_t model1, model2;        /* pKF1->mpCamera, pKF2->mpCamera: 0 = Pinhole (cam[0..3] = fx, fy, cx, cy), 1 = KannalaBrandt8
+                                    * (cam = mvParameters as orbx_camera_kb8 lays them out); projectMat is virtual */
+    float cam1[8], cam2[8];
+    float Tcw1[12], Tcw2[12];      /* GetRotation() | GetTranslation() of pKF1, pKF2: 3x4 row-major */
+    float level_sigma2[ORBX_MAX_LEVELS];     /* mvLevelSigma2 (the two keyframes of one system share it); the handle's nlevels entries are read */
+} orbx_sim3_problem;
+/* One row per problem.  Every field computed before the exit holds its value, the rest is zero (best_it: -1). */
+typedef struct orbx_sim3_result {
+    int32_t status;                /* orbx_sim3_solve_status */
+    int32_t n;                     /* N, the correspondences: the present slots */
+    int32_t max_its;               /* mRansacMaxIts after SetRansacParameters */
+    int32_t iterations;            /* mnIterations at the return */
+    int32_t best_it;               /* the iteration (from 0) whose Sim3 is returned: the converging one, or the LAST of the greatest count */
+    int32_t n_inliers;             /* nInliers: the converging count, 0 otherwise */
+    int32_t best_inliers;          /* mnBestInliers */
+    float scale;                   /* mBestScale */
+    float R[9], t[3];              /* mBestRotation (row-major), mBestTranslation */
+    float T12[16];                 /* mBestT12, 4x4 row-major */
+} orbx_sim3_result;
+
+/*   d_problems[p]   : see above.
+ *   d_x1w, d_x2w [(p*capacity + i)*3] : GetWorldPos() of pMP1 = pKF1's MapPoint i and of pMP2 = vpMatched12[i].
+ *   d_octave1, d_octave2 [p*capacity + i] : the octave of kp1 = pKF1->mvKeysUn[indexKF1] and of kp2 = pKF2->mvKeysUn[indexKF2].  A slot is
+ *                     ABSENT when either is -1: that stands for every `continue` of :73-91 - no match, no MapPoint, isBad, an index < 0.
+ *                     isBad and GetIndexInKeyFrame stay with the caller.  With a non-empty vpKeyFrameMatchedMP, the only call in the
+ *                     reference, bDifferentKFs is false and pKFm is ALWAYS pKF2 (:40-45, :84-85): indexKF2 is pMP2's index in pKF2, and a
+ *                     point pKF2 does not observe is skipped.  Entries from n1 on are not read.
+ *   probability, min_inliers, max_iterations : SetRansacParameters' arguments (0.99, 15, 300 at the call site); probability in [0, 1],
+ *                     1 <= max_iterations <= 4096, n_problems * max_iterations < 2^31 (one workgroup per iteration).
+ *   d_rand[(p*max_iterations + it)*3 + j] : the raw rand() values, ints of [0, 2^31 - 1], of iteration `it` (see
+ *                     orbx_reconstruct_two_views_device: the caller draws).  The device applies DUtils/Random.cpp:47-50 and the swap-remove of
+ *                     :251-262 itself; a value outside the range is clamped onto the list.  Iterations from max_its on are not read.
+ *   d_result[p]     : see above.  d_inliers[p*capacity + i] = vbInliers[i1] (:280-282): all zero unless CONVERGED, as in the reference;
+ *                     entries from n1 on are not touched (none at all when n1 is outside [0, capacity]).
+ * cv::eigen, cv::Rodrigues and the cv::Mat expressions are the library's own definitions (k_sim3_solver.hpp states
+ * each), and so are the double atan2 / sin / cos under them.  Three points that align exactly give the reference's NaN rotation: 0 inliers,
+ * and every NaN of a result row is 0x7fc00000.  Asynchronous on the handle's stream.  The workspace belongs to the handle and grows to
+ * 4*(13*n_problems*capacity + n_problems*max_iterations + capacity + 1) + 16*n_problems bytes; when it grows, or when (probability,
+ * min_inliers) differ from the previous call's, the entry waits for the stream and uploads the table of SetRansacParameters' iteration
+ * counts, computed with the host's libm.  No LDS.  What follows the solver - gScm * gSmw (LoopClosing.cc:720-723), OptimizeSim3 - is the
+ * caller's.  Out of scope: the first iterate overload and find (no caller on this path; find's result follows from the same outputs). */
+int orbx_sim3_solve_device(orbx_handle* h, int n_problems, const orbx_sim3_problem* d_problems, int capacity, const float* d_x1w,
+                           const float* d_x2w, const int* d_octave1, const int* d_octave2, double probability, int min_inliers,
+                           int max_iterations, const int* d_rand, orbx_sim3_result* d_result, uint8_t* d_inliers);
+
 /* ---- next row (second half): ORBmatcher::SearchByProjection ---------------------------------------
  * For Nleft == -1 frames (monocular, rectified stereo, RGB-D).  MapPoints, poses and frustum tests belong to the tracker and
  * the map (out of scope), so they enter as plain arrays.  One search request per MapPoint: */
@@ -1257,6 +1319,9 @@ int orbx_debug_new_map_points_enable(int on);
 /* orbx_reconstruct_two_views_device: which of its two hypothesis kernels the next launches take (process-wide): 1 = the rows of the 16x9 /
  * 8x9 system over the lanes of the wave (the default), 0 = one lane out of LDS.  The results are the same bit for bit. */
 int orbx_debug_two_view_shape(int shape);
+/* orbx_sim3_solve_device: which of its three kernels the next calls launch (process-wide; tools/sim3_solver_rate.py times the steps by
+ * difference): 1 = prepare, 3 = prepare + hypotheses, 7 = all (the default).  Anything but 7 leaves the result rows unfinished. */
+int orbx_debug_sim3_solve_steps(int mask);
 int orbx_debug_new_map_points_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
