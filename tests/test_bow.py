@@ -264,6 +264,12 @@ def test_gpu_bow_on_extracted_frames():
 
 def test_vocabulary_errors(tmp_path):
     import torch
+
+    def fan(n):      # one node with n children
+        return dict(k=10, L=1, scoring=0, weighting=0, parent=np.zeros(n + 1, np.int32), is_leaf=np.r_[0, np.ones(n)].astype(np.uint8),
+                    desc=np.zeros((n + 1, 32), np.uint8), weight=np.ones(n + 1))
+    with pytest.raises(X.OrbxError, match="more than 256 children"):
+        X.Vocabulary(arrays=fan(257))                        # refused for its fan-out, before any device is touched: the child rank is packed into a byte
     if not torch.cuda.is_available():
         with pytest.raises(X.OrbxError):
             X.Vocabulary(path=tmp_path / "missing.txt")
@@ -278,3 +284,4 @@ def test_vocabulary_errors(tmp_path):
                 desc=np.zeros((301, 32), np.uint8), weight=np.ones(301))
     with pytest.raises(X.OrbxError):
         X.Vocabulary(arrays=wide)                            # 300 children under one node: the child rank is packed into a byte
+    assert X.Vocabulary(arrays=fan(256)).info()["n_words"] == 256      # the bound itself: 256 children have ranks 0 ... 255
