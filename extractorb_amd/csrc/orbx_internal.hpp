@@ -49,6 +49,7 @@ void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*,
 void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const MapPointUpdateParams&);
 void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const int*, const TwoViewParams&, const TvWork&, void*, float*, uint8_t*, int);
 void launchSim3Solve(hipStream_t, const void*, const float*, const float*, const int*, const int*, const int*, const Sim3SolveParams&, const SsWork&, void*, uint8_t*, int, int);
+void launchPoseOptimization(hipStream_t, const void*, const Keypoint*, const int*, const float*, const int*, const float*, const PoseOptParams&, float*, uint8_t*, void*, int);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);

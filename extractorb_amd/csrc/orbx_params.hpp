@@ -199,6 +199,11 @@ struct SsPrep { int status, n, maxIts, n1; };
 // correspondence k (k_sim3_solver.hpp); counts [problem*maxIterations + it]; its [N], N = 0 .. capacity (SetRansacParameters' iterations)
 struct SsWork { SsPrep* prep; int* idx1; float* pts; int* counts; int* its; };
 
+struct PoseOptParams {           // k_pose_optimization.hip / k_pose_optimization.hpp
+    int capacity, eyes, nMapPoints, nlevels;
+    int frameFirst, frameStep;                           // frames (eyes = 1) or RIG frames (eyes = 2: device frames 2r, 2r + 1; one pose per rig)
+};
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

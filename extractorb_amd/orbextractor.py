@@ -40,6 +40,13 @@ SIM3_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n", "<i4"), ("max_its", "<i4"
                               ("best_inliers", "<i4"), ("scale", "<f4"), ("R", "<f4", 9), ("t", "<f4", 3), ("T12", "<f4", 16)])
 assert SIM3_PROBLEM_DTYPE.itemsize == 240 and SIM3_RESULT_DTYPE.itemsize == 144
 SIM3_STATUS = ("CONVERGED", "NO_MORE", "TOO_FEW", "BAD_ARGUMENT")
+# == orbx_pose_problem / orbx_pose_result / enum orbx_pose_optimization_status
+POSE_PROBLEM_DTYPE = np.dtype([("model", "<i4"), ("model2", "<i4"), ("cam", "<f4", 8), ("cam2", "<f4", 8), ("mbf", "<f4"), ("Trl", "<f4", 12),
+                               ("inv_level_sigma2", "<f4", 16)])
+POSE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_initial", "<i4"), ("n_bad", "<i4"), ("n_inliers", "<i4"), ("rounds", "<i4"),
+                              ("empty_rounds", "<i4"), ("its", "<i4", 4), ("trials", "<i4", 4), ("lambda", "<f8", 4), ("chi2", "<f8", 4)])
+assert POSE_PROBLEM_DTYPE.itemsize == 188 and POSE_RESULT_DTYPE.itemsize == 120
+POSE_OPTIMIZATION_STATUS = ("ALL_ROUNDS", "FEW_EDGES", "TOO_FEW", "BAD_ARGUMENT")
 FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION = 0, 1      # orbx_frustum_mode
 (FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH, FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR,
  FRUSTUM_REQUEST) = range(7)                           # orbx_frustum_exit
@@ -231,6 +238,8 @@ def load_library():
     L.orbx_debug_two_view_shape.argtypes = [C.c_int]
     L.orbx_sim3_solve_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp]
     L.orbx_debug_sim3_solve_steps.argtypes = [C.c_int]
+    L.orbx_optimize_pose_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.orbx_debug_pose_optimization_launches.argtypes = []
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -604,6 +613,20 @@ class ORBextractor:
         self._check(self._L.orbx_sim3_solve_device(self._h, n_problems, _dev(d_problems), capacity, _dev(d_x1w), _dev(d_x2w), _dev(d_octave1),
                                                    _dev(d_octave2), probability, min_inliers, max_iterations, _dev(d_rand), _dev(d_result),
                                                    _dev(d_inliers)))
+
+    def optimize_pose_device(self, n_problems, frames, d_problems, d_kps, d_n, d_u_right, capacity, d_matches, d_mp_world, n_map_points, d_poses,
+                             d_outlier, d_result, eyes=1):
+        """Optimizer::PoseOptimization (reference src/Optimizer.cc:854-1168) for n_problems frames; frames = (first, step).  d_problems:
+        POSE_PROBLEM_DTYPE rows; d_kps / d_n / d_u_right (None: no stereo edge) of all frames; d_matches [row*capacity + i] indices into
+        d_mp_world [m*3], -1 = no MapPoint; d_poses [f*12] in/out; d_outlier [row*capacity + i] in/out (mvbOutlier); d_result one
+        POSE_RESULT_DTYPE row per problem.  eyes=2: frames are rigs (device frames 2f, 2f + 1; rows 2p, 2p + 1; one pose per rig)."""
+        self._check(self._L.orbx_optimize_pose_device(self._h, n_problems, frames[0], frames[1], eyes, _dev(d_problems), _dev(d_kps), _dev(d_n),
+                                                      _dev(d_u_right), capacity, _dev(d_matches), _dev(d_mp_world), n_map_points, _dev(d_poses),
+                                                      _dev(d_outlier), _dev(d_result)))
+
+    def debug_pose_optimization_launches(self):
+        """launches of the pose optimiser's kernel so far in this process (it has one launch form)"""
+        return self._L.orbx_debug_pose_optimization_launches()
 
     def project_last_frame_device(self, n_pairs, last, cur, d_kps, d_kps_un, d_n, capacity, d_mp_flags, d_world, d_poses, cam, bounds,
                                   mbf, mb, th, mono, d_queries):

@@ -396,6 +396,68 @@ int orbx_sim3_solve_device(orbx_handle* h, int n_problems, const orbx_sim3_probl
                            const float* d_x2w, const int* d_octave1, const int* d_octave2, double probability, int min_inliers,
                            int max_iterations, const int* d_rand, orbx_sim3_result* d_result, uint8_t* d_inliers);
 
+/* ---- tracking, between every pair of searches: Optimizer::PoseOptimization ---------------------------------------------------------
+ * The motion-only bundle adjustment of src/Optimizer.cc:854-1168 - TrackReferenceKeyFrame after SearchByBoW (src/Tracking.cc:2333),
+ * TrackWithMotionModel after the frame-to-frame SearchByProjection (:2492), TrackLocalMap after SearchLocalPoints (:2554-2560),
+ * Relocalization around its SearchByProjection (:3285, :3301, :3316) - for n_problems independent problems, one per frame: everything from
+ * :856 to the return at :1167.  The pose it writes is what orbx_frustum_requests_device and both frame-to-frame projection entries read as
+ * d_poses; the flags are mvbOutlier.  How a problem left the function; every way out has a name: */
+enum orbx_pose_optimization_status {
+    ORBX_POSE_OPTIMIZATION_ALL_ROUNDS = 0,         /* the four optimisations ran (:1060-1157) */
+    ORBX_POSE_OPTIMIZATION_FEW_EDGES = 1,          /* optimizer.edges().size() < 10 after round 0 (:1155): one round, the pose is round 0's */
+    ORBX_POSE_OPTIMIZATION_TOO_FEW = 2,            /* nInitialCorrespondences < 3 (:1050): returns 0, the pose is untouched, the flags of the edges are 0 */
+    ORBX_POSE_OPTIMIZATION_BAD_ARGUMENT = 3        /* what the reference would index out of bounds on: N outside [0, capacity], a camera model that is
+                                                    * neither, a match outside [-1, n_map_points), an octave outside [0, nlevels) on a keypoint with a
+                                                    * MapPoint.  Nothing but the result row is written */
+};
+/* One row per problem, in device memory: what the caller reads off the Frame. */
+typedef struct orbx_pose_problem {
+    int32_t model, model2;         /* mpCamera and, with eyes = 2, mpCamera2: 0 = Pinhole (cam[0..3] = fx, fy, cx, cy), 1 = KannalaBrandt8
+                                    * (cam = mvParameters as orbx_camera_kb8 lays them out); project and projectJac are virtual */
+    float cam[8], cam2[8];         /* the stereo edges read Frame::fx, fy, cx, cy from cam[0..3] */
+    float mbf;                     /* Frame::mbf (stereo edges) */
+    float Trl[12];                 /* Frame::mTrl, 3x4 row-major (right-eye edges) */
+    float inv_level_sigma2[ORBX_MAX_LEVELS];      /* mvInvLevelSigma2; the handle's nlevels entries are read */
+} orbx_pose_problem;
+/* One row per problem.  Every field computed before the exit holds its value, the rest is zero. */
+typedef struct orbx_pose_result {
+    int32_t status;                /* orbx_pose_optimization_status */
+    int32_t n_initial;             /* nInitialCorrespondences */
+    int32_t n_bad;                 /* nBad of the last round run */
+    int32_t n_inliers;             /* the return value: n_initial - n_bad, 0 for TOO_FEW */
+    int32_t rounds;                /* optimisations run: 0, 1 or 4 */
+    int32_t empty_rounds;          /* bit r: round r found NO edge at level 0 - initializeOptimization(0) builds no index mapping, optimize
+                                    * returns -1 at once, the estimate stays the initial pose and every edge is classified there */
+    int32_t its[4];                /* per round what optimize() returned: the LM iterations run, the terminating one included; -1 in an empty round */
+    int32_t trials[4];             /* per round the trials (_levenbergIterations) over its iterations */
+    double lambda[4], chi2[4];     /* per round _currentLambda and the robust chi2 (currentChi) when its last iteration ended */
+} orbx_pose_result;
+
+/*   frame_first, frame_step : problem p is frame f = frame_first + p*frame_step (no index may be negative).  eyes = 1: a one-camera frame
+ *                     (monocular, rectified stereo, RGB-D).  eyes = 2: f is a RIG (mpCamera2 != 0): its eyes are device frames 2f and 2f + 1, its
+ *                     rows of d_matches / d_outlier are 2p and 2p + 1, and d_poses holds one pose per rig.
+ *   d_problems[p]   : see above.
+ *   d_kps[f*capacity + i], d_n_out[f] : the observations and N.  eyes = 1: mvKeysUn (:911, :943).  eyes = 2: the RAW mvKeys of the left eye and
+ *                     mvKeysRight of the right (:982, :1013).  x, y and octave are read.
+ *   d_u_right[f*capacity + i] : mvuRight, or NULL (no stereo edge; required NULL with eyes = 2).  An entry that is NOT < 0 makes a stereo edge.
+ *   d_matches[row*capacity + i] : the per-keypoint match rows the projection and BoW searches write, as indices into d_mp_world; -1 = the
+ *                     keypoint holds no MapPoint.  d_mp_world[m*3] = GetWorldPos(), m < n_map_points.
+ *   d_poses[f*12]   : in/out, Frame::mTcw rows 0..2 (3x4 row-major), the layout orbx_frustum_requests_device reads.  Written on ALL_ROUNDS and
+ *                     FEW_EDGES; every NaN leaves as 0x7fc00000.
+ *   d_outlier[row*capacity + i] : in/out, mvbOutlier.  Entries from N on are not touched; entries without a MapPoint are left as they were;
+ *                     the others are written on every status but BAD_ARGUMENT.  Between the rounds they are the edges' level flags.
+ *   d_result[p]     : see above.
+ * g2o's and Eigen's arithmetic is the library's own definition (k_pose_optimization.hpp states each): the order of the
+ * 28 double sums is a function of the edge index alone (256 slots, then one fixed tree), so the result does not depend on the launch; the
+ * 6x6 system is solved by Cholesky, a pivot that is not positive fails the trial.  There is no depth test: a point behind the camera
+ * contributes, a point with z == 0 makes the trial's chi2 non-finite and the trial is rejected.  The classification reads the error of the
+ * LAST trial, rejected or not, as the reference's does.  Asynchronous on the handle's stream; one launch, one workgroup of 256 lanes per
+ * problem, 896 bytes of static LDS (four waves' partial sums) and nothing staged per keypoint: the capacity has no LDS bound.  No workspace.
+ * Out of scope: PoseInertialOptimization*, discarding the outlier MapPoints after the call (src/Tracking.cc:2336-2360: the caller's). */
+int orbx_optimize_pose_device(orbx_handle* h, int n_problems, int frame_first, int frame_step, int eyes, const orbx_pose_problem* d_problems,
+                              const orbx_keypoint* d_kps, const int* d_n_out, const float* d_u_right, int capacity, const int* d_matches,
+                              const float* d_mp_world, int n_map_points, float* d_poses, uint8_t* d_outlier, orbx_pose_result* d_result);
+
 /* ---- next row (second half): ORBmatcher::SearchByProjection ---------------------------------------
  * For Nleft == -1 frames (monocular, rectified stereo, RGB-D).  MapPoints, poses and frustum tests belong to the tracker and
  * the map (out of scope), so they enter as plain arrays.  One search request per MapPoint: */
@@ -1322,6 +1384,8 @@ int orbx_debug_two_view_shape(int shape);
 /* orbx_sim3_solve_device: which of its three kernels the next calls launch (process-wide; tools/sim3_solver_rate.py times the steps by
  * difference): 1 = prepare, 3 = prepare + hypotheses, 7 = all (the default).  Anything but 7 leaves the result rows unfinished. */
 int orbx_debug_sim3_solve_steps(int mask);
+/* orbx_optimize_pose_device has ONE launch form: the launches of its kernel so far in this process (one per accepted call). */
+int orbx_debug_pose_optimization_launches(void);
 int orbx_debug_new_map_points_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
