@@ -1174,11 +1174,17 @@ int oracle_features_in_area(const void* kpsUn, const int* gridOff, const int* gr
 // in double, adds the double of tcw, and rounds to float once (OpenCV 3.x GEMMSingleMul<float,double>).  OpenCV is absent from this
 // image, so this too is "parity unpinned" (DESIGN.md §2).
 // ---------------------------------------------------------------------------------------------
+// The order of the sum is the library's (gemmRow, k_match_helpers.hpp; DESIGN.md "parity unpinned"): it starts from the first product, not from
+// +0, is scaled, and the addend is added only where the expression has one.  Against a sum that starts from +0 and always adds (an addend or
+// +0) this differs in the sign of a zero only: three products of -0 and an addend of -0 give -0 here (so z = -0 gives invzc = -inf, :1998), and
+// -Rcw.t()*tcw of a zero tcw is -0.
 static void gemm3(const float* A /*3x3 row-major, row stride sa*/, int sa, bool transA, const float* b, double alpha, const float* c, float* out) {
     for (int r = 0; r < 3; r++) {
-        double s = 0;
-        for (int k = 0; k < 3; k++) s += (double)(transA ? A[k * sa + r] : A[r * sa + k]) * (double)b[k];
-        out[r] = (float)(s * alpha + (c ? (double)c[r] : 0.0));
+        double s = (double)(transA ? A[r] : A[r * sa]) * (double)b[0];
+        for (int k = 1; k < 3; k++) s += (double)(transA ? A[k * sa + r] : A[r * sa + k]) * (double)b[k];
+        s *= alpha;
+        if (c) s += (double)c[r];
+        out[r] = (float)s;
     }
 }
 
