@@ -8,7 +8,7 @@ There is no CPU fallback: importing works anywhere (so the C ABI can be inspecte
 extractor without the built library or without a HIP device raises.
 """
 from .orbextractor import (KEYPOINT_DTYPE, ORBextractor, OrbxError, build_library, library_path, load_library,
-                           compute_tables, describe_tables, compute_level_sizes, compute_cell_grid, header_symbols, camera, camera_kb8,
+                           compute_tables, describe_tables, describe_levels, DESCRIBE_LEVEL_FIELDS, compute_level_sizes, compute_cell_grid, header_symbols, camera, camera_kb8,
                            compute_image_bounds, pinned_empty, pinned_free, source_hash, Vocabulary, debug_set_option,
                            debug_reset_options, predict_scale, predict_scale_breakpoints, sim3_hamming_bound, PROJ_QUERY_DTYPE,
                            TRACK_RECORD_DTYPE, FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION, FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH,
@@ -17,7 +17,7 @@ from .orbextractor import (KEYPOINT_DTYPE, ORBextractor, OrbxError, build_librar
                            POSE_OPTIMIZATION_STATUS)
 
 __all__ = ["KEYPOINT_DTYPE", "ORBextractor", "OrbxError", "build_library", "library_path", "load_library",
-           "compute_tables", "describe_tables", "compute_level_sizes", "compute_cell_grid", "header_symbols", "camera", "camera_kb8", "compute_image_bounds", "pinned_empty", "pinned_free", "source_hash", "Vocabulary",
+           "compute_tables", "describe_tables", "describe_levels", "DESCRIBE_LEVEL_FIELDS", "compute_level_sizes", "compute_cell_grid", "header_symbols", "camera", "camera_kb8", "compute_image_bounds", "pinned_empty", "pinned_free", "source_hash", "Vocabulary",
            "debug_set_option", "debug_reset_options", "predict_scale", "predict_scale_breakpoints", "sim3_hamming_bound",
            "PROJ_QUERY_DTYPE", "TRACK_RECORD_DTYPE", "FRUSTUM_LOCAL_MAP", "FRUSTUM_RELOCALIZATION", "FRUSTUM_FLAG", "FRUSTUM_NEG_DEPTH",
            "FRUSTUM_NOT_IN_IMAGE", "FRUSTUM_DISTANCE", "FRUSTUM_VIEW_COS", "FRUSTUM_FAR", "FRUSTUM_REQUEST", "TWO_VIEW_RESULT_DTYPE", "TWO_VIEW_STATUS",

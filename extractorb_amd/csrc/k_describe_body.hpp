@@ -210,41 +210,95 @@ extern "C" int orbx_debug_desc_stamps(unsigned long long* out) { return (int)hip
 template <bool PB>
 struct DescLds {
     static constexpr int kPatches = 2 * kDescWaves * (PB ? kPbLds : kPatchLds), kWtabWords = 2 * 16 * (PB ? 12 : 8);
-    static constexpr int kWtabOff = (kPatches + 15) & ~15, kBytes = kWtabOff + 4 * kWtabWords;
+    // The rBRIEF pattern (4 KB).  The plain form stages it behind the patches, one 16-byte load per thread, and its loop reads LDS: the eight 16-byte
+    // global loads per wave of the loop were a quarter of the L1 look-ups of a kernel that is bound by them (139 -> 123 us per 512 frames; six
+    // workgroups per CU instead of seven).  The patch-blur form reads the __constant__ table in its loop: with the copy its LDS passes 32 000 bytes,
+    // four workgroups per CU instead of five (248 -> 260 us).  docs/history/r28_describe_chain.md.
+    static constexpr int kPatternBytes = PB ? 0 : 4096;
+    static constexpr int kSmem = kPatches + kPatternBytes;
+    static constexpr int kWtabOff = (kSmem + 15) & ~15, kBytes = kWtabOff + 4 * kWtabWords;
+    static_assert(kPatches % 16 == 0, "the pattern's float4 entries are 16-byte aligned");
 };
 
-// One workgroup = eight keypoint slots [8 chunk, 8 chunk + 8) of frame f.  smem: the patches (DescLds::kPatches bytes), wtab: the weight words.
+// One workgroup = eight keypoint slots [8 chunk, 8 chunk + 8) of frame f.  smem: the patches (DescLds::kPatches bytes) and, in the plain form, the pattern; wtab: the weight words.
 // One workgroup barrier (behind the weight table, a copy of the static one).  A wave whose level lies outside [levelLo, levelHi) belongs to another launch and leaves.
+// A wave goes to memory three times, one trip behind the other: the kernel's arguments (the level table dl among them, by value); then everything
+// whose address the arguments and the wave's first slot give - the frame's rows of the per-level counts, the level's geometry, the selection entry,
+// the weight words, the plain form's copy of the pattern and the patch blur's lane tables -; then the patch gather.  (The patch-blur form's loop
+// still reads the pattern behind IC_Angle: DescLds.)
 template <bool PB>
-__device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, int nlevels,
+__device__ __forceinline__ void describeBlock(const DescLevels& dl, int nlevels, const int (&firstSlot)[kMaxLevels],
                                               const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ blur,
                                               const uint2* __restrict__ sel, int selPerFrame,
                                               const int* __restrict__ levelCount, const int* __restrict__ levelLap,
                                               Keypoint* __restrict__ outK, uint8_t* __restrict__ outD, int capacity,
                                               int* __restrict__ nOut, int* __restrict__ monoOut,
-                                              Keypoint* __restrict__ outLevelK, int* __restrict__ outLevelCounts, int fewWaves,
-                                              uint8_t* smem, unsigned (*wtab)[16][PB ? 12 : 8], int chunk, int f, int levelLo, int levelHi) {
+                                              Keypoint* __restrict__ outLevelK, int* __restrict__ outLevelCounts,
+                                              uint8_t* smem, unsigned (*wtab)[16][PB ? 12 : 8], int fewWaves, int chunk, int f, int levelLo, int levelHi) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, hl = lane & 31;
     DSTAMP(0);
-    // the weight words: requested here, stored to LDS behind the level sums (nothing before the barrier needs them)
+    const int slot0 = __builtin_amdgcn_readfirstlane((chunk * kDescWaves + wave) * 2);   // wave-uniform
+    const int slot = slot0 + half;
+    // the selection entry: its address needs the frame and the slot only (clamped: a slot past the frame's slab reads its last entry and is idle)
+    const uint2 eRaw = sel[(long long)f * selPerFrame + min(slot, selPerFrame - 1)];
+    // the weight words: requested here, stored to LDS in front of the barrier (nothing before it needs them)
     constexpr int kWords = DescLds<PB>::kWtabWords;      // 384 (PB) / 256
     const unsigned* wsrc;
     if constexpr (PB) wsrc = &c_weightsPb.w[0][0][0]; else wsrc = &c_weightsPlain.w[0][0][0];
     const unsigned wA = wsrc[tid];
     unsigned wB = 0;
     if (kWords > 256 && tid < kWords - 256) wB = wsrc[256 + tid];
-    const int slot0 = __builtin_amdgcn_readfirstlane((chunk * kDescWaves + wave) * 2);   // wave-uniform
-    const int slot = slot0 + half;
-    // totals of this frame and the level this wave belongs to.  Two forms, by the launch (wave-uniform):
-    //  * few waves on the chip (small batches: the wave's own latency is the launch's): lane l < nlevels loads level l's first slot, count and
-    //    lapping count - one memory round trip for all levels -, running sums by four DPP steps inside the first row of 16 lanes (nlevels <=
-    //    kMaxLevels = 16), the wave's level by a ballot, its sums by v_readlane: one frame 37.0 -> 36.2 us;
-    //  * a full chip: a scalar loop - nlevels dependent round trips through the scalar cache, hidden behind the other waves, while three more
-    //    vector loads per wave cost L1 look-ups, which is what this kernel is short of (512 frames: 344 against 355 us with the form above).
-    int total = 0, totalLap = 0, level = 0, seqBase = 0, lapBase = 0, levelN, selOff;
+    // the plain form's copy of the rBRIEF pattern: one 16-byte load per thread, stored to LDS in front of the barrier
+    float4* const patL = (float4*)(smem + DescLds<PB>::kPatches);
+    float4 patS = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (!PB) patS = ((const float4*)c_patternF)[tid];
+    unsigned pbRun = 0, pbSrc = 0;
+    if constexpr (PB) { pbRun = c_pbRun[hl]; pbSrc = c_pbSrc[hl]; }
+    // the level this wave belongs to: the levels' first slots ascend from 0, and those of levels >= nlevels are INT_MAX (makeDescLevels)
+    int level = 0;
+#pragma unroll
+    for (int l = 1; l < kMaxLevels; l++) level += slot0 >= firstSlot[l] ? 1 : 0;
+    // its geometry - scalar loads of the argument block - and the frame's rows of the two count arrays in batches of eight scalar dwords (a batch may
+    // reach past the row, for the last frame past the arrays - kLevelCountPad -: what lies at or beyond nlevels is never used): all in flight with the
+    // loads above, one wait (the empty statement: see k_describe.hip)
+    const DescLevel& L = dl.lv[level];
+    int selOff = L.selOff, gw = L.w, gh = L.h, pyrStride = L.pyrStride, blurStride = L.blurStride, patchSizeI = L.patchSize;
+    float scale = L.scale;
+    long long pyrOff = L.pyrOff, pyrFrameBytes = L.pyrFrameBytes, blurOff = L.blurOff, blurFrameBytes = L.blurFrameBytes;
+    // (read through the constant address space - the quad-tree's launch wrote the counts, nothing of this launch does -, which is what makes these
+    //  scalar loads whatever stands in front of them)
+    typedef __attribute__((address_space(4))) const int* ConstInts;
+    const ConstInts cRow = (ConstInts)(levelCount + f * nlevels), lRow = (ConstInts)(levelLap + f * nlevels);
+    int c[8], lp[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) { c[k] = cRow[k]; lp[k] = lRow[k]; }
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : : "s"(c[0]), "s"(c[1]), "s"(c[2]), "s"(c[3]), "s"(c[4]), "s"(c[5]), "s"(c[6]), "s"(c[7]), "s"(lp[0]), "s"(lp[1]), "s"(lp[2]),
+                 "s"(lp[3]), "s"(lp[4]), "s"(lp[5]), "s"(lp[6]), "s"(lp[7]), "s"(selOff), "s"(gw), "s"(gh), "s"(pyrStride), "s"(blurStride),
+                 "s"(patchSizeI), "s"(scale), "s"(pyrOff), "s"(pyrFrameBytes), "s"(blurOff), "s"(blurFrameBytes));
+#endif
+    const uint8_t* pyrL = pyr + pyrOff + (long long)f * pyrFrameBytes;      // wave-uniform bases:
+    const uint8_t* blurL = blur + blurOff + (long long)f * blurFrameBytes;   // lanes add 32-bit offsets
+    // totals of this frame and the sums in front of the wave's level: scalar arithmetic with static indices
+    int total = 0, totalLap = 0, seqBase = 0, lapBase = 0, levelN = 0;
+    auto sumBatch = [&](int l0) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int l = l0 + k, cl = l < nlevels ? c[k] : 0, ll = l < nlevels ? lp[k] : 0;
+            if (l == level) { seqBase = total; lapBase = totalLap; levelN = cl; }
+            total += cl;
+            totalLap += ll;
+        }
+    };
+    // Two forms of the sums, by the launch (wave-uniform):
+    //  * few waves on the chip (small batches: the wave's own latency is the launch's): lane l < nlevels loads level l's count and lapping count, running
+    //    sums by four DPP steps inside the first row of 16 lanes (nlevels <= kMaxLevels = 16), the wave's sums by v_readlane - some twenty vector
+    //    instructions where the scalar form below takes a hundred scalar ones, one behind the other (one frame per call: 35.5 against 36.2 us);
+    //  * a full chip: the scalar form - its instructions hide behind the other waves, while two more vector loads per wave cost L1 look-ups, which
+    //    is what this kernel is short of.
     if (fewWaves) {
-        int myOff = 0x7fffffff, myCnt = 0, myLap = 0;
-        if (lane < nlevels) { myOff = lv[lane].selOff; myCnt = levelCount[f * nlevels + lane]; myLap = levelLap[f * nlevels + lane]; }
+        int myCnt = 0, myLap = 0;
+        if (lane < nlevels) { myCnt = levelCount[f * nlevels + lane]; myLap = levelLap[f * nlevels + lane]; }
         int incC = myCnt, incL = myLap;
         static_assert(kMaxLevels == 16, "the scan below covers one DPP row of 16 lanes");
         incC += __builtin_amdgcn_update_dpp(0, incC, 0x111, 0xF, 0xF, true); incL += __builtin_amdgcn_update_dpp(0, incL, 0x111, 0xF, 0xF, true);      // row_shr:1
@@ -252,35 +306,31 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
         incC += __builtin_amdgcn_update_dpp(0, incC, 0x114, 0xF, 0xF, true); incL += __builtin_amdgcn_update_dpp(0, incL, 0x114, 0xF, 0xF, true);      // row_shr:4
         incC += __builtin_amdgcn_update_dpp(0, incC, 0x118, 0xF, 0xF, true); incL += __builtin_amdgcn_update_dpp(0, incL, 0x118, 0xF, 0xF, true);      // row_shr:8
         total = __builtin_amdgcn_readlane(incC, kMaxLevels - 1); totalLap = __builtin_amdgcn_readlane(incL, kMaxLevels - 1);      // (lanes >= nlevels add 0)
-        level = __popcll(__ballot(slot0 >= myOff)) - 1;      // (level 0's first slot is 0: level >= 0; the first slots ascend)
         seqBase = __builtin_amdgcn_readlane(incC - myCnt, level); lapBase = __builtin_amdgcn_readlane(incL - myLap, level);
-        levelN = __builtin_amdgcn_readlane(myCnt, level); selOff = __builtin_amdgcn_readlane(myOff, level);
-        if (slot0 == 0 && outLevelCounts && lane < nlevels) outLevelCounts[f * nlevels + lane] = myCnt;
+        levelN = __builtin_amdgcn_readlane(myCnt, level);
     } else {
-        for (int l = 0; l < nlevels; l++) {
-            const int c = levelCount[f * nlevels + l], lp = levelLap[f * nlevels + l];
-            if (slot0 >= lv[l].selOff) { level = l; seqBase = total; lapBase = totalLap; }
-            total += c;
-            totalLap += lp;
-        }
-        selOff = lv[level].selOff;
-        levelN = levelCount[f * nlevels + level];
-        if (slot0 == 0 && outLevelCounts && lane < nlevels) outLevelCounts[f * nlevels + lane] = levelCount[f * nlevels + lane];
+    sumBatch(0);
+    static_assert(kMaxLevels == 16 && kLevelCountPad >= 16, "two batches of eight cover every level");
+    if (nlevels > 8) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) { c[k] = cRow[8 + k]; lp[k] = lRow[8 + k]; }
+        sumBatch(8);
     }
+    }
+    if (slot0 == 0 && outLevelCounts && lane < nlevels) outLevelCounts[f * nlevels + lane] = levelCount[f * nlevels + lane];
     if (slot0 == 0 && lane == 0) { nOut[f] = total; monoOut[f] = total - totalLap; }      // monoIndex after the loop (:1161)
     const bool mine = level >= levelLo && level < levelHi;      // (wave-uniform: the other launch of a blur split by level describes the other levels)
     const int i = slot - selOff;
     const bool active = mine && slot < selPerFrame && i < levelN;
-    (&wtab[0][0][0])[tid] = wA;      // (requested in front of the level sums: here by now)
+    (&wtab[0][0][0])[tid] = wA;
     if (kWords > 256 && tid < kWords - 256) (&wtab[0][0][0])[256 + tid] = wB;
-    const uint2 e = active ? sel[(long long)f * selPerFrame + slot] : make_uint2(0u, 0u);      // (in flight across the barrier)
+    if constexpr (!PB) patL[tid] = patS;
+    const uint2 e = active ? eRaw : make_uint2(0u, 0u);
     __syncthreads();
     if (!mine) return;
     if (__ballot(active) == 0) return;
     DSTAMP(1);
-    const int gw = lv[level].w, gh = lv[level].h, pyrStride = lv[level].pyrStride, blurStride = lv[level].blurStride;
-    const uint8_t* pyrL = pyr + lv[level].pyrOff + (long long)f * lv[level].pyrFrameBytes;      // wave-uniform bases:
-    const uint8_t* blurL = blur + lv[level].blurOff + (long long)f * lv[level].blurFrameBytes;   // lanes add 32-bit offsets
+    if constexpr (PB) asm volatile("" : "+v"(pbRun), "+v"(pbSrc));      // (keeps the two loads at the top, where they are written)
     int kx = e.x & 0xffff, ky = e.x >> 16;      // (orbx_device.hpp: the selection entry)
     const float response = (float)(e.y >> 24);
     // the quad-tree only emits points of the FAST rectangle; clamp anyway so a corrupted entry (or an idle half)
@@ -292,8 +342,6 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
     int m10 = 0, m01 = 0;
     uint8_t* blurT;
     int blurMis;
-    unsigned pbRun = 0, pbSrc = 0;
-    if constexpr (PB) { pbRun = c_pbRun[hl]; pbSrc = c_pbSrc[hl]; }      // (requested ahead of the tile's loads)
     if constexpr (PB) {
         // ---- stage the raw 43 x 44 tile, re-aligned: 8 lanes per tile row (6 load an 8-byte pair of source dwords - 4-byte aligned: one
         //      global_load_dwordx2 -, 11 re-aligned dwords stored), four rows per step: 11 load instructions per wave (dword loads: 22; the gather is bound
@@ -448,7 +496,8 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const int p = hl + 32 * j;        // test pair index; bit (p & 7) of descriptor byte (p >> 3)
-        const float4 pt = ((const float4*)c_patternF)[p];
+        float4 pt;
+        if constexpr (PB) pt = ((const float4*)c_patternF)[p]; else pt = patL[p];
         const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
         const unsigned r0 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(x0, b), __fmul_rn(y0, a)), kRintMagic));
         const unsigned q0 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b)), kRintMagic));
@@ -468,9 +517,8 @@ __device__ __forceinline__ void describeBlock(const LevelGeom* __restrict__ lv, 
     const int monoBefore = (seqBase - lapBase) + (i - lapRank);
     const int at = isLap ? total - 1 - lapBefore : monoBefore;
     float ox = (float)kx, oy = (float)ky;
-    const float scale = lv[level].scale;
     if (level != 0) { ox = __fmul_rn(ox, scale); oy = __fmul_rn(oy, scale); }
-    const float patchSize = (float)lv[level].patchSize;
+    const float patchSize = (float)patchSizeI;
     if (at < capacity) {
         if (hl == 0) {
             Keypoint k;

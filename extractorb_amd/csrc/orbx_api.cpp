@@ -157,6 +157,7 @@ int installGeometry(orbx_handle* h, int rows, int cols) {
     for (int i = 0; i < 4; i++) { h->colsOff[i] = colsOff[i]; h->colCoefOff[i] = colCoefOff[i]; }
     h->geomPlan = gp;
     h->geom = g;
+    h->descLevels = makeDescLevels(g.lv, g.nlevels);
     return ORBX_OK;
 }
 
@@ -310,9 +311,9 @@ int enqueueBatch(orbx_handle* h, int B, const uint8_t* d_imgs, int rows, int col
             Prof p(h, S_DESCRIBE, st);
             auto describe = [&](bool pb, int l0, int l1) {      // the keypoints of levels [l0, l1): their slots are [selOff(l0), selOff(l1))
                 pollute(st);
-                launchDescribe(st, h->d_lv, g.nlevels, h->d_pyr, h->d_blur, h->d_sel, g.selPerFrame, h->d_levelCount,
+                launchDescribe(st, h->descLevels, h->d_pyr, h->d_blur, h->d_sel, g.selPerFrame, h->d_levelCount,
                                h->d_levelLap, d_kps, d_desc, capacity, d_nOut, d_monoOut, d_levelK, d_levelCounts, pb, l0, l1,
-                               g.lv[l0].selOff, l1 < g.nlevels ? g.lv[l1].selOff : g.selPerFrame, f0, Bn);
+                               g.lv[l0].selOff, l1 < g.nlevels ? g.lv[l1].selOff : g.selPerFrame, f0, Bn, h->describeSums);
             };
             if (bp.splitL) {
                 // (side by side on two streams - the plain launch behind the blur on ITS stream, starting together with the per-keypoint one - measured
@@ -589,8 +590,9 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
         CREATE_TRY(hipMemsetAsync(h->d_leafBest, 0, n * sizeof(unsigned), h->stream));
         CREATE_ALLOC(h->d_leafCode, (size_t)2 * nlevels * h->octXT);
     }
-    CREATE_ALLOC(h->d_levelCount, sizeof(int) * max_batch * nlevels);
-    CREATE_ALLOC(h->d_levelLap, sizeof(int) * max_batch * nlevels);
+    // (k_describe reads a frame's rows in batches of eight dwords: the last frame's reach into the padding, whose values it never uses)
+    CREATE_ALLOC(h->d_levelCount, sizeof(int) * ((size_t)max_batch * nlevels + kLevelCountPad));
+    CREATE_ALLOC(h->d_levelLap, sizeof(int) * ((size_t)max_batch * nlevels + kLevelCountPad));
     CREATE_ALLOC(h->d_lap, sizeof(int) * 2 * max_batch);
     CREATE_ALLOC(h->d_lv, sizeof(LevelGeom) * kMaxLevels);
     CREATE_ALLOC(h->d_cells, sizeof(CellDesc) * h->cellCap);
@@ -607,6 +609,7 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     h->launch.blurSplit = envInt("ORBX_BLUR_SPLIT", -1);
     h->sharedUploadBytes = g_aids.sharedUploadBytes;
     h->twoEyesWalk = g_aids.twoEyesWalk == 1;
+    h->describeSums = g_aids.describeSums == 0 || g_aids.describeSums == 1 ? g_aids.describeSums : -1;
     h->twoEyesBowStage = g_aids.twoEyesBowStage != 0;
     h->launch.colsShape = g_aids.colsShape == 1 || g_aids.colsShape == 4 || g_aids.colsShape == 6 ? g_aids.colsShape : -1;
     h->colsCap = 0;
@@ -645,6 +648,7 @@ int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevel
     if (poison >= 0 || h->ldsPollute >= 0 || h->testFailAfterFast || h->launch.colsShape > 0 || h->sharedUploadBytes >= 0)
         h->policy += " test_aids=poison:" + std::to_string(poison) + ",lds_pollute:" + std::to_string(h->ldsPollute) + ",fail_after_fast:" + std::to_string((int)h->testFailAfterFast) +
                      ",pyr_cols_shape:" + std::to_string(h->launch.colsShape) + ",shared_upload_bytes:" + std::to_string(h->sharedUploadBytes);
+    if (h->describeSums >= 0) h->policy += " test_aid=describe_sums:" + std::to_string(h->describeSums);
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->launch.numCUs = cus;

@@ -20,6 +20,7 @@ int orbx_debug_set_option(const char* name, int value) {
     else if (n == "fail_after_fast") g_aids.failAfterFast = value;
     else if (n == "pyr_cols_shape") g_aids.colsShape = value;
     else if (n == "shared_upload_bytes") g_aids.sharedUploadBytes = value;
+    else if (n == "describe_sums") g_aids.describeSums = value;
     else if (n == "two_eyes_walk") g_aids.twoEyesWalk = value;
     else if (n == "two_eyes_bow_stage") g_aids.twoEyesBowStage = value;
     else return ORBX_ERR_BAD_ARGUMENT;
@@ -30,6 +31,33 @@ int orbx_debug_set_option(const char* name, int value) {
 int orbx_debug_describe_tables(unsigned* pb384, unsigned* plain256) {
     if (!pb384 || !plain256) return ORBX_ERR_BAD_ARGUMENT;
     describeTables(pb384, plain256);
+    return ORBX_OK;
+}
+
+// The level table k_describe takes by value (orbx_device.hpp: DescLevels) beside the LevelGeom table installGeometry fills it from, for the
+// geometry of a rows x cols image on a handle of max_batch frames; needs no device
+int orbx_debug_describe_levels(int nfeatures, float scale_factor, int nlevels, int rows, int cols, int max_batch, int* desc_nlevels,
+                               long long* desc176, long long* geom176) {
+    if (nlevels < 1 || nlevels > kMaxLevels || nfeatures < 1 || !(scale_factor > 1.0f) || max_batch < 1 || !desc_nlevels || !desc176 || !geom176)
+        return ORBX_ERR_BAD_ARGUMENT;
+    const ScaleTables t = makeScaleTables(nfeatures, scale_factor, nlevels);
+    FrameGeom g;
+    const std::string why = makeFrameGeom(t, rows, cols, g);
+    if (!why.empty()) return geometryRefusalCode(why);
+    layoutArenas(g, max_batch);
+    const DescLevels d = makeDescLevels(g.lv, g.nlevels);
+    *desc_nlevels = d.nlevels;
+    auto bits = [](float v) { unsigned u; std::memcpy(&u, &v, 4); return (long long)u; };
+    for (int l = 0; l < kMaxLevels; l++) {
+        const DescLevel& D = d.lv[l];
+        if (D.selOff != d.firstSlot[l]) return ORBX_ERR_UNSUPPORTED;      // (the level search's copy of the first slots)
+        const long long dv[11] = {D.selOff, D.w, D.h, D.pyrStride, D.blurStride, D.pyrOff, D.pyrFrameBytes, D.blurOff, D.blurFrameBytes, bits(D.scale),
+                                  D.patchSize};
+        const LevelGeom L = l < g.nlevels ? g.lv[l] : LevelGeom{};
+        const long long gv[11] = {L.selOff, L.w, L.h, L.pyrStride, L.blurStride, L.pyrOff, L.pyrFrameBytes, L.blurOff, L.blurFrameBytes, bits(L.scale),
+                                  L.patchSize};
+        for (int k = 0; k < 11; k++) { desc176[k * kMaxLevels + l] = dv[k]; geom176[k * kMaxLevels + l] = gv[k]; }
+    }
     return ORBX_OK;
 }
 

@@ -207,6 +207,39 @@ struct ColLevels {      // what the kernel needs of the level tables, by value (
     long long pyrOff[kMaxLevels], pyrFrameBytes[kMaxLevels];
 };
 
+// What k_describe reads of the level tables, by value (kernel argument: the wave's level comes from firstSlot and its first slot alone, and the
+// level's record is scalar loads of the kernel's own argument block - no load waits for another load before the level is known).  One record is
+// one 64-byte line of the argument block, the first slots are another: a wave touches two lines of the table, whatever its level.
+// firstSlot[l] (= lv[l].selOff) of a level l >= nlevels is INT_MAX, so that no slot is ever found to lie in such a level (makeDescLevels).
+struct DescLevel {
+    int selOff, w, h, pyrStride, blurStride, patchSize;      // LevelGeom's fields of the same names
+    float scale;
+    int pad;
+    long long pyrOff, pyrFrameBytes, blurOff, blurFrameBytes;
+};
+static_assert(sizeof(DescLevel) == 64, "one line per level");
+struct DescLevels {
+    int firstSlot[kMaxLevels];
+    DescLevel lv[kMaxLevels];
+    int nlevels, pad;
+};
+static_assert(offsetof(DescLevels, lv) == 64 && sizeof(DescLevels) == 64 + 64 * kMaxLevels + 8, "DescLevels layout");
+inline DescLevels makeDescLevels(const LevelGeom* lv, int nlevels) {
+    DescLevels d{};
+    d.nlevels = nlevels;
+    for (int l = 0; l < kMaxLevels; l++) d.firstSlot[l] = d.lv[l].selOff = 0x7fffffff;
+    for (int l = 0; l < nlevels && l < kMaxLevels; l++) {
+        DescLevel& L = d.lv[l];
+        d.firstSlot[l] = L.selOff = lv[l].selOff;
+        L.w = lv[l].w; L.h = lv[l].h; L.pyrStride = lv[l].pyrStride; L.blurStride = lv[l].blurStride; L.patchSize = lv[l].patchSize; L.scale = lv[l].scale;
+        L.pyrOff = lv[l].pyrOff; L.pyrFrameBytes = lv[l].pyrFrameBytes; L.blurOff = lv[l].blurOff; L.blurFrameBytes = lv[l].blurFrameBytes;
+    }
+    return d;
+}
+// The description reads a frame's rows of the per-level count arrays ([frame][nlevels]) in batches of eight dwords: the last frame's batches reach up
+// to this many entries past the arrays' end (orbx_create pads the two allocations; the values are never used).
+constexpr int kLevelCountPad = kMaxLevels;
+
 #ifdef __HIPCC__
 // The dynamically sized LDS block of a kernel.  (tools/octree_emu compiles k_octree.hip for the HOST to run it under sanitizers; its
 // shim defines this as a pointer to an exactly sized heap block, and ORBX_OCT_EMU_PAD > 0 puts poisoned red zones between the

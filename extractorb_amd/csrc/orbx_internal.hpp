@@ -62,8 +62,8 @@ bool fastCanCarryBlur(int, int);
 size_t octreeLdsBytes(int M, int P, int R, int XT);
 void launchOctree(hipStream_t, const LevelGeom*, int, const CellDesc*, int, const unsigned*, const unsigned*, int*, unsigned*,
                   unsigned*, unsigned short*, uint2*, int, int*, int*, const int*, int, int, int, int, const int*, bool, int, int, uint8_t*, LeafTables, bool);
-void launchDescribe(hipStream_t, const LevelGeom*, int, const uint8_t*, const uint8_t*, const uint2*, int, const int*,
-                    const int*, Keypoint*, uint8_t*, int, int*, int*, Keypoint*, int*, bool, int, int, int, int, int, int);
+void launchDescribe(hipStream_t, const DescLevels&, const uint8_t*, const uint8_t*, const uint2*, int, const int*,
+                    const int*, Keypoint*, uint8_t*, int, int*, int*, Keypoint*, int*, bool, int, int, int, int, int, int, int);
 bool checkUmax(const int* umax16);
 void describeTables(unsigned* pb384, unsigned* plain256);
 hipError_t runPackedSelfTest(hipStream_t, unsigned*, unsigned*);
@@ -116,6 +116,7 @@ struct TestAids {
     long long sharedUploadBytes = -1;      // "shared_upload_bytes": input copies of at least this size go through the device's shared copy queue (-1: 16 MiB)
     int failAfterFast = 0;    // "fail_after_fast": the next handle's first call with leaf tables returns between k_fast and k_octree (one shot)
     int twoEyesBowStage = -1; // "two_eyes_bow_stage": 0 = the two-eye BoW search reads the frame pair's descriptors from L2 whatever the capacity (the form of large capacities)
+    int describeSums = -1;    // "describe_sums": pins the form of k_describe's level sums (0: the scalar form of a full chip, 1: the lane form of small launches)
     int twoEyesWalk = 0;      // "two_eyes_walk": 1 = the two-eye projection search settles every pair by its walk instead of the fixed point
 };
 extern TestAids g_aids;
@@ -151,6 +152,7 @@ struct orbx_handle {
     uint2* d_sel = nullptr;
     int *d_levelCount = nullptr, *d_levelLap = nullptr, *d_lap = nullptr;
     LevelGeom* d_lv = nullptr;
+    DescLevels descLevels = {};         // what k_describe takes of the level table, by value (installGeometry fills it beside d_lv)
     CellDesc* d_cells = nullptr;
     ResizeX *d_rx = nullptr, *d_ry = nullptr;
     QuadRec* d_xq = nullptr;            // per level: the tile resize's dword-column records (FrameGeom::xq)
@@ -213,6 +215,7 @@ struct orbx_handle {
     long long sharedUploadBytes = -1;      // test aid "shared_upload_bytes" as orbx_create read it (-1: the default limit, uploadFrames)
     bool twoEyesBowStage = true;       // test aid "two_eyes_bow_stage" as orbx_create read it
     bool twoEyesWalk = false;          // test aid "two_eyes_walk" as orbx_create read it
+    int describeSums = -1;             // test aid "describe_sums" as orbx_create read it (-1: by the launch's size)
     hipEvent_t evUp[2] = {nullptr, nullptr};      // uploadFrames: the handle's stream -> the device's shared input-copy queue -> back
     hipStream_t aux2 = nullptr;        // the blur's side stream (pyramid -> {blur, FAST -> quad-tree} -> description), events per half-batch
     hipEvent_t evPyr[2] = {nullptr, nullptr}, evBlur[2] = {nullptr, nullptr};

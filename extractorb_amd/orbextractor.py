@@ -167,6 +167,8 @@ def load_library():
     L.orbx_debug_set_option.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "orbx_debug_describe_tables"):      # (an earlier build loaded through ORBX_LIBRARY for an A/B has no such export)
         L.orbx_debug_describe_tables.argtypes = [vp, vp]
+    if hasattr(L, "orbx_debug_describe_levels"):
+        L.orbx_debug_describe_levels.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, ip, vp, vp]
     L.orbx_debug_clock_probe.argtypes = [vp, C.c_int]
     L.orbx_debug_clock_read.argtypes = [vp, C.c_int, vp]
     L.orbx_debug_policy.restype = C.c_char_p
@@ -330,6 +332,7 @@ def debug_reset_options():
     debug_set_option("shared_upload_bytes", -1)
     debug_set_option("two_eyes_walk", 0)
     debug_set_option("two_eyes_bow_stage", -1)
+    load_library().orbx_debug_set_option(b"describe_sums", -1)      # (an earlier build loaded through ORBX_LIBRARY for an A/B has no such aid)
 
 
 # ---- handle-free host helpers (no GPU needed) -------------------------------------------------------------
@@ -340,6 +343,20 @@ def describe_tables():
     if rc != ORBX_OK:
         raise OrbxError(rc, "orbx_debug_describe_tables")
     return pb, plain
+
+
+DESCRIBE_LEVEL_FIELDS = ("selOff", "w", "h", "pyrStride", "blurStride", "pyrOff", "pyrFrameBytes", "blurOff", "blurFrameBytes", "scale_bits", "patchSize")
+
+
+def describe_levels(rows, cols, nfeatures=1000, scale_factor=1.2, nlevels=8, max_batch=1):
+    """(nlevels, desc, geom): the level table the description kernels take by value and the per-level geometry it is filled from, both int64
+    [11, 16] with the rows of DESCRIBE_LEVEL_FIELDS (include/orbx.h: orbx_debug_describe_levels)"""
+    desc = np.zeros((11, 16), np.int64); geom = np.zeros((11, 16), np.int64)
+    n = C.c_int()
+    rc = load_library().orbx_debug_describe_levels(nfeatures, scale_factor, nlevels, rows, cols, max_batch, C.byref(n), _ptr(desc), _ptr(geom))
+    if rc != ORBX_OK:
+        raise OrbxError(rc, "orbx_debug_describe_levels")
+    return n.value, desc, geom
 
 
 def compute_tables(nfeatures=1000, scale_factor=1.2, nlevels=8):

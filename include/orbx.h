@@ -1411,7 +1411,9 @@ int orbx_debug_last_split_level(const orbx_handle* h);
  * size), "shared_upload_bytes" (host-buffer batches whose input is at least this large copy it through the device's shared copy queue
  * and bring the results back by DMA, smaller ones use the handle's stream and a copy kernel; -1 = 16 MiB), "two_eyes_walk" (1: the two-eye
  * projection search settles every pair by its walk instead of the fixed point; 0 = by the decisions), "two_eyes_bow_stage" (0: the two-eye
- * BoW search reads the frame pair's descriptors from L2 whatever the capacity; -1 = staged in LDS where they fit).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
+ * BoW search reads the frame pair's descriptors from L2 whatever the capacity; -1 = staged in LDS where they fit), "describe_sums" (pins how the
+ * description kernels sum a frame's per-level counts: 0 = the scalar form of large launches, 1 = the lane form of small ones; -1 = by the
+ * launch's size).  Unknown name: ORBX_ERR_BAD_ARGUMENT. */
 int orbx_debug_set_option(const char* name, int value);
 
 /* IC_Angle's weight words, the static tables the description kernels fill their LDS copy from: pb384 = [2][16][12] words over the 44-byte tile
@@ -1419,6 +1421,13 @@ int orbx_debug_set_option(const char* name, int value);
  * u = k - 15); plane 0 holds u + 16 inside the disc's row (|u| <= umax[|v|], |u| <= 15), plane 1 holds 1 there, both 0 outside.  The host's copy
  * of the array the device's is initialised from: needs no device. */
 int orbx_debug_describe_tables(unsigned* pb384, unsigned* plain256);
+
+/* The level table the description kernels take by value, beside the per-level geometry it is filled from, for a rows x cols image on a handle
+ * of max_batch frames: both as [11][16] 64-bit values, rows = first selection slot, width, height, pyramid row stride, blurred row stride, pyramid
+ * offset, pyramid bytes per frame, blurred offset, blurred bytes per frame, scale factor (the float's bits), keypoint size; columns = levels.  In
+ * desc176 a level >= nlevels has INT_MAX as its first slot (no slot lies in it) and 0 elsewhere; in geom176 it is all 0.  Needs no device. */
+int orbx_debug_describe_levels(int nfeatures, float scale_factor, int nlevels, int rows, int cols, int max_batch, int* desc_nlevels,
+                               long long* desc176, long long* geom176);
 
 /* The launch-policy switches as orbx_create read them, "NAME=value" separated by blanks, "(env)" behind a value that came from an ORBX_<NAME>
  * environment variable (read once, at orbx_create; they choose between result-identical launch forms), and the test aids in force, if any.
