@@ -285,7 +285,10 @@ int enqueueBatch(orbx_handle* h, int B, const uint8_t* d_imgs, int rows, int col
             if (lt.hist) h->leafDirty = true;
             if (h->testFailAfterFast && lt.hist) { injected = true; h->testFailAfterFast = false; }      // (test aid: a call that dies between k_fast and k_octree)
             h->lastKernel[S_FAST] = k.fastKernel;
-            launchFast(st, h->d_cells, (int)g.cells.size(), h->d_lv, g.nlevels, h->d_pyr, h->iniTh, h->minTh, h->d_candSeg,
+            // iniThFAST < minThFAST (the reference takes any pair): the first call already returns everything above iniThFAST and the retry, at a
+            // higher threshold, can add nothing, so the cell's answer is the first call's.  The kernels suppress and list at the LOWER threshold
+            // (they fold it into the neighbour maximum), which is then iniThFAST: handed minThFAST they would lose the keys in between
+            launchFast(st, h->d_cells, (int)g.cells.size(), h->d_lv, g.nlevels, h->d_pyr, h->iniTh, std::min(h->iniTh, h->minTh), h->d_candSeg,
                        h->d_cellCount, g.maxRoiW, g.maxRoiH, f0, Bn, k.carry ? h->d_tiles + gp.blurItemOff[1] : nullptr,
                        h->d_laneItem + gp.blurLaneOff[1], gp.nBlurLanes[1], h->d_blur, lt, k.wide, g.big);
         }

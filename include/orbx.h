@@ -56,7 +56,8 @@ typedef struct orbx_handle orbx_handle; /* opaque */
 /* Replaces ORBextractor::ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST)
  * (inc/ORBextractor.h:50-51, ORBextractor.cc:408-475).  All device memory for images up to
  * max_width x max_height and batches up to max_batch frames is allocated here, once.
- * device < 0 selects the current HIP device. */
+ * device < 0 selects the current HIP device.  The thresholds are 1 ... 254 each, in either order
+ * (as the reference takes them: with ini_th_fast < min_th_fast the retry can add nothing). */
 int orbx_create(orbx_handle** out, int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
                 int min_th_fast, int max_width, int max_height, int max_batch, int device);
 void orbx_destroy(orbx_handle* h);
