@@ -3,9 +3,9 @@
 // device in the manner of k_camera_kb8.hpp.  TwoViewReconstruction::CheckRT (reference src/TwoViewReconstruction.cc:904) calls it through
 // `using namespace std` on a float.  tests/cpp/two_view_host_check.cpp compares it with the host libm on every float of [0.9, 1], on a
 // fixed stride over the rest of [-1, 1] and on the values outside the domain (which give NaN).
-// Plain arithmetic only: compiles for the host behind tests/cpp/host_shim.
+// Takes sqrtFloat32 from k_small_math.hpp.  Plain arithmetic only: compiles for the host behind tests/cpp/host_shim.
 #pragma once
-#include "k_camera_kb8.hpp"
+#include "k_small_math.hpp"
 
 namespace orbx {
 
@@ -30,11 +30,11 @@ __device__ __forceinline__ float acosFloat32(float x) {
         return __fsub_rn(pio2_hi, __fsub_rn(x, __fsub_rn(pio2_lo, __fmul_rn(r, x))));
     }
     if (neg) {                                                                                // x <= -0.5
-        const float z = __fmul_rn(__fadd_rn(1.0f, x), 0.5f), r = acosfRational(z), s = kb8Sqrt(z);
+        const float z = __fmul_rn(__fadd_rn(1.0f, x), 0.5f), r = acosfRational(z), s = sqrtFloat32(z);
         const float w = __fsub_rn(__fmul_rn(r, s), pio2_lo);
         return __fsub_rn(pi, __fmul_rn(2.0f, __fadd_rn(s, w)));
     }
-    const float z = __fmul_rn(__fsub_rn(1.0f, x), 0.5f), s = kb8Sqrt(z);                      // x >= 0.5
+    const float z = __fmul_rn(__fsub_rn(1.0f, x), 0.5f), s = sqrtFloat32(z);                      // x >= 0.5
     const float df = __uint_as_float(__float_as_uint(s) & 0xfffff000u);
     const float c = __fdiv_rn(__fsub_rn(z, __fmul_rn(df, df)), __fadd_rn(s, df));
     const float r = acosfRational(z), w = __fadd_rn(__fmul_rn(r, s), c);

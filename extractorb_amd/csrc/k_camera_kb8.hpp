@@ -5,10 +5,13 @@
 // rounded individually in binary32 (the reference's x86-64 build has no FMA), the sine / cosine polynomials in binary64 as libm has them.
 // Every Nleft != -1 / bRight branch projects with this: isInFrustumChecks (k_frustum_two_eyes_point.hpp) and Fuse's bRight
 // (k_fuse_two_eyes.hip) are built on it.  It is built once, here.  cos(psi) / sin(psi) on a float are taken as the float overloads (DESIGN.md §2 divergence (3)).
+// sqrtf is sqrtFloat32 of k_small_math.hpp, the one thing this header takes from another.
 // Plain arithmetic only: compiles for the host behind tests/cpp/host_shim (tests/cpp/kb8_host_check.cpp proves each routine against libm).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "k_small_math.hpp"
 
 namespace orbx {
 
@@ -119,15 +122,10 @@ __device__ __forceinline__ void kb8SinCos(float y, float* s_out, float* c_out) {
     *c_out = odd ? ps : pc;
 }
 
-// sqrtf.  Not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS HIP maps that name to the hardware's approximate root (1 ulp), which moved
-// 3 % of the projections by one float.  The correctly rounded binary64 root of a binary32 number, rounded to binary32, is the correctly
-// rounded binary32 root (53 >= 2 * 24 + 2 bits), and __dsqrt_rn is IEEE.
-__device__ __forceinline__ float kb8Sqrt(float x) { return (float)__dsqrt_rn((double)x); }
-
 // KannalaBrandt8::project: k = mvParameters[0..7] = fx, fy, cx, cy, k1, k2, k3, k4
 __device__ __forceinline__ void kb8Project(const float (&k)[8], float x, float y, float z, float& u, float& v) {
     const float x2y2 = __fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y));
-    const float theta = atan2f32(kb8Sqrt(x2y2), z);
+    const float theta = atan2f32(sqrtFloat32(x2y2), z);
     const float psi = atan2f32(y, x);
     const float theta2 = __fmul_rn(theta, theta), theta3 = __fmul_rn(theta, theta2), theta5 = __fmul_rn(theta3, theta2),
                 theta7 = __fmul_rn(theta5, theta2), theta9 = __fmul_rn(theta7, theta2);
@@ -138,5 +136,8 @@ __device__ __forceinline__ void kb8Project(const float (&k)[8], float x, float y
     u = __fadd_rn(__fmul_rn(__fmul_rn(k[0], r), c), k[2]);
     v = __fadd_rn(__fmul_rn(__fmul_rn(k[1], r), s), k[3]);
 }
+
+// sqrtFloat32's earlier name, ONLY for tests/cpp/kb8_host_check.cpp, which the existing tests build as it is; the library does not call it
+__device__ __forceinline__ float kb8Sqrt(float x) { return sqrtFloat32(x); }
 
 }  // namespace orbx

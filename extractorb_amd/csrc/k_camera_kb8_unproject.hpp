@@ -5,22 +5,17 @@
 //                       binary32 and s_sincosf.h's argument reduction in binary64), on every float (tests/cpp/kb8_unproject_host_check.cpp
 //                       compares every float of [-pi/2 - 1, pi/2 + 1], unproject's range plus slack, and a structured set outside it);
 //   kb8Unproject        :103-130, every operation rounded on its own in binary32;
-//   nullVector4         vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on a 4x4 binary32 matrix.  cv::SVD is OpenCV's
-//                       own Jacobi or LAPACK's sgesdd, by its build: this routine is the PROJECT'S definition, a one-sided
-//                       (Hestenes) Jacobi in binary32 with the constants below;
-//   kb8TriangulateMatches  :336-405 on the above.
+//   kb8TriangulateMatches  :336-405 on the above and on nullVector4 (k_small_svd.hpp: vt.row(3) of cv::SVD::compute on the 4x4 A).
+// Takes kb8Project and atan2f32 from k_camera_kb8.hpp, nullVector4 from k_small_svd.hpp, sqrtFloat32 from k_small_math.hpp, gemmRow and
+// dot3Double from k_match_helpers.hpp.
 // Plain arithmetic only: compiles for the host behind tests/cpp/host_shim (tests/cpp/kb8_unproject_host_check.cpp).
 #pragma once
 #include "k_camera_kb8.hpp"
 #include "k_match_helpers.hpp"
+#include "k_small_math.hpp"
+#include "k_small_svd.hpp"
 
 namespace orbx {
-
-// ---- nullVector4's constants (DESIGN.md §2 quotes them; tests/triangulation_two_eyes_walk.py states the same iteration) ----
-constexpr int kJacobiSweeps = 15;                    // cap on sweeps: the bound that ends a NaN or degenerate matrix
-constexpr float kJacobiEps = 0x1p-22f;               // a pair rotates when |p| > kJacobiEps * sqrt(a * b)  (2 * FLT_EPSILON)
-// pair order of a sweep: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
-constexpr float kJacobiPolishRatio = 64.0f;          // the correction step uses the columns whose squared norm exceeds this times the smallest
 
 // __kernel_tanf(x, y, iy) of k_tanf.c: tan(x + y) for iy = 1, -1 / tan(x + y) for iy = -1, |x| <= pi/4 (+ rounding)
 __device__ __forceinline__ float kernelTanf32(float x, float y, int iy) {
@@ -124,7 +119,7 @@ __device__ __forceinline__ void kb8Unproject(const float (&k)[8], float u, float
     const float pio2 = 1.5707963705e+00f, precision = 1e-6f;
     const float pwx = __fdiv_rn(__fsub_rn(u, k[2]), k[0]), pwy = __fdiv_rn(__fsub_rn(v, k[3]), k[1]);
     float scale = 1.0f;
-    float theta_d = kb8Sqrt(__fadd_rn(__fmul_rn(pwx, pwx), __fmul_rn(pwy, pwy)));
+    float theta_d = sqrtFloat32(__fadd_rn(__fmul_rn(pwx, pwx), __fmul_rn(pwy, pwy)));
     theta_d = kb8Fmin(kb8Fmax(-pio2, theta_d), pio2);
     if ((double)theta_d > 1e-8) {
         float theta = theta_d;
@@ -143,95 +138,6 @@ __device__ __forceinline__ void kb8Unproject(const float (&k)[8], float u, float
     }
     rx = __fmul_rn(pwx, scale);
     ry = __fmul_rn(pwy, scale);
-}
-
-// one pair of a sweep: columns i and j of the working matrix and of V
-__device__ __forceinline__ void jacobiPair4(float (&ai)[4], float (&aj)[4], float (&vi)[4], float (&vj)[4], bool& rotated) {
-    float a = 0.0f, b = 0.0f, p = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        a = __fadd_rn(a, __fmul_rn(ai[k], ai[k]));
-        b = __fadd_rn(b, __fmul_rn(aj[k], aj[k]));
-        p = __fadd_rn(p, __fmul_rn(ai[k], aj[k]));
-    }
-    if (!(fabsf(p) > __fmul_rn(kJacobiEps, kb8Sqrt(__fmul_rn(a, b))))) return;      // (a NaN never rotates)
-    rotated = true;
-    p = __fmul_rn(p, 2.0f);
-    const float beta = __fsub_rn(a, b), gamma = kb8Sqrt(__fadd_rn(__fmul_rn(p, p), __fmul_rn(beta, beta)));
-    float c, s;
-    if (beta < 0.0f) {
-        const float delta = __fmul_rn(__fsub_rn(gamma, beta), 0.5f);
-        s = kb8Sqrt(__fdiv_rn(delta, gamma));
-        c = __fdiv_rn(p, __fmul_rn(__fmul_rn(gamma, s), 2.0f));
-    } else {
-        c = kb8Sqrt(__fdiv_rn(__fadd_rn(gamma, beta), __fmul_rn(gamma, 2.0f)));
-        s = __fdiv_rn(p, __fmul_rn(__fmul_rn(gamma, c), 2.0f));
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float x0 = ai[k], x1 = aj[k], y0 = vi[k], y1 = vj[k];
-        ai[k] = __fadd_rn(__fmul_rn(c, x0), __fmul_rn(s, x1));
-        aj[k] = __fsub_rn(__fmul_rn(c, x1), __fmul_rn(s, x0));
-        vi[k] = __fadd_rn(__fmul_rn(c, y0), __fmul_rn(s, y1));
-        vj[k] = __fsub_rn(__fmul_rn(c, y1), __fmul_rn(s, y0));
-    }
-}
-
-// The right singular vector of A's smallest singular value.  A is row-major; out is NOT normalised in sign (it cancels in x / w).
-// One-sided Jacobi: the columns of A are rotated pairwise until a sweep rotates nothing or kJacobiSweeps sweeps are done; the rotations
-// accumulate in V; the column of smallest squared norm selects V's column, of equal norms the highest index (a NaN norm never wins: column 3).
-__device__ __forceinline__ void nullVector4(const float (&A)[16], float (&out)[4]) {
-    float c0[4], c1[4], c2[4], c3[4];
-    float v0[4] = {1.f, 0.f, 0.f, 0.f}, v1[4] = {0.f, 1.f, 0.f, 0.f}, v2[4] = {0.f, 0.f, 1.f, 0.f}, v3[4] = {0.f, 0.f, 0.f, 1.f};
-#pragma unroll
-    for (int r = 0; r < 4; r++) { c0[r] = A[4 * r]; c1[r] = A[4 * r + 1]; c2[r] = A[4 * r + 2]; c3[r] = A[4 * r + 3]; }
-    for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
-        bool rotated = false;
-        jacobiPair4(c0, c1, v0, v1, rotated);
-        jacobiPair4(c0, c2, v0, v2, rotated);
-        jacobiPair4(c0, c3, v0, v3, rotated);
-        jacobiPair4(c1, c2, v1, v2, rotated);
-        jacobiPair4(c1, c3, v1, v3, rotated);
-        jacobiPair4(c2, c3, v2, v3, rotated);
-        if (!rotated) break;
-    }
-    float n0 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        n0 = __fadd_rn(n0, __fmul_rn(c0[k], c0[k])); n1 = __fadd_rn(n1, __fmul_rn(c1[k], c1[k]));
-        n2 = __fadd_rn(n2, __fmul_rn(c2[k], c2[k])); n3 = __fadd_rn(n3, __fmul_rn(c3[k], c3[k]));
-    }
-    int sel = 3;
-    float best = n3;
-    if (n2 < best) { best = n2; sel = 2; }
-    if (n1 < best) { best = n1; sel = 1; }
-    if (n0 < best) { best = n0; sel = 0; }
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = sel == 0 ? v0[k] : sel == 1 ? v1[k] : sel == 2 ? v2[k] : v3[k];
-    // One correction step.  The rotations' roundings leave `out` with a component eps_i along each other column v_i of V; A*out, accumulated
-    // in binary64 from the ORIGINAL matrix, shows it: the rotated column c_i is sigma_i*u_i, so eps_i = (c_i . A*out) / |c_i|^2.  Taken only
-    // against columns whose squared norm is above kJacobiPolishRatio times the selected one (a column as small as the selected one spans
-    // the same null space, and its c_i is rounding noise).
-    double r[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        double acc = __dmul_rn((double)A[4 * k], (double)out[0]);
-#pragma unroll
-        for (int c = 1; c < 4; c++) acc = __dadd_rn(acc, __dmul_rn((double)A[4 * k + c], (double)out[c]));
-        r[k] = acc;
-    }
-    auto component = [&](const float (&c)[4], float n) {
-        double acc = __dmul_rn((double)c[0], r[0]);
-#pragma unroll
-        for (int k = 1; k < 4; k++) acc = __dadd_rn(acc, __dmul_rn((double)c[k], r[k]));
-        return __fdiv_rn((float)acc, n);
-    };
-    const float bound = __fmul_rn(kJacobiPolishRatio, best);
-    const float e0 = sel != 0 && n0 > bound ? component(c0, n0) : 0.0f, e1 = sel != 1 && n1 > bound ? component(c1, n1) : 0.0f,
-                e2 = sel != 2 && n2 > bound ? component(c2, n2) : 0.0f, e3 = sel != 3 && n3 > bound ? component(c3, n3) : 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        out[k] = __fsub_rn(__fsub_rn(__fsub_rn(__fsub_rn(out[k], __fmul_rn(e0, v0[k])), __fmul_rn(e1, v1[k])), __fmul_rn(e2, v2[k])), __fmul_rn(e3, v3[k]));
 }
 
 // what depends on the eye combination only: R12 (row-major), R21 = R12.t(), t21 = -R21*t12 (one gemm, alpha = -1; :365-366)
@@ -262,11 +168,8 @@ __device__ __forceinline__ float kb8TriangulateMatches(const float (&k1)[8], con
     float r21[3];
 #pragma unroll
     for (int r = 0; r < 3; r++) r21[r] = gemmRow(q.R12[3 * r], q.R12[3 * r + 1], q.R12[3 * r + 2], r2, 1.0, 0.f, false);
-    auto dot3 = [](float a0, float a1, float a2, float b0, float b1, float b2) {
-        return __dadd_rn(__dadd_rn(__dmul_rn((double)a0, (double)b0), __dmul_rn((double)a1, (double)b1)), __dmul_rn((double)a2, (double)b2));
-    };
-    const double dot = dot3(r1x, r1y, 1.0f, r21[0], r21[1], r21[2]);
-    const double n1 = __dsqrt_rn(dot3(r1x, r1y, 1.0f, r1x, r1y, 1.0f)), n2 = __dsqrt_rn(dot3(r21[0], r21[1], r21[2], r21[0], r21[1], r21[2]));
+    const double dot = dot3Double(r1x, r1y, 1.0f, r21[0], r21[1], r21[2]);
+    const double n1 = __dsqrt_rn(dot3Double(r1x, r1y, 1.0f, r1x, r1y, 1.0f)), n2 = __dsqrt_rn(dot3Double(r21[0], r21[1], r21[2], r21[0], r21[1], r21[2]));
     const float cosParallaxRays = (float)__ddiv_rn(dot, __dmul_rn(n1, n2));
     // From here on nothing returns early: every stage is computed for every lane and the FIRST failing test decides at the end.  The lanes
     // of a wave run in lockstep, so a lane that left early would wait for the others anyway, and each early return is a divergent region
@@ -290,7 +193,7 @@ __device__ __forceinline__ float kb8TriangulateMatches(const float (&k1)[8], con
 #pragma unroll
     for (int r = 0; r < 3; r++) x3D[r] = __fdiv_rn(vt[r], vt[3]);
     const float z1 = x3D[2];
-    const float z2 = (float)__dadd_rn(dot3(q.R21[6], q.R21[7], q.R21[8], x3D[0], x3D[1], x3D[2]), (double)q.t21[2]);
+    const float z2 = (float)__dadd_rn(dot3Double(q.R21[6], q.R21[7], q.R21[8], x3D[0], x3D[1], x3D[2]), (double)q.t21[2]);
     float pu, pv;
     kb8Project(k1, x3D[0], x3D[1], x3D[2], pu, pv);
     const float e1x = __fsub_rn(pu, u1), e1y = __fsub_rn(pv, v1);

@@ -7,7 +7,8 @@
 // It is a statement of its own and NOT projectIntoKeyFrame of k_keyframe_project.hpp: the bounds are Frame's FLOAT mnMinX .. mnMaxY with
 // NON-STRICT tests (uv.x < mnMinX || uv.x > mnMaxX, src/Frame.cc:520-523, src/ORBmatcher.cc:2209-2212), not KeyFrame's truncated, strict
 // ones; there is no cell window; the viewing-angle test has another form (below); the relocalisation path has no depth test at all.  What
-// is shared: gemmRow (cv::gemm, k_match_helpers.hpp) and predictScaleLevel (MapPoint::PredictScale as a count of breakpoints, that header).
+// is shared: gemmRow (cv::gemm) and dot3Double (cv::norm / Mat::dot) of k_match_helpers.hpp, and predictScaleLevel
+// (MapPoint::PredictScale as a count of breakpoints, k_keyframe_project.hpp).
 // The arithmetic is the reference's x86-64 build, every operation rounded on its own (-ffp-contract=off and the __f*_rn / __d*_rn
 // intrinsics).  Where the forms matter:
 //   * Pc_dist, dist = cv::norm of CV_32F: squares summed in double in element order, one square root, then float;
@@ -53,8 +54,7 @@ __device__ __forceinline__ int frustumPoint(const float* __restrict__ T, const f
     for (int r = 0; r < 3; r++) xc[r] = gemmRow(R[3 * r], R[3 * r + 1], R[3 * r + 2], xw, 1.0, tcw[r], true);      // mRcw*P+mtcw (Frame.cc:507, ORBmatcher.cc:2205)
     float depth = 0.f, invz = 0.f;
     if (local) {
-        const double c2 = __dadd_rn(__dadd_rn(__dmul_rn((double)xc[0], (double)xc[0]), __dmul_rn((double)xc[1], (double)xc[1])),
-                                    __dmul_rn((double)xc[2], (double)xc[2]));
+        const double c2 = dot3Double(xc[0], xc[1], xc[2], xc[0], xc[1], xc[2]);
         depth = (float)__dsqrt_rn(c2);                                               // Pc_dist = cv::norm(Pc) (:508)
         invz = __fdiv_rn(1.0f, xc[2]);                                               // :512, a float division, in front of the test
         if (xc[2] < 0.0f) return t.exit = kFrustumNegDepth;                          // :513 (z == 0 goes on).  The relocalisation path has NO depth test.
@@ -67,14 +67,12 @@ __device__ __forceinline__ int frustumPoint(const float* __restrict__ T, const f
     float Ow[3], PO[3];
     for (int r = 0; r < 3; r++) Ow[r] = gemmRow(R[r], R[3 + r], R[6 + r], tcw, -1.0, 0.f, false);      // mOw = -mRcw.t()*mtcw (Frame.cc:466-472, ORBmatcher.cc:2185)
     for (int r = 0; r < 3; r++) PO[r] = __fsub_rn(xw[r], Ow[r]);                     // :532 / :2215
-    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)PO[0]), __dmul_rn((double)PO[1], (double)PO[1])),
-                                __dmul_rn((double)PO[2], (double)PO[2]));
+    const double n2 = dot3Double(PO[0], PO[1], PO[2], PO[0], PO[1], PO[2]);
     const float dist = (float)__dsqrt_rn(n2);                                        // :533 / :2216
     if (dist < dst[0] || dist > dst[1]) return t.exit = kFrustumDistance;            // :535 / :2222, both ends pass
     float viewCos = 0.f;
     if (local) {
-        const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)nrm[0]), __dmul_rn((double)PO[1], (double)nrm[1])),
-                                     __dmul_rn((double)PO[2], (double)nrm[2]));
+        const double dot = dot3Double(PO[0], PO[1], PO[2], nrm[0], nrm[1], nrm[2]);
         viewCos = (float)__ddiv_rn(dot, (double)dist);                               // :545: a double quotient stored to float
         if (viewCos < p.viewCosLimit) return t.exit = kFrustumViewCos;               // :547
     }

@@ -12,8 +12,8 @@
 //     this frame and the reference reads what an earlier frame left there, which the caller passes in (prevDepth);
 //   * the left radius takes th (:69-70), the right one does not (:148).
 // Every operation is rounded on its own, in the forms the tree already has: gemmRow / gemmMat3 (cv::gemm, k_match_helpers.hpp), cv::norm and
-// Mat::dot accumulated in double in element order (the norm: one __dsqrt_rn, then float), predictScaleLevel (k_keyframe_project.hpp),
-// kb8Project (k_camera_kb8.hpp).  The cv::Mat roundings are parity unpinned, as Fuse's.
+// Mat::dot accumulated in double in element order (dot3Double, k_match_helpers.hpp; the norm: one __dsqrt_rn, then float), predictScaleLevel
+// (k_keyframe_project.hpp), kb8Project (k_camera_kb8.hpp).  The cv::Mat roundings are parity unpinned, as Fuse's.
 // Plain arithmetic only, nothing that talks to other lanes: also compiled for the HOST by the CPU suite (tests/cpp/frustum_two_eyes_host_check.cpp
 // behind tests/cpp/host_shim/kb8_shim.h).  A device word this header gains needs its stand-in there.
 #pragma once
@@ -69,8 +69,7 @@ __device__ __forceinline__ int frustumEyeCheck(const float* __restrict__ e, cons
     const float xw[3] = {xwp[0], xwp[1], xwp[2]};
     float xc[3];
     for (int r = 0; r < 3; r++) xc[r] = gemmRow(e[3 * r], e[3 * r + 1], e[3 * r + 2], xw, 1.0, e[9 + r], true);      // Pc = mR*P+mt (:1200)
-    const double c2 = __dadd_rn(__dadd_rn(__dmul_rn((double)xc[0], (double)xc[0]), __dmul_rn((double)xc[1], (double)xc[1])),
-                                __dmul_rn((double)xc[2], (double)xc[2]));
+    const double c2 = dot3Double(xc[0], xc[1], xc[2], xc[0], xc[1], xc[2]);
     const float depth = (float)__dsqrt_rn(c2);                                       // Pc_dist = cv::norm(Pc) (:1201)
     if (xc[2] < 0.0f) return t.exit = kFrustumNegDepth;                              // :1205 (z == 0 goes on)
     float u, v;
@@ -79,12 +78,10 @@ __device__ __forceinline__ int frustumEyeCheck(const float* __restrict__ e, cons
     if (v < p.minY || v > p.maxY) return t.exit = kFrustumNotInImage;                //   a NaN passes every one of the four, as it does there
     float PO[3];
     for (int r = 0; r < 3; r++) PO[r] = __fsub_rn(xw[r], e[12 + r]);                 // PO = P - twc (:1221)
-    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)PO[0]), __dmul_rn((double)PO[1], (double)PO[1])),
-                                __dmul_rn((double)PO[2], (double)PO[2]));
+    const double n2 = dot3Double(PO[0], PO[1], PO[2], PO[0], PO[1], PO[2]);
     const float dist = (float)__dsqrt_rn(n2);                                        // :1222
     if (dist < dst[0] || dist > dst[1]) return t.exit = kFrustumDistance;            // :1224, both ends pass
-    const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)nrm[0]), __dmul_rn((double)PO[1], (double)nrm[1])),
-                                 __dmul_rn((double)PO[2], (double)nrm[2]));
+    const double dot = dot3Double(PO[0], PO[1], PO[2], nrm[0], nrm[1], nrm[2]);
     const float viewCos = (float)__ddiv_rn(dot, (double)dist);                       // :1230: a double quotient stored to float
     if (viewCos < p.viewCosLimit) return t.exit = kFrustumViewCos;                   // :1232
     const float ratio = __fdiv_rn(dst[2], dist);                                     // mfMaxDistance itself (MapPoint.cc:519)

@@ -11,6 +11,7 @@
 // which differ in the last bit.  What follows (u, v) - IsInImage, the distance and normal tests, PredictScale, the cell window - is
 // keyFrameIsInImage + keyFrameWindow, stated apart so that a third user takes it as it is:
 //   k_fuse_two_eyes.hip  Fuse on a two-camera keyframe (NLeft != -1): its own pose per eye and KannalaBrandt8::project in front, then these two.
+// Takes gemmRow, dot3Double (cv::norm, Mat::dot) and the cell window from k_match_helpers.hpp.
 // Also compiled for the HOST by the CPU suite (tests/cpp/host_shim): a device word this header gains needs its stand-in there.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -57,13 +58,11 @@ __device__ __forceinline__ int keyFrameWindow(float u, float v, const float (&xw
     float PO[3];
     for (int r = 0; r < 3; r++) PO[r] = __fsub_rn(xw[r], Ow[r]);                     // :1483, :528
     // cv::norm of CV_32F: squares accumulated in double in element order, one square root, then float
-    const double n2 = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)PO[0]), __dmul_rn((double)PO[1], (double)PO[1])),
-                                __dmul_rn((double)PO[2], (double)PO[2]));
+    const double n2 = dot3Double(PO[0], PO[1], PO[2], PO[0], PO[1], PO[2]);
     const float dist3D = (float)__dsqrt_rn(n2);
     const float minDistance = dst[0], maxDistance = dst[1];
     if (dist3D < minDistance || dist3D > maxDistance) return kFrontDistance;         // :1487, :531
-    const double dot = __dadd_rn(__dadd_rn(__dmul_rn((double)PO[0], (double)nrm[0]), __dmul_rn((double)PO[1], (double)nrm[1])),
-                                 __dmul_rn((double)PO[2], (double)nrm[2]));
+    const double dot = dot3Double(PO[0], PO[1], PO[2], nrm[0], nrm[1], nrm[2]);
     if (dot < __dmul_rn(0.5, (double)dist3D)) return kFrontNormal;                   // :1496, :537
     const float ratio = __fdiv_rn(dst[2], dist3D);                                   // mfMaxDistance itself, not 1.2f * it (MapPoint.cc:519)
     const int level = predictScaleLevel(ratio, p);

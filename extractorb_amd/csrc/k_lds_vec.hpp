@@ -6,7 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifdef ORBX_HOST_ROW
+#if defined(ORBX_HOST_ROW) || !defined(__HIPCC__)
 #define ORBX_LDS
 namespace orbx { typedef uint4 LdsU4; }
 #else

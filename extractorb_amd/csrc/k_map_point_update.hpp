@@ -13,7 +13,7 @@
 // THE NORMAL AND DEPTH HALF is cv::Mat arithmetic (parity unpinned):
 //   centres      GetCameraCenter / GetRightCameraCenter are the records of k_rig_two_eyes.hpp (Ow = -Rcw.t()*tcw one gemmRow with alpha -1;
 //                twr = Rwl*mTlr.t + Ow one gemmRow with the float addend);
-//   normali      Pos - Owi, a float subtraction per element; cv::norm the sum of squares and the root in double;
+//   normali      Pos - Owi, a float subtraction per element; cv::norm the sum of squares (dot3Double, k_match_helpers.hpp) and the root in double;
 //   the sum      normal + normali/norm is cv::scaleAdd: normal[c] = fadd(fmul(normali[c], (float)(1.0/norm)), normal[c]), SEQUENTIALLY in
 //                list order, one float rounding per step (mpuUnit makes the products, mpuAccumulate adds them: never a tree).  EVERY entry
 //                counts, flagged or not: UpdateNormalAndDepth has no isBad() test;
@@ -64,8 +64,7 @@ __device__ __forceinline__ void mpuCentre(const float* poses, const MapPointUpda
 // cv::norm(Pos - Ow): the difference in float (d), squares summed and rooted in double
 __device__ __forceinline__ double mpuNorm(const float (&pos)[3], const float (&Ow)[3], float (&d)[3]) {
     for (int c = 0; c < 3; c++) d[c] = __fsub_rn(pos[c], Ow[c]);
-    return __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)d[0], (double)d[0]), __dmul_rn((double)d[1], (double)d[1])),
-                                __dmul_rn((double)d[2], (double)d[2])));
+    return __dsqrt_rn(dot3Double(d[0], d[1], d[2], d[0], d[1], d[2]));
 }
 
 // normali * (float)(1.0 / norm): the products of one entry's scaleAdd (:456-457, :462-463)

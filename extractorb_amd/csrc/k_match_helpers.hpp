@@ -1,6 +1,6 @@
 // k_match_helpers.hpp - the lines of the reference that every matcher kernel restates, stated ONCE: ORBmatcher::DescriptorDistance,
-// Frame / KeyFrame::GetFeaturesInArea's cell window, the rotation-histogram bin, ORBmatcher::ComputeThreeMaxima, the sorted best-key list and
-// cv::gemm on 3x3 data.  Their exact rounding and tie order are the reference's; a correction here reaches every kernel.  A new matcher entry
+// Frame / KeyFrame::GetFeaturesInArea's cell window, the rotation-histogram bin, ORBmatcher::ComputeThreeMaxima, the sorted best-key list,
+// cv::gemm on 3x3 data and Mat::dot / cv::norm on three floats (dot3Double, which the geometry entries take through k_small_math.hpp).  Their exact rounding and tie order are the reference's; a correction here reaches every kernel.  A new matcher entry
 // uses these and adds what it shares to this file.
 // Plain arithmetic only - nothing that talks to other lanes (that is k_wave_min.hpp) - so the kernels the CPU suite compiles for the HOST
 // (k_fuse.hip, k_project_sim3.hip, k_frustum_point.hpp behind tests/cpp/host_shim) can include it, and tests/cpp/match_helpers_check.cpp
@@ -99,6 +99,11 @@ __device__ __forceinline__ float gemmMat3Element(const float* A, int sa, const f
 __device__ __forceinline__ void gemmMat3(const float* A, int sa, const float* B, int sb, float* out) {
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) out[3 * r + c] = gemmMat3Element(A, sa, B, sb, r, c);
+}
+
+// Mat::dot / cv::norm's sum on CV_32F data: three products and two sums in binary64, in element order
+__device__ __forceinline__ double dot3Double(float a0, float a1, float a2, float b0, float b1, float b2) {
+    return __dadd_rn(__dadd_rn(__dmul_rn((double)a0, (double)b0), __dmul_rn((double)a1, (double)b1)), __dmul_rn((double)a2, (double)b2));
 }
 
 }  // namespace orbx

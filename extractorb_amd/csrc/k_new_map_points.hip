@@ -11,8 +11,8 @@
 //   STAGING: the pose records of the pair's two keyframes (2 keyframes x up to 2 eyes x kRigEyeFloats, k_rig_two_eyes.hpp) and the two
 //   level tables go to LDS once per workgroup, one element per lane, behind one barrier; a lane then reads the records of its own eyes.
 //   COUNT: d_n_new[p] += popcount(ballot(accepted)), one atomic per workgroup; the marks are atomic ORs (nmpMark).
-//   The SVD is skipped wave-uniformly when no lane of the wave takes that branch (nmpAny).
-// Registers (gfx950, kernel_table.json): k_new_map_points<0> 182 VGPRs, k_new_map_points<1> 164, no scratch, no spill, with the library's
+//   The SVD is skipped wave-uniformly when no lane of the wave takes that branch (waveAny).
+// Registers (gfx950, kernel_table.json): k_new_map_points<0> 178 VGPRs, k_new_map_points<1> 160, no scratch, no spill, with the library's
 // common flags (no TRI2_FLAGS: the first build showed no scalar spill).  Two waves per SIMD would fit; a pair's grid offers a handful
 // of waves to the whole device, so occupancy does not bound the call.
 #include <hip/hip_runtime.h>

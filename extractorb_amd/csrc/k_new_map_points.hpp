@@ -28,13 +28,17 @@
 // On a NaN pose every test is false: the match leaves as LOW_PARALLAX.
 // Nothing returns early between the branch and the end: every stage is computed for every lane and the FIRST failing test decides (as
 // kb8TriangulateMatches; the lanes of a wave run in lockstep).  The one region a wave skips is the SVD, when NO lane of it takes that branch
-// (nmpAny: a ballot on the device, the lane's own bit in the host build).
+// (waveAny: a ballot on the device, the lane's own bit in the host build).
+// Takes the KannalaBrandt8 camera from k_camera_kb8.hpp / k_camera_kb8_unproject.hpp, nullVector4 from k_small_svd.hpp, the Pinhole pair,
+// quietNaN and waveAny from k_small_math.hpp, gemmRow and dot3Double from k_match_helpers.hpp, the eye records from k_rig_two_eyes.hpp.
 // Plain arithmetic plus that one ballot: compiles for the host behind tests/cpp/host_shim (tests/cpp/new_map_points_host_check.cpp).
 #pragma once
 #include "k_camera_kb8_unproject.hpp"
 #include "k_lds_vec.hpp"
 #include "k_match_helpers.hpp"
 #include "k_rig_two_eyes.hpp"
+#include "k_small_math.hpp"
+#include "k_small_svd.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
 
@@ -50,12 +54,6 @@ enum {
 constexpr int kNmpThreads = 64;                           // matches of a workgroup, one per lane: one wave
 constexpr int kNmpRigFloats = 4 * kRigEyeFloats;          // the staged records of a pair: [keyframe 1 | 2][eye][kRigEyeFloats]
 constexpr int kNmpLdsFloats = kNmpRigFloats + 2 * kMaxLevels;      // ... then mvScaleFactors and mvLevelSigma2 (a lane indexes them by its octaves)
-
-#ifdef ORBX_HOST_ROW
-__device__ __forceinline__ bool nmpAny(bool b) { return b; }
-#else
-__device__ __forceinline__ bool nmpAny(bool b) { return __ballot(b) != 0ull; }
-#endif
 
 // one eye of a keyframe, as k_rig_two_eyes.hpp lays it out
 struct NmpPose { float R[9], t[3], Ow[3]; };
@@ -82,25 +80,21 @@ __device__ __forceinline__ float nmpStereoCos(float mb, float depth) {
     return c;
 }
 
-__device__ __forceinline__ double nmpDot3(float a0, float a1, float a2, float b0, float b1, float b2) {
-    return __dadd_rn(__dadd_rn(__dmul_rn((double)a0, (double)b0), __dmul_rn((double)a1, (double)b1)), __dmul_rn((double)a2, (double)b2));
-}
-
 // unproject / project of the match's camera: Pinhole on k[0..3], or KannalaBrandt8
 template <bool TwoEyes>
 __device__ __forceinline__ void nmpUnproject(const float (&k)[8], float u, float v, float& x, float& y) {
     if constexpr (TwoEyes) kb8Unproject(k, u, v, x, y);
-    else { x = __fdiv_rn(__fsub_rn(u, k[2]), k[0]); y = __fdiv_rn(__fsub_rn(v, k[3]), k[1]); }
+    else pinholeUnproject(k, u, v, x, y);
 }
 template <bool TwoEyes>
 __device__ __forceinline__ void nmpProject(const float (&k)[8], float x, float y, float z, float& u, float& v) {
     if constexpr (TwoEyes) kb8Project(k, x, y, z, u, v);
-    else { u = __fadd_rn(__fdiv_rn(__fmul_rn(k[0], x), z), k[2]); v = __fadd_rn(__fdiv_rn(__fmul_rn(k[1], y), z), k[3]); }
+    else pinholeProject(k, x, y, z, u, v);
 }
 
 // x, y, z of x3D in the eye (:629-640), then the reprojection gate of that keyframe (:643-663 / :670-688); behind = z <= 0
 __device__ __forceinline__ float nmpRowDot(const NmpPose& P, int r, const float (&x3D)[3]) {
-    return (float)__dadd_rn(nmpDot3(P.R[3 * r], P.R[3 * r + 1], P.R[3 * r + 2], x3D[0], x3D[1], x3D[2]), (double)P.t[r]);
+    return (float)__dadd_rn(dot3Double(P.R[3 * r], P.R[3 * r + 1], P.R[3 * r + 2], x3D[0], x3D[1], x3D[2]), (double)P.t[r]);
 }
 template <bool TwoEyes>
 __device__ __forceinline__ void nmpGate(const NmpPose& P, const float (&k)[8], const NmpObs& o, const float (&x3D)[3], float sigma2, float mbf,
@@ -138,9 +132,9 @@ __device__ __forceinline__ int nmpMatch(const NmpPose& P1, const NmpPose& P2, co
         ray1[r] = gemmRow(P1.R[r], P1.R[3 + r], P1.R[6 + r], xn1, 1.0, 0.f, false);
         ray2[r] = gemmRow(P2.R[r], P2.R[3 + r], P2.R[6 + r], xn2, 1.0, 0.f, false);
     }
-    const double n1 = __dsqrt_rn(nmpDot3(ray1[0], ray1[1], ray1[2], ray1[0], ray1[1], ray1[2])),
-                 n2 = __dsqrt_rn(nmpDot3(ray2[0], ray2[1], ray2[2], ray2[0], ray2[1], ray2[2]));
-    const float cosRays = (float)__ddiv_rn(nmpDot3(ray1[0], ray1[1], ray1[2], ray2[0], ray2[1], ray2[2]), __dmul_rn(n1, n2));
+    const double n1 = __dsqrt_rn(dot3Double(ray1[0], ray1[1], ray1[2], ray1[0], ray1[1], ray1[2])),
+                 n2 = __dsqrt_rn(dot3Double(ray2[0], ray2[1], ray2[2], ray2[0], ray2[1], ray2[2]));
+    const float cosRays = (float)__ddiv_rn(dot3Double(ray1[0], ray1[1], ray1[2], ray2[0], ray2[1], ray2[2]), __dmul_rn(n1, n2));
     // :578-587
     float cos1 = __fadd_rn(cosRays, 1.0f), cos2 = cos1;
     if (o1.stereo) cos1 = nmpStereoCos(p.mb, o1.depth);
@@ -152,7 +146,7 @@ __device__ __forceinline__ int nmpMatch(const NmpPose& P1, const NmpPose& P2, co
     stereoBranch = st1 || st2;
     int first = svd || stereoBranch ? -1 : kNmpLowParallax;
     x3D[0] = x3D[1] = x3D[2] = 0.0f;
-    if (nmpAny(svd)) {                                                                         // (wave-uniform)
+    if (waveAny(svd)) {                                                                         // (wave-uniform)
         float A[16], vt[4];
 #pragma unroll
         for (int c = 0; c < 4; c++) {
@@ -190,7 +184,7 @@ __device__ __forceinline__ int nmpMatch(const NmpPose& P1, const NmpPose& P2, co
     // :691-707
     const float a0 = __fsub_rn(x3D[0], P1.Ow[0]), a1 = __fsub_rn(x3D[1], P1.Ow[1]), a2 = __fsub_rn(x3D[2], P1.Ow[2]);
     const float b0 = __fsub_rn(x3D[0], P2.Ow[0]), b1 = __fsub_rn(x3D[1], P2.Ow[1]), b2 = __fsub_rn(x3D[2], P2.Ow[2]);
-    const float dist1 = (float)__dsqrt_rn(nmpDot3(a0, a1, a2, a0, a1, a2)), dist2 = (float)__dsqrt_rn(nmpDot3(b0, b1, b2, b0, b1, b2));
+    const float dist1 = (float)__dsqrt_rn(dot3Double(a0, a1, a2, a0, a1, a2)), dist2 = (float)__dsqrt_rn(dot3Double(b0, b1, b2, b0, b1, b2));
     const bool zeroDist = dist1 == 0.0f || dist2 == 0.0f;
     const bool far = p.farPoints && (dist1 >= p.thFarPoints || dist2 >= p.thFarPoints);
     const float ratioDist = __fdiv_rn(dist2, dist1), ratioOctave = __fdiv_rn(lev[2], lev[3]);
@@ -267,7 +261,7 @@ __device__ __forceinline__ bool nmpLane(int pair, int k, bool active, const ORBX
         o2 = nmpLoadObs<TwoEyes>(f2 + eye2, local2, kps, raw, uRight, depth, p);
     } else {
         eye1 = eye2 = 0;
-        o1.u = o1.v = __uint_as_float(0x7fc00000u); o1.ur = -1.0f; o1.depth = o1.rawU = o1.rawV = 0.0f; o1.octave = 0; o1.stereo = false;
+        o1.u = o1.v = quietNaN(); o1.ur = -1.0f; o1.depth = o1.rawU = o1.rawV = 0.0f; o1.octave = 0; o1.stereo = false;
         o2 = o1;
     }
     NmpPose P1, P2;

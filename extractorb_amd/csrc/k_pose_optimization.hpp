@@ -33,13 +33,17 @@
 //                normalisation (w < 0 negated, then divided by the norm), map, Quaterniond(Matrix3d) (the trace branch and the three
 //                diagonal branches), toRotationMatrix, Converter::toSE3Quat (float to double, then the quaternion) and toCvMat (narrowed);
 //   cameras      Pinhole / KannalaBrandt8 project and projectJac, Eigen overloads, as written: KB8 project narrows to float for atan2f and
-//                sqrtf (atan2f32, kb8Sqrt) and takes a DOUBLE cos / sin of psi (ssSinCos of |psi|, the sine's sign restored); projectJac a
-//                double atan2 (ssAtan2) and float products 3 * k1 ..; the stereo edge's invz is a float of a double quotient;
-//   NaN          every NaN leaves in the pose and the result row as one quiet NaN.
+//                sqrtf (atan2f32, sqrtFloat32) and takes a DOUBLE cos / sin of psi (sinCosDouble of |psi|, the sine's sign restored); projectJac a
+//                double atan2 (atan2Double) and float products 3 * k1 ..; the stereo edge's invz is a float of a double quotient;
+//   NaN          every NaN leaves in the pose and the result row as one quiet NaN (canonNaN).
 // One workgroup of kPoSlots lanes is one problem through all four rounds.  The pose, lambda and the LM state are uniform: every lane computes
 // them from the same reduced sums.  The host build (ORBX_HOST_ROW, tests/cpp/host_shim) runs the same function with the slots in a loop.
+// Takes atan2f32 from k_camera_kb8.hpp, sqrtFloat32 / atan2Double / sinCosDouble / canonNaN from k_small_math.hpp; nothing from another solver.
 #pragma once
-#include "k_sim3_solver.hpp"
+#include "k_camera_kb8.hpp"
+#include "k_small_math.hpp"
+#include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
@@ -67,7 +71,6 @@ struct PoArgs {                                           // what a problem read
     int n[2], cap, eyes, nMapPoints, nlevels;
 };
 
-__device__ __forceinline__ double poCanon(double x) { return x != x ? ssNaN() : x; }
 __device__ __forceinline__ double poSqrtOfFloat(double v) { return (double)(float)__dsqrt_rn(v); }      // deltaMono, deltaStereo
 
 // ---- Eigen's quaternion and g2o's SE3Quat ----------------------------------------------------------------------------------------------------
@@ -162,8 +165,8 @@ __device__ __forceinline__ void poToFloat(const PoSE3& T, float* out) {
 #pragma unroll
     for (int r = 0; r < 3; r++) {
 #pragma unroll
-        for (int c = 0; c < 3; c++) out[4 * r + c] = ssCanon((float)R[3 * r + c]);
-        out[4 * r + 3] = ssCanon((float)T.t[r]);
+        for (int c = 0; c < 3; c++) out[4 * r + c] = canonNaN((float)R[3 * r + c]);
+        out[4 * r + 3] = canonNaN((float)T.t[r]);
     }
 }
 __device__ __forceinline__ void poMat3(const double (&A)[9], const double (&B)[9], double (&C)[9]) {
@@ -183,7 +186,7 @@ __device__ __forceinline__ void poExp(const double (&x)[6], PoSE3& out) {
         for (int k = 0; k < 9; k++) { R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + Om[k]) + Om2[k]; V[k] = R[k]; }
     } else {
         double s, c;
-        ssSinCos(theta, s, c);
+        sinCosDouble(theta, s, c);
         const double th2 = theta * theta, a = __ddiv_rn(s, theta), b = __ddiv_rn(1.0 - c, th2), d = __ddiv_rn(theta - s, th2 * theta);
 #pragma unroll
         for (int k = 0; k < 9; k++) {
@@ -206,11 +209,11 @@ __device__ __forceinline__ void poProject(int model, const float (&k)[8], const 
         return;
     }
     const double x2y2 = X[0] * X[0] + X[1] * X[1];
-    const double theta = (double)atan2f32(kb8Sqrt((float)x2y2), (float)X[2]), psi = (double)atan2f32((float)X[1], (float)X[0]);
+    const double theta = (double)atan2f32(sqrtFloat32((float)x2y2), (float)X[2]), psi = (double)atan2f32((float)X[1], (float)X[0]);
     const double t2 = theta * theta, t3 = theta * t2, t5 = t3 * t2, t7 = t5 * t2, t9 = t7 * t2;
     const double r = (((theta + (double)k[4] * t3) + (double)k[5] * t5) + (double)k[6] * t7) + (double)k[7] * t9;
     double s, c;
-    ssSinCos(fabs(psi), s, c);
+    sinCosDouble(fabs(psi), s, c);
     if (psi < 0.0) s = -s;
     uv[0] = ((double)k[0] * r) * c + (double)k[2];
     uv[1] = ((double)k[1] * r) * s + (double)k[3];
@@ -222,7 +225,7 @@ __device__ __forceinline__ void poProjectJac(int model, const float (&k)[8], con
         return;
     }
     const double x2 = X[0] * X[0], y2 = X[1] * X[1], z2 = X[2] * X[2], r2 = x2 + y2, r = __dsqrt_rn(r2), r3 = r2 * r;
-    const double theta = ssAtan2(r, X[2]);
+    const double theta = atan2Double(r, X[2]);
     const double t2 = theta * theta, t3 = t2 * theta, t4 = t2 * t2, t5 = t4 * theta, t6 = t2 * t4, t7 = t6 * theta, t8 = t4 * t4, t9 = t8 * theta;
     const double f = (((theta + t3 * (double)k[4]) + t5 * (double)k[5]) + t7 * (double)k[6]) + t9 * (double)k[7];
     const double fd = (((1.0 + (double)__fmul_rn(3.0f, k[4]) * t2) + (double)__fmul_rn(5.0f, k[5]) * t4) + (double)__fmul_rn(7.0f, k[6]) * t6) +
@@ -590,7 +593,7 @@ __device__ __forceinline__ void poSolveProblem(int tid, const PoseProblem& pb, c
                 else nBadLm = 0;
                 if (nBadLm >= 3) break;
             }
-            if (tid == 0) { result->its[round] = cj; result->trials[round] = trials; result->lambda[round] = poCanon(lambda); result->chi2[round] = poCanon(currentChi); }
+            if (tid == 0) { result->its[round] = cj; result->trials[round] = trials; result->lambda[round] = canonNaN(lambda); result->chi2[round] = canonNaN(currentChi); }
         }
         // the classification: an active edge keeps the last trial's error, a flagged one is recomputed at the estimate
         PoFrame Fe = F;

@@ -18,18 +18,18 @@
 //                build does (cvttsd2si: INT_MIN), which max(1, .) turns into 1;
 //   sets         the three indices of an iteration from the CALLER'S raw rand() values r: randi = int(((double)r / 2147483648.0) * size)
 //                (DUtils/Random.cpp:47-50) clamped into [0, size - 1], idx = avail[randi], avail[randi] = avail.back(), pop_back (:251-262):
-//                tvDrawSet's statement (k_two_view.hpp) for three draws (ssDraw3);
+//                drawSet<3> (k_small_math.hpp; TwoViewReconstruction's sets are its K = 8);
 //   ComputeSim3  :316-427.  cv::reduce's row sums are left-to-right float sums, `C / P.cols` a float product with (float)(1.0 / 3);
 //                M = Pr2 * Pr1.t() one gemmRow per element; N's ten entries are FLOAT sums as written (assigned to doubles and narrowed again:
-//                no effect); the quaternion is ssEigenTop4; norm(vec) the double root of a double sum of double products; ang = atan2 in
-//                double (ssAtan2); `2 * ang * vec / norm(vec)` scales vec by (float)((2 * ang) * (1 / norm)) (as t / cv::norm(t) in
+//                no effect); the quaternion is topEigenvector4; norm(vec) the double root of a double sum of double products; ang = atan2 in
+//                double (atan2Double); `2 * ang * vec / norm(vec)` scales vec by (float)((2 * ang) * (1 / norm)) (as t / cv::norm(t) in
 //                k_two_view.hpp); cv::Rodrigues is ssRodrigues; P3 = R * Pr2 (gemm3); nom = Pr1.dot(P3) a double sum of double products in
 //                row-major order, den a double sum of the FLOAT squares (cv::pow), ms12i = (float)(nom / den), 1.0f when the scale is fixed;
 //                mt12i = O1 - ms12i * R * O2 one gemmRow per row with alpha = -s and the addend O1; sR = fmul(s, R); sRinv =
 //                fmul(R.t(), (float)(1.0 / s)); tinv = -sRinv * mt12i a gemmRow with alpha = -1;
-//   ssEigenTop4  cv::eigen's row 0 on the symmetric 4x4 N.  N is traceless and, with three points, has the eigenvalues +-(s1 + s2), +-(s1 - s2):
+//   quaternion   topEigenvector4 (k_small_svd.hpp): cv::eigen's row 0 on the symmetric 4x4 N.  N is traceless and, with three points, has the eigenvalues +-(s1 + s2), +-(s1 - s2):
 //                the top eigenvalue has a partner of equal size and opposite sign, which a one-sided iteration cannot tell apart.  So the
-//                iteration runs on N + mu * I, mu = the Frobenius norm of N (a float sum of float squares, left to right, kb8Sqrt) - positive
+//                iteration runs on N + mu * I, mu = the Frobenius norm of N (a float sum of float squares, left to right, sqrtFloat32) - positive
 //                semi-definite with the same eigenvectors, the top eigenvalue now the unique largest singular value: nullVector4's Hestenes
 //                iteration (jacobiAngle, kJacobiSweeps, pair order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)) on its columns with V from the
 //                identity; the column of LARGEST squared norm selects V's column, of equal norms (three collinear points: two equal top
@@ -38,12 +38,7 @@
 //                is >= 0 and ang lies in [0, pi / 2]);
 //   ssRodrigues  cv::Rodrigues of a float 1x3: in double theta = sqrt(rx^2 + ry^2 + rz^2); theta < DBL_EPSILON gives the identity; else
 //                c = cos, s = sin, c1 = 1 - c, r *= 1 / theta, R[i][j] = float((c * I[i][j] + c1 * r[i] * r[j]) + s * [r]x[i][j]);
-//   ssAtan2, ssSinCos   the double atan2 / sin / cos of the above, stated in plain binary64 operations so that the host build and the device
-//                agree by construction (k_acosf.hpp and atan2f32 are the precedent): atan of a ratio in [0, 1] by two half-angle steps
-//                t / (1 + sqrt(1 + t^2)) and twelve terms of the odd series, moved to the octant by pi / 2 and pi as hi + lo pairs;
-//                sin / cos by a three-part reduction against pi / 2 and the Taylor series to r^19 / r^20.  Not libm's roundings: how many
-//                float-rounded results differ from the host libm over a sweep is measured (docs/history/r24_sim3_solver.md).  ssAtan2 is
-//                stated for y >= 0 (a norm); a NaN argument gives NaN, ssSinCos of a NaN or of more than 2^20 gives NaN;
+//   atan2, sin, cos   atan2Double and sinCosDouble of k_small_math.hpp, not libm's;
 //   CheckInliers :430-454 per correspondence: P2 in image 1 under mT12i, P1 in image 2 under mT21i, dist.dot(dist) a double sum of double
 //                products narrowed to float, err1 < max1 && err2 < max2.  A point with z <= 0 projects as the arithmetic says;
 //   iterate      sequential semantics, stated once.  mnBestInliers starts at 0 and the update test is >=: the first iteration always becomes
@@ -55,12 +50,19 @@
 //   NaN          three points that align exactly (P1 == P2) give a quaternion whose imaginary part is exactly 0: ang = 0, norm = 0,
 //                2 * ang / norm = 0 * inf = NaN, a NaN rotation, 0 inliers - and, by >=, a "best" when no count is above 0.  The statement
 //                keeps that.  Which NaN 0 * inf gives differs between host and device arithmetic: every NaN leaves in the result row as THE
-//                quiet NaN 0x7fc00000 (ssCanon).
+//                quiet NaN (canonNaN, k_small_math.hpp).
 // One workgroup is ONE WAVE everywhere (kSsLanes lanes); the host build (ORBX_HOST_ROW, tests/cpp/host_shim) runs the same functions with a
 // wave of one lane.
+// Takes kb8Project from k_camera_kb8.hpp, topEigenvector4 / gemm3 from k_small_svd.hpp, drawSet / atan2Double / sinCosDouble /
+// pinholeProject / transformPoint / canonNaN from k_small_math.hpp, gemmRow / dot3Double from k_match_helpers.hpp, the parameter blocks from
+// orbx_params.hpp.
 #pragma once
-#include "k_new_map_points.hpp"
+#include "k_camera_kb8.hpp"
+#include "k_match_helpers.hpp"
+#include "k_small_math.hpp"
 #include "k_small_svd.hpp"
+#include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
@@ -85,9 +87,6 @@ constexpr int kSsLanes = 1;
 constexpr int kSsLanes = 64;
 #endif
 
-__device__ __forceinline__ float ssCanon(float x) { return x != x ? __uint_as_float(0x7fc00000u) : x; }
-__device__ __forceinline__ double ssNaN() { return (double)__uint_as_float(0x7fc00000u); }
-
 // mvnMaxError: (size_t)(9.210 * sigmaSquare), then the float the comparison converts it to
 __device__ __forceinline__ float ssMaxError(float sigma2) {
     const double v = __dmul_rn(9.210, (double)sigma2);
@@ -95,124 +94,7 @@ __device__ __forceinline__ float ssMaxError(float sigma2) {
     return (float)(unsigned long long)(v < 1.0e19 ? v : 1.0e19);
 }
 
-// the three indices of one iteration from three raw rand() values
-__device__ __forceinline__ void ssDraw3(const int* __restrict__ r3, int N, int (&idx)[3]) {
-    int slot[3], val[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int size = N - j;
-        int randi = (int)__dmul_rn(__ddiv_rn((double)r3[j], 2147483648.0), (double)size);
-        randi = max(0, min(randi, size - 1));
-        int va = randi, vb = size - 1;
-#pragma unroll
-        for (int t = 0; t < j; t++) {                       // ascending: the latest displacement of a slot wins
-            if (slot[t] == randi) va = val[t];
-            if (slot[t] == size - 1) vb = val[t];
-        }
-        idx[j] = va; slot[j] = randi; val[j] = vb;
-    }
-}
-
-// ---- the double functions -----------------------------------------------------------------------------------------------------------------
-// atan(t), 0 <= t <= 1
-__device__ __forceinline__ double ssAtanUnit(double t) {
-    const double t1 = __ddiv_rn(t, __dadd_rn(1.0, __dsqrt_rn(__dadd_rn(1.0, __dmul_rn(t, t)))));
-    const double t2 = __ddiv_rn(t1, __dadd_rn(1.0, __dsqrt_rn(__dadd_rn(1.0, __dmul_rn(t1, t1)))));      // <= tan(pi / 16)
-    const double z = __dmul_rn(t2, t2);
-    double acc = __ddiv_rn(1.0, 23.0);
-#pragma unroll
-    for (int k = 10; k >= 0; k--) acc = __dsub_rn(__ddiv_rn(1.0, (double)(2 * k + 1)), __dmul_rn(z, acc));
-    return __dmul_rn(4.0, __dmul_rn(t2, acc));
-}
-// atan2(y, x) for y >= 0
-__device__ __forceinline__ double ssAtan2(double y, double x) {
-    const double pio2Hi = 0x1.921fb54442d18p+0, pio2Lo = 0x1.1a62633145c07p-54, piHi = 0x1.921fb54442d18p+1, piLo = 0x1.1a62633145c07p-53;
-    if (y != y || x != x) return ssNaN();
-    const double ax = fabs(x), big = y > ax ? y : ax, small = y > ax ? ax : y;
-    double a = big == 0.0 ? 0.0 : ssAtanUnit(big == small ? 1.0 : __ddiv_rn(small, big));        // (inf / inf is atan(1))
-    if (y > ax) a = __dadd_rn(__dsub_rn(pio2Hi, a), pio2Lo);
-    if (x < 0.0) a = __dadd_rn(__dsub_rn(piHi, a), piLo);
-    return a;
-}
-__device__ __forceinline__ void ssSinCos(double theta, double& s, double& c) {
-    if (!(theta >= 0.0 && theta < 1048576.0)) { s = c = ssNaN(); return; }
-    const double twoOverPi = 0x1.45f306dc9c883p-1, p1 = 0x1.921fb54400000p+0, p2 = 0x1.0b4611a600000p-34, p3 = 0x1.3198a2e037073p-69;
-    const int k = (int)__dadd_rn(__dmul_rn(theta, twoOverPi), 0.5);
-    const double kd = (double)k;
-    const double r = __dsub_rn(__dsub_rn(__dsub_rn(theta, __dmul_rn(kd, p1)), __dmul_rn(kd, p2)), __dmul_rn(kd, p3));
-    const double z = __dmul_rn(r, r);
-    // sin r = r * (1 - z/3! + ... - z^9/19!), cos r = 1 - z/2! + ... + z^10/20!
-    const double sd[10] = {1.0, 6.0, 120.0, 5040.0, 362880.0, 39916800.0, 6227020800.0, 1307674368000.0, 355687428096000.0, 121645100408832000.0};
-    const double cd[11] = {1.0, 2.0, 24.0, 720.0, 40320.0, 3628800.0, 479001600.0, 87178291200.0, 20922789888000.0, 6402373705728000.0,
-                           2432902008176640000.0};
-    double ps = __ddiv_rn(1.0, sd[9]), pc = __ddiv_rn(1.0, cd[10]);
-#pragma unroll
-    for (int i = 8; i >= 0; i--) ps = __dsub_rn(__ddiv_rn(1.0, sd[i]), __dmul_rn(z, ps));
-#pragma unroll
-    for (int i = 9; i >= 0; i--) pc = __dsub_rn(__ddiv_rn(1.0, cd[i]), __dmul_rn(z, pc));
-    const double sr = __dmul_rn(r, ps), cr = pc;
-    const int quad = k & 3;
-    s = quad == 0 ? sr : quad == 1 ? cr : quad == 2 ? -sr : -cr;
-    c = quad == 0 ? cr : quad == 1 ? -sr : quad == 2 ? -cr : sr;
-}
-
-// ---- cv::eigen's row 0 and cv::Rodrigues ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ssJacobiPair4(float (&ai)[4], float (&aj)[4], float (&vi)[4], float (&vj)[4], bool& rotated) {
-    float a = 0.0f, b = 0.0f, p = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        a = __fadd_rn(a, __fmul_rn(ai[k], ai[k]));
-        b = __fadd_rn(b, __fmul_rn(aj[k], aj[k]));
-        p = __fadd_rn(p, __fmul_rn(ai[k], aj[k]));
-    }
-    float c, s;
-    if (!jacobiAngle(a, b, p, c, s)) return;
-    rotated = true;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float x0 = ai[k], x1 = aj[k], y0 = vi[k], y1 = vj[k];
-        ai[k] = __fadd_rn(__fmul_rn(c, x0), __fmul_rn(s, x1));
-        aj[k] = __fsub_rn(__fmul_rn(c, x1), __fmul_rn(s, x0));
-        vi[k] = __fadd_rn(__fmul_rn(c, y0), __fmul_rn(s, y1));
-        vj[k] = __fsub_rn(__fmul_rn(c, y1), __fmul_rn(s, y0));
-    }
-}
-// the eigenvector of the largest eigenvalue of the symmetric 4x4 Nm (row-major), sign fixed
-__device__ __forceinline__ void ssEigenTop4(const float (&Nm)[16], float (&q)[4]) {
-    float fro = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) fro = __fadd_rn(fro, __fmul_rn(Nm[k], Nm[k]));
-    const float mu = kb8Sqrt(fro);
-    float c0[4], c1[4], c2[4], c3[4], v0[4] = {1.f, 0.f, 0.f, 0.f}, v1[4] = {0.f, 1.f, 0.f, 0.f}, v2[4] = {0.f, 0.f, 1.f, 0.f}, v3[4] = {0.f, 0.f, 0.f, 1.f};
-#pragma unroll
-    for (int r = 0; r < 4; r++) { c0[r] = Nm[4 * r]; c1[r] = Nm[4 * r + 1]; c2[r] = Nm[4 * r + 2]; c3[r] = Nm[4 * r + 3]; }
-    c0[0] = __fadd_rn(c0[0], mu); c1[1] = __fadd_rn(c1[1], mu); c2[2] = __fadd_rn(c2[2], mu); c3[3] = __fadd_rn(c3[3], mu);
-    for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
-        bool rotated = false;
-        ssJacobiPair4(c0, c1, v0, v1, rotated);
-        ssJacobiPair4(c0, c2, v0, v2, rotated);
-        ssJacobiPair4(c0, c3, v0, v3, rotated);
-        ssJacobiPair4(c1, c2, v1, v2, rotated);
-        ssJacobiPair4(c1, c3, v1, v3, rotated);
-        ssJacobiPair4(c2, c3, v2, v3, rotated);
-        if (!rotated) break;
-    }
-    auto norm2 = [](const float (&c)[4]) {
-        return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c[0], c[0]), __fmul_rn(c[1], c[1])), __fmul_rn(c[2], c[2])), __fmul_rn(c[3], c[3]));
-    };
-    const float n0 = norm2(c0), n1 = norm2(c1), n2 = norm2(c2), n3 = norm2(c3);
-    float best = n0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) q[k] = v0[k];
-    if (n1 > best) { best = n1; for (int k = 0; k < 4; k++) q[k] = v1[k]; }
-    if (n2 > best) { best = n2; for (int k = 0; k < 4; k++) q[k] = v2[k]; }
-    if (n3 > best) { best = n3; for (int k = 0; k < 4; k++) q[k] = v3[k]; }
-    const bool neg = q[0] != 0.0f ? q[0] < 0.0f : q[1] != 0.0f ? q[1] < 0.0f : q[2] != 0.0f ? q[2] < 0.0f : q[3] < 0.0f;
-    if (neg)
-#pragma unroll
-        for (int k = 0; k < 4; k++) q[k] = -q[k];
-}
-
+// ---- cv::Rodrigues -----------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ssRodrigues(const float (&rv)[3], float (&R)[9]) {
     double r[3] = {(double)rv[0], (double)rv[1], (double)rv[2]};
     const double theta = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(r[0], r[0]), __dmul_rn(r[1], r[1])), __dmul_rn(r[2], r[2])));
@@ -222,7 +104,7 @@ __device__ __forceinline__ void ssRodrigues(const float (&rv)[3], float (&R)[9])
         return;
     }
     double s, c;
-    ssSinCos(theta, s, c);
+    sinCosDouble(theta, s, c);
     const double c1 = __dsub_rn(1.0, c), itheta = __ddiv_rn(1.0, theta);
 #pragma unroll
     for (int k = 0; k < 3; k++) r[k] = __dmul_rn(r[k], itheta);
@@ -266,9 +148,9 @@ __device__ __forceinline__ void ssComputeSim3(const float (&P1)[9], const float 
     const float N33 = __fsub_rn(__fadd_rn(-M[0], M[4]), M[8]), N34 = __fadd_rn(M[5], M[7]), N44 = __fadd_rn(__fsub_rn(-M[0], M[4]), M[8]);
     const float Nm[16] = {N11, N12, N13, N14, N12, N22, N23, N24, N13, N23, N33, N34, N14, N24, N34, N44};
     float q[4];
-    ssEigenTop4(Nm, q);
-    const double nrm = __dsqrt_rn(nmpDot3(q[1], q[2], q[3], q[1], q[2], q[3]));
-    const double ang = ssAtan2(nrm, (double)q[0]);
+    topEigenvector4(Nm, q);
+    const double nrm = __dsqrt_rn(dot3Double(q[1], q[2], q[3], q[1], q[2], q[3]));
+    const double ang = atan2Double(nrm, (double)q[0]);
     const float alpha = (float)__dmul_rn(__dmul_rn(2.0, ang), __ddiv_rn(1.0, nrm));
     const float rv[3] = {__fmul_rn(q[1], alpha), __fmul_rn(q[2], alpha), __fmul_rn(q[3], alpha)};
     ssRodrigues(rv, h.R);
@@ -298,14 +180,8 @@ __device__ __forceinline__ void ssComputeSim3(const float (&P1)[9], const float 
 
 // ---- projections and the inlier test ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ssProjectCam(int model, const float (&k)[8], float x, float y, float z, float& u, float& v) {
-    if (model) { kb8Project(k, x, y, z, u, v); return; }
-    u = __fadd_rn(__fdiv_rn(__fmul_rn(k[0], x), z), k[2]);
-    v = __fadd_rn(__fdiv_rn(__fmul_rn(k[1], y), z), k[3]);
-}
-// Rcw * X + tcw of a 3x4 row-major T
-__device__ __forceinline__ void ssTransform(const float* T, const float (&X)[3], float (&out)[3]) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) out[r] = gemmRow(T[4 * r], T[4 * r + 1], T[4 * r + 2], X, 1.0, T[4 * r + 3], true);
+    if (model) kb8Project(k, x, y, z, u, v);
+    else pinholeProject(k, x, y, z, u, v);
 }
 __device__ __forceinline__ float ssErr(float au, float av, float bu, float bv) {
     const float du = __fsub_rn(au, bu), dv = __fsub_rn(av, bv);
@@ -315,9 +191,9 @@ __device__ __forceinline__ float ssErr(float au, float av, float bu, float bv) {
 __device__ __forceinline__ bool ssInlier(const Sim3Hyp& h, const Sim3Problem& pb, const float* __restrict__ pts, int cap, int k) {
     const float X1[3] = {pts[k], pts[cap + k], pts[2 * cap + k]}, X2[3] = {pts[3 * cap + k], pts[4 * cap + k], pts[5 * cap + k]};
     float a[3], b[3], u21, v21, u12, v12;
-    ssTransform(h.T12, X2, a);
+    transformPoint(h.T12, X2, a);
     ssProjectCam(pb.model1, pb.cam1, a[0], a[1], a[2], u21, v21);                            // vP2im1
-    ssTransform(h.T21, X1, b);
+    transformPoint(h.T21, X1, b);
     ssProjectCam(pb.model2, pb.cam2, b[0], b[1], b[2], u12, v12);                            // vP1im2
     const float err1 = ssErr(pts[6 * cap + k], pts[7 * cap + k], u21, v21), err2 = ssErr(u12, v12, pts[8 * cap + k], pts[9 * cap + k]);
     return err1 < pts[10 * cap + k] && err2 < pts[11 * cap + k];
@@ -326,7 +202,7 @@ __device__ __forceinline__ bool ssInlier(const Sim3Hyp& h, const Sim3Problem& pb
 __device__ __forceinline__ void ssHypothesis(const int* __restrict__ rnd, long long slot, int N, const float* __restrict__ pts, int cap, bool fixScale,
                                              Sim3Hyp& h) {
     int idx[3];
-    ssDraw3(rnd + slot * 3, N, idx);
+    drawSet<3>(rnd + slot * 3, N, idx);
     float P1[9], P2[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -365,11 +241,8 @@ __device__ __forceinline__ void ssPrepareProblem(int lane, int p, const Sim3Prob
             const float Xa[3] = {x1w[(at + i) * 3], x1w[(at + i) * 3 + 1], x1w[(at + i) * 3 + 2]},
                         Xb[3] = {x2w[(at + i) * 3], x2w[(at + i) * 3 + 1], x2w[(at + i) * 3 + 2]};
             float c1[3], c2[3], u1, v1, u2, v2;
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                c1[r] = gemmRow(pb.Tcw1[4 * r], pb.Tcw1[4 * r + 1], pb.Tcw1[4 * r + 2], Xa, 1.0, pb.Tcw1[4 * r + 3], true);
-                c2[r] = gemmRow(pb.Tcw2[4 * r], pb.Tcw2[4 * r + 1], pb.Tcw2[4 * r + 2], Xb, 1.0, pb.Tcw2[4 * r + 3], true);
-            }
+            transformPoint(pb.Tcw1, Xa, c1);
+            transformPoint(pb.Tcw2, Xb, c2);
             ssProjectCam(pb.model1, pb.cam1, c1[0], c1[1], c1[2], u1, v1);
             ssProjectCam(pb.model2, pb.cam2, c2[0], c2[1], c2[2], u2, v2);
             w.idx1[at + pos] = i;
@@ -437,11 +310,17 @@ __device__ __forceinline__ void ssDecideProblem(int lane, int p, const Sim3Probl
     res.status = converged ? kSsConverged : kSsNoMore;
     res.iterations = converged ? bestIt + 1 : pr.maxIts;
     res.bestIt = bestIt; res.nInliers = converged ? best : 0; res.bestInliers = best;
-    res.scale = ssCanon(h.s);
-    for (int c = 0; c < 9; c++) res.R[c] = ssCanon(h.R[c]);
-    for (int c = 0; c < 3; c++) res.t[c] = ssCanon(h.t[c]);
-    for (int c = 0; c < 12; c++) res.T12[c] = ssCanon(h.T12[c]);
+    res.scale = canonNaN(h.s);
+    for (int c = 0; c < 9; c++) res.R[c] = canonNaN(h.R[c]);
+    for (int c = 0; c < 3; c++) res.t[c] = canonNaN(h.t[c]);
+    for (int c = 0; c < 12; c++) res.T12[c] = canonNaN(h.T12[c]);
     res.T12[12] = res.T12[13] = res.T12[14] = 0.0f; res.T12[15] = 1.0f;
 }
+
+// Earlier names, ONLY for tests/cpp/sim3_solver_host_check.cpp, which the existing tests build as it is; the library does not call them
+__device__ __forceinline__ void ssDraw3(const int* __restrict__ r3, int N, int (&idx)[3]) { drawSet<3>(r3, N, idx); }
+__device__ __forceinline__ void ssEigenTop4(const float (&Nm)[16], float (&q)[4]) { topEigenvector4(Nm, q); }
+__device__ __forceinline__ double ssAtan2(double y, double x) { return atan2Double(y, x); }
+__device__ __forceinline__ void ssSinCos(double theta, double& s, double& c) { sinCosDouble(theta, s, c); }
 
 }  // namespace orbx

@@ -1,9 +1,15 @@
-// k_small_svd.hpp - the small-matrix routines of TwoViewReconstruction (reference src/TwoViewReconstruction.cc): what cv::SVD, cv::Mat::inv,
-// cv::determinant and cv::gemm do there on 16x9, 8x9 and 3x3 binary32 matrices.  cv::SVD is OpenCV's own Jacobi or LAPACK's sgesdd, by its
-// build: these routines are the PROJECT'S definition ("parity unpinned"), nullVector4's Hestenes iteration
-// (k_camera_kb8_unproject.hpp) with its constants kJacobiSweeps, kJacobiEps, kJacobiPolishRatio, generalised:
-//   jacobiAngle     the rotation of one column pair from a = |ci|^2, b = |cj|^2, p = ci.cj (nullVector4's formulas, stated once here for
-//                   the two routines below);
+// k_small_svd.hpp - the small-matrix routines of the geometry entries: what cv::SVD, cv::eigen, cv::Mat::inv, cv::determinant and cv::gemm do
+// on 4x4, 16x9, 8x9 and 3x3 binary32 matrices in KannalaBrandt8::Triangulate, LocalMapping's and TwoViewReconstruction's Triangulate,
+// ComputeH21 / ComputeF21 / ReconstructH / DecomposeE and Sim3Solver::ComputeSim3.  cv::SVD is OpenCV's own Jacobi or LAPACK's sgesdd, by its
+// build: these routines are the PROJECT'S definition ("parity unpinned"), ONE one-sided (Hestenes) Jacobi iteration in
+// binary32 with the constants below, and EVERY Jacobi routine of the library lives here:
+//   jacobiAngle     the rotation of one column pair from a = |ci|^2, b = |cj|^2, p = ci.cj, stated once for every routine below;
+//   jacobiPair<N>   one pair of a sweep on columns of N floats in registers.  The three register routines below call it pair by pair, in
+//                   the order (i, j), i < j, until a sweep rotates nothing or kJacobiSweeps sweeps are done.  That driver is WRITTEN OUT
+//                   three times on purpose: as one template every 4-column kernel took 65 more VGPRs (docs/history/r30_small_math.md);
+//   nullVector4     vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on a 4x4 matrix: the column of smallest squared norm
+//                   selects V's column, then one correction step in binary64 (tests/triangulation_two_eyes_walk.py states it too);
+//   topEigenvector4 cv::eigen's row 0 on a symmetric 4x4 matrix (Sim3Solver's quaternion; k_sim3_solver.hpp says why it is shifted);
 //   nullVector9<M>  vt.row(8) of an M x 9 matrix (M = 16: ComputeH21, M = 8: ComputeF21, rank <= 8: one column goes to zero).  The matrix,
 //                   its copy and V live in MEMORY (LDS on the device, one lane works on them): nothing is indexed at run time in registers.
 //                   Pair order of a sweep: (i, j) for i = 0 .. 7, j = i + 1 .. 8; every dot product runs over the rows k = 0 .. M - 1 in
@@ -20,27 +26,150 @@
 //   gemm3           a 3x3 * 3x3 product, one gemmRow per element with a scale (k_match_helpers.hpp).
 // The sign and order freedom of an SVD is fixed by the above and may differ from OpenCV's: in ReconstructH and DecomposeE it can permute
 // the 8 or 4 motion hypotheses, never change their set.
+// Takes sqrtFloat32 from k_small_math.hpp, gemmRow from k_match_helpers.hpp, ORBX_LDS from k_lds_vec.hpp; nothing from a feature header.
 // Plain arithmetic only: compiles for the host behind tests/cpp/host_shim.
 #pragma once
-#include "k_camera_kb8_unproject.hpp"
 #include "k_lds_vec.hpp"
 #include "k_match_helpers.hpp"
+#include "k_small_math.hpp"
 
 namespace orbx {
 
+// ---- the iteration's constants (DESIGN.md section 2 quotes them) ----
+constexpr int kJacobiSweeps = 15;                    // cap on sweeps: the bound that ends a NaN or degenerate matrix
+constexpr float kJacobiEps = 0x1p-22f;               // a pair rotates when |p| > kJacobiEps * sqrt(a * b)  (2 * FLT_EPSILON)
+constexpr float kJacobiPolishRatio = 64.0f;          // the correction step uses the columns whose squared norm exceeds this times the smallest
+
 // whether the pair rotates, and by which (c, s)
 __device__ __forceinline__ bool jacobiAngle(float a, float b, float p, float& c, float& s) {
-    if (!(fabsf(p) > __fmul_rn(kJacobiEps, kb8Sqrt(__fmul_rn(a, b))))) return false;      // (a NaN never rotates)
+    if (!(fabsf(p) > __fmul_rn(kJacobiEps, sqrtFloat32(__fmul_rn(a, b))))) return false;      // (a NaN never rotates)
     p = __fmul_rn(p, 2.0f);
-    const float beta = __fsub_rn(a, b), gamma = kb8Sqrt(__fadd_rn(__fmul_rn(p, p), __fmul_rn(beta, beta)));
+    const float beta = __fsub_rn(a, b), gamma = sqrtFloat32(__fadd_rn(__fmul_rn(p, p), __fmul_rn(beta, beta)));
     // beta < 0: s = sqrt(((gamma - beta) * 0.5) / gamma), c = p / (gamma * s * 2); else c = sqrt((gamma + beta) / (gamma * 2)), s = p / (gamma * c * 2)
     const bool swap = beta < 0.0f;
-    const float root = swap ? kb8Sqrt(__fdiv_rn(__fmul_rn(__fsub_rn(gamma, beta), 0.5f), gamma))
-                            : kb8Sqrt(__fdiv_rn(__fadd_rn(gamma, beta), __fmul_rn(gamma, 2.0f)));
+    const float root = swap ? sqrtFloat32(__fdiv_rn(__fmul_rn(__fsub_rn(gamma, beta), 0.5f), gamma))
+                            : sqrtFloat32(__fdiv_rn(__fadd_rn(gamma, beta), __fmul_rn(gamma, 2.0f)));
     const float other = __fdiv_rn(p, __fmul_rn(__fmul_rn(gamma, root), 2.0f));
     c = swap ? other : root;
     s = swap ? root : other;
     return true;
+}
+
+// one pair of a sweep: columns i and j of the working matrix and of V, N floats each in registers
+template <int N>
+__device__ __forceinline__ void jacobiPair(float (&ai)[N], float (&aj)[N], float (&vi)[N], float (&vj)[N], bool& rotated) {
+    float a = 0.0f, b = 0.0f, p = 0.0f;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        a = __fadd_rn(a, __fmul_rn(ai[k], ai[k]));
+        b = __fadd_rn(b, __fmul_rn(aj[k], aj[k]));
+        p = __fadd_rn(p, __fmul_rn(ai[k], aj[k]));
+    }
+    float c, s;
+    if (!jacobiAngle(a, b, p, c, s)) return;
+    rotated = true;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const float x0 = ai[k], x1 = aj[k], y0 = vi[k], y1 = vj[k];
+        ai[k] = __fadd_rn(__fmul_rn(c, x0), __fmul_rn(s, x1));
+        aj[k] = __fsub_rn(__fmul_rn(c, x1), __fmul_rn(s, x0));
+        vi[k] = __fadd_rn(__fmul_rn(c, y0), __fmul_rn(s, y1));
+        vj[k] = __fsub_rn(__fmul_rn(c, y1), __fmul_rn(s, y0));
+    }
+}
+
+// The right singular vector of A's smallest singular value.  A is row-major; out is NOT normalised in sign (it cancels in x / w).
+// The column of smallest squared norm selects V's column, of equal norms the highest index (a NaN norm never wins: column 3).
+__device__ __forceinline__ void nullVector4(const float (&A)[16], float (&out)[4]) {
+    float c0[4], c1[4], c2[4], c3[4];
+    float v0[4] = {1.f, 0.f, 0.f, 0.f}, v1[4] = {0.f, 1.f, 0.f, 0.f}, v2[4] = {0.f, 0.f, 1.f, 0.f}, v3[4] = {0.f, 0.f, 0.f, 1.f};
+#pragma unroll
+    for (int r = 0; r < 4; r++) { c0[r] = A[4 * r]; c1[r] = A[4 * r + 1]; c2[r] = A[4 * r + 2]; c3[r] = A[4 * r + 3]; }
+    for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
+        bool rotated = false;
+        jacobiPair<4>(c0, c1, v0, v1, rotated);
+        jacobiPair<4>(c0, c2, v0, v2, rotated);
+        jacobiPair<4>(c0, c3, v0, v3, rotated);
+        jacobiPair<4>(c1, c2, v1, v2, rotated);
+        jacobiPair<4>(c1, c3, v1, v3, rotated);
+        jacobiPair<4>(c2, c3, v2, v3, rotated);
+        if (!rotated) break;
+    }
+    float n0 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        n0 = __fadd_rn(n0, __fmul_rn(c0[k], c0[k])); n1 = __fadd_rn(n1, __fmul_rn(c1[k], c1[k]));
+        n2 = __fadd_rn(n2, __fmul_rn(c2[k], c2[k])); n3 = __fadd_rn(n3, __fmul_rn(c3[k], c3[k]));
+    }
+    int sel = 3;
+    float best = n3;
+    if (n2 < best) { best = n2; sel = 2; }
+    if (n1 < best) { best = n1; sel = 1; }
+    if (n0 < best) { best = n0; sel = 0; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[k] = sel == 0 ? v0[k] : sel == 1 ? v1[k] : sel == 2 ? v2[k] : v3[k];
+    // One correction step.  The rotations' roundings leave `out` with a component eps_i along each other column v_i of V; A*out, accumulated
+    // in binary64 from the ORIGINAL matrix, shows it: the rotated column c_i is sigma_i*u_i, so eps_i = (c_i . A*out) / |c_i|^2.  Taken only
+    // against columns whose squared norm is above kJacobiPolishRatio times the selected one (a column as small as the selected one spans
+    // the same null space, and its c_i is rounding noise).
+    double r[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        double acc = __dmul_rn((double)A[4 * k], (double)out[0]);
+#pragma unroll
+        for (int c = 1; c < 4; c++) acc = __dadd_rn(acc, __dmul_rn((double)A[4 * k + c], (double)out[c]));
+        r[k] = acc;
+    }
+    auto component = [&](const float (&c)[4], float n) {
+        double acc = __dmul_rn((double)c[0], r[0]);
+#pragma unroll
+        for (int k = 1; k < 4; k++) acc = __dadd_rn(acc, __dmul_rn((double)c[k], r[k]));
+        return __fdiv_rn((float)acc, n);
+    };
+    const float bound = __fmul_rn(kJacobiPolishRatio, best);
+    const float e0 = sel != 0 && n0 > bound ? component(c0, n0) : 0.0f, e1 = sel != 1 && n1 > bound ? component(c1, n1) : 0.0f,
+                e2 = sel != 2 && n2 > bound ? component(c2, n2) : 0.0f, e3 = sel != 3 && n3 > bound ? component(c3, n3) : 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        out[k] = __fsub_rn(__fsub_rn(__fsub_rn(__fsub_rn(out[k], __fmul_rn(e0, v0[k])), __fmul_rn(e1, v1[k])), __fmul_rn(e2, v2[k])), __fmul_rn(e3, v3[k]));
+}
+
+// The eigenvector of the largest eigenvalue of the symmetric 4x4 Nm (row-major), sign fixed.  The iteration runs on Nm + mu * I, mu = the
+// Frobenius norm of Nm (a float sum of float squares, left to right): the column of LARGEST squared norm selects V's column, of equal norms
+// the lowest index; the first component that is not zero is made positive.
+__device__ __forceinline__ void topEigenvector4(const float (&Nm)[16], float (&q)[4]) {
+    float fro = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; k++) fro = __fadd_rn(fro, __fmul_rn(Nm[k], Nm[k]));
+    const float mu = sqrtFloat32(fro);
+    float c0[4], c1[4], c2[4], c3[4], v0[4] = {1.f, 0.f, 0.f, 0.f}, v1[4] = {0.f, 1.f, 0.f, 0.f}, v2[4] = {0.f, 0.f, 1.f, 0.f}, v3[4] = {0.f, 0.f, 0.f, 1.f};
+#pragma unroll
+    for (int r = 0; r < 4; r++) { c0[r] = Nm[4 * r]; c1[r] = Nm[4 * r + 1]; c2[r] = Nm[4 * r + 2]; c3[r] = Nm[4 * r + 3]; }
+    c0[0] = __fadd_rn(c0[0], mu); c1[1] = __fadd_rn(c1[1], mu); c2[2] = __fadd_rn(c2[2], mu); c3[3] = __fadd_rn(c3[3], mu);
+    for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
+        bool rotated = false;
+        jacobiPair<4>(c0, c1, v0, v1, rotated);
+        jacobiPair<4>(c0, c2, v0, v2, rotated);
+        jacobiPair<4>(c0, c3, v0, v3, rotated);
+        jacobiPair<4>(c1, c2, v1, v2, rotated);
+        jacobiPair<4>(c1, c3, v1, v3, rotated);
+        jacobiPair<4>(c2, c3, v2, v3, rotated);
+        if (!rotated) break;
+    }
+    auto norm2 = [](const float (&c)[4]) {
+        return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c[0], c[0]), __fmul_rn(c[1], c[1])), __fmul_rn(c[2], c[2])), __fmul_rn(c[3], c[3]));
+    };
+    const float n0 = norm2(c0), n1 = norm2(c1), n2 = norm2(c2), n3 = norm2(c3);
+    float best = n0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) q[k] = v0[k];
+    if (n1 > best) { best = n1; for (int k = 0; k < 4; k++) q[k] = v1[k]; }
+    if (n2 > best) { best = n2; for (int k = 0; k < 4; k++) q[k] = v2[k]; }
+    if (n3 > best) { best = n3; for (int k = 0; k < 4; k++) q[k] = v3[k]; }
+    const bool neg = q[0] != 0.0f ? q[0] < 0.0f : q[1] != 0.0f ? q[1] < 0.0f : q[2] != 0.0f ? q[2] < 0.0f : q[3] < 0.0f;
+    if (neg)
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = -q[k];
 }
 
 // W: the M x 9 matrix, row-major, overwritten by the rotated columns; A0: its untouched copy; V: 9 x 9 scratch.
@@ -119,7 +248,7 @@ __device__ __forceinline__ void nullVector9(ORBX_LDS float* W, const ORBX_LDS fl
     }
 }
 
-#ifndef ORBX_HOST_ROW
+#if !defined(ORBX_HOST_ROW) && defined(__HIPCC__)
 // ---- nullVector9 with the ROWS OVER THE LANES of a wave: the same definition, bit for bit ---------------------------------------------
 // Lane k < M holds row k of the matrix (w), of its copy (a0) and, for k < 9, row k of V (v), all in registers; lanes from M on hold zeros.
 // A dot product over the rows is the SAME left-to-right sum: one chain of v_readlane + v_add over lanes 0 .. M - 1, uniform on every lane
@@ -191,27 +320,6 @@ __device__ __forceinline__ void nullVector9Wave(const float (&a0)[9], float (&ou
 }
 #endif
 
-__device__ __forceinline__ void jacobiPair3(float (&ai)[3], float (&aj)[3], float (&vi)[3], float (&vj)[3], bool& rotated) {
-    float a = 0.0f, b = 0.0f, p = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        a = __fadd_rn(a, __fmul_rn(ai[k], ai[k]));
-        b = __fadd_rn(b, __fmul_rn(aj[k], aj[k]));
-        p = __fadd_rn(p, __fmul_rn(ai[k], aj[k]));
-    }
-    float c, s;
-    if (!jacobiAngle(a, b, p, c, s)) return;
-    rotated = true;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float x0 = ai[k], x1 = aj[k], y0 = vi[k], y1 = vj[k];
-        ai[k] = __fadd_rn(__fmul_rn(c, x0), __fmul_rn(s, x1));
-        aj[k] = __fsub_rn(__fmul_rn(c, x1), __fmul_rn(s, x0));
-        vi[k] = __fadd_rn(__fmul_rn(c, y0), __fmul_rn(s, y1));
-        vj[k] = __fsub_rn(__fmul_rn(c, y1), __fmul_rn(s, y0));
-    }
-}
-
 __device__ __forceinline__ void svd3Swap(float (&a)[3], float (&b)[3]) {
 #pragma unroll
     for (int k = 0; k < 3; k++) { const float t = a[k]; a[k] = b[k]; b[k] = t; }
@@ -224,12 +332,12 @@ __device__ __forceinline__ void svd3(const float (&A)[9], float (&U)[9], float (
     for (int r = 0; r < 3; r++) { c0[r] = A[3 * r]; c1[r] = A[3 * r + 1]; c2[r] = A[3 * r + 2]; }
     for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
         bool rotated = false;
-        jacobiPair3(c0, c1, v0, v1, rotated);
-        jacobiPair3(c0, c2, v0, v2, rotated);
-        jacobiPair3(c1, c2, v1, v2, rotated);
+        jacobiPair<3>(c0, c1, v0, v1, rotated);
+        jacobiPair<3>(c0, c2, v0, v2, rotated);
+        jacobiPair<3>(c1, c2, v1, v2, rotated);
         if (!rotated) break;
     }
-    auto norm = [](const float (&c)[3]) { return kb8Sqrt(__fadd_rn(__fadd_rn(__fmul_rn(c[0], c[0]), __fmul_rn(c[1], c[1])), __fmul_rn(c[2], c[2]))); };
+    auto norm = [](const float (&c)[3]) { return sqrtFloat32(__fadd_rn(__fadd_rn(__fmul_rn(c[0], c[0]), __fmul_rn(c[1], c[1])), __fmul_rn(c[2], c[2]))); };
     float w0 = norm(c0), w1 = norm(c1), w2 = norm(c2);
     // descending, of equal values the lower column first (a bubble of three compares; a NaN stays where it is)
     auto order = [](float& wa, float& wb, float (&ca)[3], float (&cb)[3], float (&va)[3], float (&vb)[3]) {

@@ -6,7 +6,7 @@
 //   matches      mvMatches12 = the (i, vMatches12[i]) with vMatches12[i] >= 0 in ascending i (:53-62); N = their count;
 //   sets         mvSets[it][j] from the CALLER'S raw rand() values r (ints of [0, 2^31 - 1]): randi = int(((double)r / 2147483648.0) * (N - j))
 //                (DUtils/Random.cpp:47-50), idx = avail[randi], avail[randi] = avail[N - j - 1] (:83-95) - at most eight displaced slots
-//                of the identity, kept in registers (tvDrawSet).  randi is clamped into [0, N - j - 1]: a value outside [0, 2^31 - 1] is the
+//                of the identity, kept in registers (drawSet<8>, k_small_math.hpp).  randi is clamped into [0, N - j - 1]: a value outside [0, 2^31 - 1] is the
 //                caller's error and must not index outside the list;
 //   Normalize    :752-798 over ALL n keypoints of a frame, not the matched ones: four left-to-right binary32 sums, meanX / N a float
 //                division, sX = 1.0 / meanDevX in double rounded once; T = [sX 0 -meanX*sX; 0 sY -meanY*sY; 0 0 1]; T2inv = inv3(T2);
@@ -20,7 +20,7 @@
 //   RH           SH + SF == 0 rejects (:111); RH = SH / (SH + SF) in binary32; RH > rhThreshold takes H;
 //   ReconstructF :473-574 with DecomposeE :912-932;  ReconstructH :576-735;  CheckRT :801-910;  Triangulate :737-750 is the row form of
 //                k_new_map_points.hpp's A (float(p * P.row(2)[c]) - P.row(r)[c]) and nullVector4, skipped by a wave in which no lane has an
-//                inlier (nmpAny).  t / cv::norm(t) is fmul(t[c], (float)(1.0 / norm)) with the norm in double;
+//                inlier (waveAny).  t / cv::norm(t) is fmul(t[c], (float)(1.0 / norm)) with the norm in double;
 //   mixed precision   invZ = 1.0 / z in double rounded once; 4.0 * mSigma2 a double narrowed to float; d1 / d2 < 1.00001,
 //                cosParallax < 0.99998, 0.9 * N, 0.7 * maxGood, 0.75 * bestGood compare in double; normal1.dot(normal2) and cv::norm in
 //                double, dist narrowed to float, dist1 * dist2 a float product under a double division;
@@ -30,10 +30,16 @@
 //                NaN is undefined).  A cosine above 1 gives NaN, on which :528's > and :724's >= are false.
 // One workgroup is ONE WAVE everywhere (kTvLanes lanes); the host build (ORBX_HOST_ROW, tests/cpp/host_shim) runs the same functions
 // with a wave of one lane: ballots are the lane's own bit, the chain adds one match at a time - the same order.
+// Takes acosFloat32 from k_acosf.hpp, the null vectors / svd3 / det3 / inv3 / gemm3 from k_small_svd.hpp, drawSet / sqrtFloat32 / quietNaN /
+// canonNaN / waveAny from k_small_math.hpp, gemmRow / dot3Double from k_match_helpers.hpp, the parameter blocks from orbx_params.hpp.
 #pragma once
 #include "k_acosf.hpp"
-#include "k_new_map_points.hpp"
+#include "k_lds_vec.hpp"
+#include "k_match_helpers.hpp"
+#include "k_small_math.hpp"
 #include "k_small_svd.hpp"
+#include "orbx_device.hpp"
+#include "orbx_params.hpp"
 
 namespace orbx {
 
@@ -73,27 +79,8 @@ constexpr int kTvHypLdsFloats = 2 * 16 * 9 + 81 + 18;    // the hypothesis wave:
 constexpr int kTvMotionFloats = 27;                       // R[9] t[3] P2[12] O2[3]
 constexpr int kTvDecideLdsFloats = 8 * kTvMotionFloats + 8 + 12;     // the motions, their parallaxes, then as ints a status and the motions' counts
 
-__device__ __forceinline__ float tvQuietNaN() { return __uint_as_float(0x7fc00000u); }
 __device__ __forceinline__ bool tvFinite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ float tvInvDouble(float x) { return (float)__ddiv_rn(1.0, (double)x); }      // `1.0 / x` assigned to a float
-
-// mvSets[it] from eight raw rand() values
-__device__ __forceinline__ void tvDrawSet(const int* __restrict__ r8, int N, int (&idx)[8]) {
-    int slot[8], val[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const int size = N - j;
-        int randi = (int)__dmul_rn(__ddiv_rn((double)r8[j], 2147483648.0), (double)size);
-        randi = max(0, min(randi, size - 1));
-        int va = randi, vb = size - 1;
-#pragma unroll
-        for (int t = 0; t < j; t++) {                       // ascending: the latest displacement of a slot wins
-            if (slot[t] == randi) va = val[t];
-            if (slot[t] == size - 1) vb = val[t];
-        }
-        idx[j] = va; slot[j] = randi; val[j] = vb;
-    }
-}
 
 // Normalize's two chains of one coordinate (comp 0: x, 1: y) over the n keypoints of a frame: the mean and the scale
 __device__ __forceinline__ void tvNormalizeChain(const Keypoint* __restrict__ kps, int n, int comp, float& mean, float& s) {
@@ -273,7 +260,7 @@ __device__ __forceinline__ void tvStoreMotion(ORBX_LDS float* mo, const float (&
 
 // t / cv::norm(t)
 __device__ __forceinline__ void tvUnit(float (&t)[3]) {
-    const float inv = (float)__ddiv_rn(1.0, __dsqrt_rn(nmpDot3(t[0], t[1], t[2], t[0], t[1], t[2])));
+    const float inv = (float)__ddiv_rn(1.0, __dsqrt_rn(dot3Double(t[0], t[1], t[2], t[0], t[1], t[2])));
 #pragma unroll
     for (int c = 0; c < 3; c++) t[c] = __fmul_rn(t[c], inv);
 }
@@ -318,8 +305,8 @@ __device__ __forceinline__ bool tvMotionsH(const float (&H21)[9], const TwoViewP
     if ((double)__fdiv_rn(d1, d2) < 1.00001 || (double)__fdiv_rn(d2, d3) < 1.00001) return false;
     const float d11 = __fmul_rn(d1, d1), d22 = __fmul_rn(d2, d2), d33 = __fmul_rn(d3, d3);
     const float a12 = __fsub_rn(d11, d22), a23 = __fsub_rn(d22, d33), a13 = __fsub_rn(d11, d33);
-    const float aux1 = kb8Sqrt(__fdiv_rn(a12, a13)), aux3 = kb8Sqrt(__fdiv_rn(a23, a13));
-    const float root = kb8Sqrt(__fmul_rn(a12, a23));
+    const float aux1 = sqrtFloat32(__fdiv_rn(a12, a13)), aux3 = sqrtFloat32(__fdiv_rn(a23, a13));
+    const float root = sqrtFloat32(__fmul_rn(a12, a23));
     const float denT = __fmul_rn(__fadd_rn(d1, d3), d2), denP = __fmul_rn(__fsub_rn(d1, d3), d2);
     const float auxS = __fdiv_rn(root, denT), ctheta = __fdiv_rn(__fadd_rn(d22, __fmul_rn(d1, d3)), denT);
     const float auxP = __fdiv_rn(root, denP), cphi = __fdiv_rn(__fsub_rn(__fmul_rn(d1, d3), d22), denP);
@@ -351,7 +338,7 @@ __device__ __forceinline__ TvPoint tvCheckPoint(bool active, const ORBX_LDS floa
                                                 float u2, float v2) {
     TvPoint out;
     out.counted = out.good = false; out.cosPar = 0.0f; out.p[0] = out.p[1] = out.p[2] = 0.0f;
-    if (!nmpAny(active)) return out;                                                           // (wave-uniform)
+    if (!waveAny(active)) return out;                                                           // (wave-uniform)
     const float P1[12] = {q.fx, 0.f, q.cx, 0.f, 0.f, q.fy, q.cy, 0.f, 0.f, 0.f, 1.f, 0.f};
     float A[16], vt[4], x[3];
 #pragma unroll
@@ -367,9 +354,9 @@ __device__ __forceinline__ TvPoint tvCheckPoint(bool active, const ORBX_LDS floa
     const bool finite = tvFinite(x[0]) && tvFinite(x[1]) && tvFinite(x[2]);
     const float n1[3] = {__fsub_rn(x[0], 0.0f), __fsub_rn(x[1], 0.0f), __fsub_rn(x[2], 0.0f)};
     const float n2[3] = {__fsub_rn(x[0], mo[24]), __fsub_rn(x[1], mo[25]), __fsub_rn(x[2], mo[26])};
-    const float dist1 = (float)__dsqrt_rn(nmpDot3(n1[0], n1[1], n1[2], n1[0], n1[1], n1[2])),
-                dist2 = (float)__dsqrt_rn(nmpDot3(n2[0], n2[1], n2[2], n2[0], n2[1], n2[2]));
-    const float cosPar = (float)__ddiv_rn(nmpDot3(n1[0], n1[1], n1[2], n2[0], n2[1], n2[2]), (double)__fmul_rn(dist1, dist2));
+    const float dist1 = (float)__dsqrt_rn(dot3Double(n1[0], n1[1], n1[2], n1[0], n1[1], n1[2])),
+                dist2 = (float)__dsqrt_rn(dot3Double(n2[0], n2[1], n2[2], n2[0], n2[1], n2[2]));
+    const float cosPar = (float)__ddiv_rn(dot3Double(n1[0], n1[1], n1[2], n2[0], n2[1], n2[2]), (double)__fmul_rn(dist1, dist2));
     const bool lowCos = (double)cosPar < 0.99998;
     float x2[3];
 #pragma unroll
@@ -397,10 +384,10 @@ __device__ __forceinline__ bool tvRankHit(const float* cosv, const uint8_t* coun
     }
     return less <= idx && idx < leq;
 }
-// (a NaN leaves as THE quiet NaN 0x7fc00000: which NaN 0 / 0 gives differs between the host's and the device's arithmetic)
+// (a NaN leaves as THE quiet NaN, canonNaN: which NaN 0 / 0 gives differs between the host's and the device's arithmetic)
 __device__ __forceinline__ float tvParallax(float cosPar) {
     const float p = (float)__ddiv_rn((double)__fmul_rn(acosFloat32(cosPar), 180.0f), 3.1415926535897932384626433832795);
-    return p != p ? tvQuietNaN() : p;
+    return canonNaN(p);
 }
 
 // the end of ReconstructF (:502-573) / ReconstructH (:692-734) on the counts and parallaxes of the motions; N = the inliers
@@ -495,7 +482,7 @@ __device__ __forceinline__ void tvHypothesisWave(int lane, int pair, int model, 
 #ifndef ORBX_HOST_ROW
     if constexpr (Spread) {
         int idx[8];
-        tvDrawSet(rnd + ((long long)pair * q.iterations + it) * 8, N, idx);
+        drawSet<8>(rnd + ((long long)pair * q.iterations + it) * 8, N, idx);
         if (model == 0) tvHypothesisSpread<16>(idx, pr, w.first + at, w.second + at, k1, k2, m);
         else tvHypothesisSpread<8>(idx, pr, w.first + at, w.second + at, k1, k2, m);
     } else
@@ -503,7 +490,7 @@ __device__ __forceinline__ void tvHypothesisWave(int lane, int pair, int model, 
     {
         if (lane == 0) {
             int idx[8];
-            tvDrawSet(rnd + ((long long)pair * q.iterations + it) * 8, N, idx);
+            drawSet<8>(rnd + ((long long)pair * q.iterations + it) * 8, N, idx);
             tvHypothesis(model, idx, pr, w.first + at, w.second + at, k1, k2, sMem, sMem + 144, sMem + 288, out18);
         }
         __syncthreads();
@@ -598,7 +585,7 @@ __device__ __forceinline__ void tvDecidePair(int lane, int pair, const Keypoint*
             if (k < N) { w.counted[at + k] = pt.counted ? 1 : 0; w.cosv[at + k] = pt.cosPar; }
             good += __popcll(__ballot(pt.counted));
         }
-        if (lane == 0) { sGood[h] = good; sPar[h] = good > 0 ? tvQuietNaN() : 0.0f; }
+        if (lane == 0) { sGood[h] = good; sPar[h] = good > 0 ? quietNaN() : 0.0f; }
         __syncthreads();
         if (good > 0) {
             const int idx = min(50, good - 1);
@@ -636,5 +623,8 @@ __device__ __forceinline__ void tvDecidePair(int lane, int pair, const Keypoint*
     }
     if (lane == 0 && q.prune) nMatches[pair] -= pruned;
 }
+
+// drawSet<8>'s earlier name, ONLY for tests/cpp/two_view_host_check.cpp, which the existing tests build as it is; the library does not call it
+__device__ __forceinline__ void tvDrawSet(const int* __restrict__ r8, int N, int (&idx)[8]) { drawSet<8>(r8, N, idx); }
 
 }  // namespace orbx
