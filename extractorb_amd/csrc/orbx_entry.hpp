@@ -36,6 +36,29 @@ inline bool fitsLds(size_t bytes) { return bytes <= kLdsBudget; }
 constexpr size_t kBowMatchLdsBudget = 150 * 1024;
 inline int clampDistance(int d) { return d < 255 ? d : 255; }      // no descriptor distance exceeds 255: a larger bound accepts the same matches
 
+// orbx_detect_candidates_device: both kernels' tables must fit (k_place_recognition.hip).  160 KB - 512 holds 12 bytes for each of 13610 query
+// words, and 12 * 8192 + 4 * 8192 + 80 bytes of lists for 8192 rows; 8193 rows need a sort of 16384 slots, which does not fit
+inline bool placeFits(int nDb, int qCapacity) { return fitsLds(prPairLdsBytes(qCapacity)) && fitsLds(prQueryLdsBytes(nDb)); }
+// ... and what it refuses as ORBX_ERR_BAD_ARGUMENT, the handle apart: the pointers as the entry was given them.  The database's arrays and
+// d_score may be NULL when n_db == 0, d_loop / d_merge when n_candidates == 0, d_cand when cand_capacity == 0; d_connected and
+// d_common_words are optional.  n_candidates stays below 2^30 (k_place_query packs a list position beside two flag bits)
+inline bool placeBadArgument(const void* v, int mode, int nDb, const void* dbIds, const void* dbW, const void* dbN, int capacity, const void* dbMap,
+                             const void* dbFlags, const void* dbCovis, int nQueries, int qFirst, int qStep, const void* qIds, const void* qW,
+                             const void* qN, int qCapacity, const void* qMap, int nCandidates, const void* score, const void* result, const void* loop,
+                             const void* merge, const void* cand, int candCapacity) {
+    const bool nBest = mode == ORBX_PLACE_N_BEST;
+    return !v || (mode != ORBX_PLACE_N_BEST && mode != ORBX_PLACE_RELOCALIZATION) || nDb < 0 || nQueries < 1 || nQueries > 65535 || capacity < 1 ||
+           qCapacity < 1 || !qIds || !qW || !qN || !qMap || !result || negativeWalk(qFirst, qStep, nQueries) ||
+           (nDb > 0 && (!dbIds || !dbW || !dbN || !dbMap || !dbFlags || !dbCovis || !score)) ||
+           (nBest && (nCandidates < 0 || nCandidates > 0x3fffffff || (nCandidates > 0 && (!loop || !merge)) || (long long)nQueries * nCandidates > 0x7fffffffLL)) ||
+           (!nBest && (candCapacity < 0 || (candCapacity > 0 && !cand) || (long long)nQueries * candCapacity > 0x7fffffffLL)) ||
+           (long long)nQueries * nDb > 0x7fffffffLL;
+}
+// ... and as ORBX_ERR_UNSUPPORTED: a scoring other than L1_NORM (0), a database or a query capacity past the LDS bounds
+inline bool placeUnsupported(int scoring, int nDb, int qCapacity) { return scoring != 0 || !placeFits(nDb, qCapacity); }
+static_assert(prQueryLdsBytes(kPrMaxDb) <= kLdsBudget && prQueryLdsBytes(kPrMaxDb + 1) > kLdsBudget, "kPrMaxDb is the LDS bound on n_db");
+static_assert(prPairLdsBytes(kPrMaxQueryWords) <= kLdsBudget && prPairLdsBytes(kPrMaxQueryWords + 1) > kLdsBudget, "kPrMaxQueryWords is the LDS bound on q_capacity");
+
 // Sim3Solver::SetRansacParameters' nIterations for N correspondences, before max(1, min(., maxIterations)) (reference src/Sim3Solver.cc:
 // 137-147): epsilon is a FLOAT, pow / log / ceil run in double, minInliers == N gives 1.  The reference assigns the double to an int: a value
 // outside the int range (epsilon^3 below 2^-53 gives log(1) = 0 and an infinite quotient) converts as its x86-64 build does, to INT_MIN.

@@ -50,6 +50,7 @@ void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const 
 void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const int*, const TwoViewParams&, const TvWork&, void*, float*, uint8_t*, int);
 void launchSim3Solve(hipStream_t, const void*, const float*, const float*, const int*, const int*, const int*, const Sim3SolveParams&, const SsWork&, void*, uint8_t*, int, int);
 void launchPoseOptimization(hipStream_t, const void*, const Keypoint*, const int*, const float*, const int*, const float*, const PoseOptParams&, float*, uint8_t*, void*, int);
+void launchPlaceRecognition(hipStream_t, const PlaceArrays&, const PlaceParams&);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
@@ -242,6 +243,11 @@ struct orbx_handle {
     std::vector<int> sim3Its;
     double sim3ItsProb = 0.0;
     int sim3ItsMin = 0;
+    // place recognition's workspace (allocated on first use): a shared-word count, a smallest shared word id and a score per (query, row)
+    size_t placeEntries = 0;
+    int* d_placeWords = nullptr;
+    uint32_t* d_placeFirst = nullptr;
+    float* d_placeScore = nullptr;
     // stereo matching (allocated on first use)
     struct StereoShape { int pairs = 0, cap = 0, rows = 0; } stereo;      // what the six buffers below are sized for
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;
@@ -352,6 +358,10 @@ inline int growDevice(orbx_handle* h, Cap& recorded, const Cap& wanted, std::ini
     recorded = wanted;
     return ORBX_OK;
 }
+
+// the vocabulary is orbx_rows.cpp's: what another entry file needs of it (orbx_place_recognition.cpp: only L1_NORM is built)
+int vocabularyScoring(const orbx_vocabulary* v);
+int vocabularyDeviceIndex(const orbx_vocabulary* v);
 
 // MapPoint::PredictScale's breakpoints for the handle's (scaleFactor, nlevels), computed by the first entry that needs them
 inline int ensureScaleBreaks(orbx_handle* h) {

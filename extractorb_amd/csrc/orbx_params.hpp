@@ -204,6 +204,36 @@ struct PoseOptParams {           // k_pose_optimization.hip / k_pose_optimizatio
     int frameFirst, frameStep;                           // frames (eyes = 1) or RIG frames (eyes = 2: device frames 2r, 2r + 1; one pose per rig)
 };
 
+struct PlaceParams {             // k_place_recognition.hip / k_place_recognition.hpp
+    int mode, nDb, capacity;                             // mode: orbx_place_mode; capacity: words per database row
+    int nQueries, qFirst, qStep, qCapacity;              // query q is row qFirst + q * qStep of the query arrays, qCapacity words per row
+    int nCandidates, candCapacity;                       // nNumCandidates (N_BEST); entries of a query's row of d_cand (RELOCALIZATION)
+    int pairRows;                                        // database rows per workgroup of k_place_pairs (prPairRows): speed only
+};
+struct PlaceArrays {             // the arrays of orbx_detect_candidates_device, as the entry was given them, and the handle's workspace
+    const uint32_t* dbIds; const double* dbW; const int* dbN; const int* dbMap; const uint8_t* dbFlags; const int* dbCovis;
+    const uint32_t* qIds; const double* qW; const int* qN; const int* qMap; const uint8_t* connected;
+    float* score; void* result; int* loop; int* merge; int* cand; int* commonWords;
+    int* wsWords; uint32_t* wsFirst; float* wsScore;     // [q * nDb + k]: the pair's shared words, smallest shared word id, L1 score
+};
+
+constexpr int kPrScratchInts = 20;
+constexpr int prPow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+// LDS of the two kernels.  k_place_pairs: the query's weights and ids, 12 bytes a word.  k_place_query: 8 bytes of key and 4 of pBestKF per
+// list slot (a power of two of slots, for the sorts), 4 per row for the duplicate set, the scratch words
+constexpr size_t prPairLdsBytes(int qCapacity) { return (size_t)12 * (size_t)qCapacity; }
+constexpr size_t prQueryLdsBytes(int nDb) { return (size_t)12 * (size_t)prPow2(nDb) + (size_t)4 * (size_t)nDb + 4 * kPrScratchInts; }
+// Database rows per workgroup of k_place_pairs: a multiple of its four waves.  Every workgroup stages the query again (as many bytes as one
+// row), so many rows per workgroup save traffic and few give a small call enough workgroups for the chip: 4 rows while the call has fewer
+// than 2048 workgroups of them, up to 32
+constexpr int prPairRows(int nDb, int nQueries) {
+    int rows = 4;
+    while (rows < 32 && ((long long)nDb * nQueries + rows - 1) / rows > 2048) rows <<= 1;
+    return rows;
+}
+constexpr int kPrMaxDb = 8192;                            // the largest n_db whose lists fit the LDS budget (orbx_entry.hpp: placeFits)
+constexpr int kPrMaxQueryWords = 13610;                   // the largest q_capacity whose staged query does
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

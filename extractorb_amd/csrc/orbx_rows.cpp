@@ -363,6 +363,9 @@ struct orbx_vocabulary {
     double* d_weight = nullptr;
 };
 
+int vocabularyScoring(const orbx_vocabulary* v) { return v->scoring; }
+int vocabularyDeviceIndex(const orbx_vocabulary* v) { return v->device; }
+
 extern "C" {
 
 void orbx_vocabulary_destroy(orbx_vocabulary* v) {

@@ -47,6 +47,12 @@ POSE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_initial", "<i4"), ("n_bad",
                               ("empty_rounds", "<i4"), ("its", "<i4", 4), ("trials", "<i4", 4), ("lambda", "<f8", 4), ("chi2", "<f8", 4)])
 assert POSE_PROBLEM_DTYPE.itemsize == 188 and POSE_RESULT_DTYPE.itemsize == 120
 POSE_OPTIMIZATION_STATUS = ("ALL_ROUNDS", "FEW_EDGES", "TOO_FEW", "BAD_ARGUMENT")
+# == orbx_place_result / enum orbx_place_mode / enum orbx_place_status
+PLACE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"),
+                               ("n_scored", "<i4"), ("best_acc_score", "<f4"), ("n_loop", "<i4"), ("n_merge", "<i4")])
+assert PLACE_RESULT_DTYPE.itemsize == 32
+PLACE_N_BEST, PLACE_RELOCALIZATION = 0, 1
+PLACE_STATUS = ("OK", "NO_SHARING", "NONE_SCORED", "EMPTY_DATABASE", "EMPTY_QUERY", "BAD_KEYFRAME", "TRUNCATED")
 FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION = 0, 1      # orbx_frustum_mode
 (FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH, FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR,
  FRUSTUM_REQUEST) = range(7)                           # orbx_frustum_exit
@@ -242,6 +248,10 @@ def load_library():
     L.orbx_debug_sim3_solve_steps.argtypes = [C.c_int]
     L.orbx_optimize_pose_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     L.orbx_debug_pose_optimization_launches.argtypes = []
+    if hasattr(L, "orbx_detect_candidates_device"):      # (an earlier build loaded through ORBX_LIBRARY for an A/B has no such export)
+        L.orbx_detect_candidates_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                                    C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+        L.orbx_debug_place_recognition_launches.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -644,6 +654,26 @@ class ORBextractor:
     def debug_pose_optimization_launches(self):
         """launches of the pose optimiser's kernel so far in this process (it has one launch form)"""
         return self._L.orbx_debug_pose_optimization_launches()
+
+    def detect_candidates_device(self, vocab, mode, n_db, d_db_word_ids, d_db_word_weights, d_db_n_words, capacity, d_db_map_id, d_db_flags,
+                                 d_db_covis, n_queries, queries, d_q_word_ids, d_q_word_weights, d_q_n_words, q_capacity, d_q_map_id, d_score,
+                                 d_result, d_connected=None, n_candidates=3, d_loop=None, d_merge=None, d_cand=None, cand_capacity=0,
+                                 d_common_words=None):
+        """KeyFrameDatabase::DetectNBestCandidates (mode PLACE_N_BEST) / DetectRelocalizationCandidates (PLACE_RELOCALIZATION) (reference
+        src/KeyFrameDatabase.cc:612-780, :783-895) for n_queries queries against n_db database rows in KeyFrameDatabase::add order; queries
+        = (first, step) into the query arrays.  The three BoW arrays are compute_bow_device's layout.  d_db_flags: bit 0 isBad(), bit 1
+        GetMap()->IsBad(); d_db_covis [k*10 + j] database rows or -1; d_connected [q*n_db + k] (N_BEST, None = none); d_score [q*n_db + k]
+        in/out (mPlaceRecognitionScore / mRelocScore: state); d_result one PLACE_RESULT_DTYPE row per query; d_loop / d_merge
+        [q*n_candidates + i] (N_BEST), d_cand [q*cand_capacity + i] (RELOCALIZATION); d_common_words [q*n_db + k] optional."""
+        self._check(self._L.orbx_detect_candidates_device(
+            self._h, vocab._v, int(mode), n_db, _dev(d_db_word_ids), _dev(d_db_word_weights), _dev(d_db_n_words), capacity, _dev(d_db_map_id),
+            _dev(d_db_flags), _dev(d_db_covis), n_queries, queries[0], queries[1], _dev(d_q_word_ids), _dev(d_q_word_weights), _dev(d_q_n_words),
+            q_capacity, _dev(d_q_map_id), _dev(d_connected), n_candidates, _dev(d_score), _dev(d_result), _dev(d_loop), _dev(d_merge), _dev(d_cand),
+            cand_capacity, _dev(d_common_words)))
+
+    def debug_place_recognition_launches(self, which):
+        """launches so far in this process of k_place_pairs (which = 0) / k_place_query (which = 1): the entry has one launch form"""
+        return self._L.orbx_debug_place_recognition_launches(which)
 
     def project_last_frame_device(self, n_pairs, last, cur, d_kps, d_kps_un, d_n, capacity, d_mp_flags, d_world, d_poses, cam, bounds,
                                   mbf, mb, th, mono, d_queries):

@@ -627,6 +627,93 @@ int orbx_compute_bow_device(orbx_handle* h, const orbx_vocabulary* v, int n_fram
                             int levels_up, uint32_t* d_word_ids, double* d_word_weights, int* d_n_words, uint32_t* d_feat_nodes,
                             uint32_t* d_feat_idx, int* d_n_feat);
 
+/* ---- the consumer of the BowVector: KeyFrameDatabase's place recognition -----------------------------------------------------------
+ * KeyFrameDatabase::DetectNBestCandidates (src/KeyFrameDatabase.cc:612-780; LoopClosing::NewDetectCommonRegions, src/LoopClosing.cc:463:
+ * the vpLoopBowCand / vpMergeBowCand that orbx_search_by_bow_keyframes_device -> orbx_sim3_solve_device ->
+ * orbx_search_by_projection_sim3_device start from) and KeyFrameDatabase::DetectRelocalizationCandidates (:783-895;
+ * Tracking::Relocalization, src/Tracking.cc:3192: the keyframes orbx_search_by_bow_device -> orbx_optimize_pose_device ->
+ * orbx_frustum_requests_device(RELOCALIZATION) -> orbx_search_by_projection_device start from) for n_queries independent queries against
+ * one database of n_db keyframe rows.  Who is in the database and who observes whom stays with the caller: the add / erase bookkeeping
+ * is not built.  DetectLoopCandidates, DetectCandidates and DetectBestCandidates have no caller in the reference and are not built. */
+enum orbx_place_mode {
+    ORBX_PLACE_N_BEST = 0,                 /* DetectNBestCandidates(pKF, vpLoopCand, vpMergeCand, nNumCandidates) */
+    ORBX_PLACE_RELOCALIZATION = 1          /* DetectRelocalizationCandidates(F, pMap) */
+};
+/* How a query left the function; every way out has a name: */
+enum orbx_place_status {
+    ORBX_PLACE_OK = 0,                     /* the function ran to its end */
+    ORBX_PLACE_NO_SHARING = 1,             /* lKFsSharingWords.empty() (:655, :808): no row shares a word (N_BEST: no row that is not connected) */
+    ORBX_PLACE_NONE_SCORED = 2,            /* lScoreAndMatch.empty() (:686, :839).  Unreachable - the row that holds maxCommonWords passes its own
+                                            * threshold - and kept as a name */
+    ORBX_PLACE_EMPTY_DATABASE = 3,         /* n_db == 0: NO_SHARING, named apart */
+    ORBX_PLACE_EMPTY_QUERY = 4,            /* the query has no words: NO_SHARING, named apart */
+    ORBX_PLACE_BAD_KEYFRAME = 5,           /* N_BEST: `if(pKFi->isBad()) continue;` (:735-736) advances neither i nor it - once a bad keyframe
+                                            * reaches the front of the walk the reference never returns.  The entry stops there and writes what
+                                            * was collected.  SetBadFlag erases a keyframe from the database, so only a caller's row with bit 0 of
+                                            * its flags set gets here */
+    ORBX_PLACE_TRUNCATED = 6               /* RELOCALIZATION: the list is longer than cand_capacity; its first cand_capacity entries are written,
+                                            * n_loop holds the true count */
+};
+/* One row per query.  Every field computed before the exit holds its value, the rest is zero. */
+typedef struct orbx_place_result {
+    int32_t status;                /* orbx_place_status */
+    int32_t n_sharing;             /* lKFsSharingWords.size() */
+    int32_t max_common_words;      /* maxCommonWords */
+    int32_t min_common_words;      /* minCommonWords = maxCommonWords*0.8f: a float product truncated to int; a row is scored when words > it */
+    int32_t n_scored;              /* nscores = lScoreAndMatch.size() */
+    float best_acc_score;          /* bestAccScore */
+    int32_t n_loop;                /* N_BEST: vpLoopCand.size(); RELOCALIZATION: vpRelocCandidates.size(), whatever cand_capacity is */
+    int32_t n_merge;               /* N_BEST: vpMergeCand.size() */
+} orbx_place_result;
+
+/*   v               : the vocabulary the BoW vectors were made with.  Only L1_NORM scoring (ORBvoc.txt's) is built: another scoring returns
+ *                     ORBX_ERR_UNSUPPORTED before any launch.
+ *   d_db_word_ids[k*capacity + j], d_db_word_weights[k*capacity + j], d_db_n_words[k] : the mBowVec of database row k, the layout
+ *                     orbx_compute_bow_device writes (a keyframe's row is a copy of what that entry produced).  The n_db rows are IN THE ORDER
+ *                     OF KeyFrameDatabase::add, erased keyframes removed: that is the order inside every mvInvertedFile[word] (:39-66).
+ *   d_db_map_id[k]  : GetMap() as a number.  d_db_flags[k]: bit 0 = isBad(), bit 1 = GetMap()->IsBad().  Bit 1 is the MAP's: it must be the same
+ *                     on every row of one map; the entry reads it from the candidate's own row.
+ *   d_db_covis[k*10 + j] : GetBestCovisibilityKeyFrames(10) as database rows, in that function's order; -1 for a neighbour that is not in
+ *                     the database or a list shorter than ten (a value outside [0, n_db) is skipped).
+ *   q_first, q_step, d_q_word_ids, d_q_word_weights, d_q_n_words, q_capacity : query q is row q_first + q*q_step of these arrays (no index
+ *                     may be negative): the frames orbx_compute_bow_device just wrote can be used directly.  d_q_map_id[q]: the map of pKF
+ *                     (N_BEST), pMap (RELOCALIZATION).
+ *   d_connected[q*n_db + k] : N_BEST: non-zero when row k is in pKF->GetConnectedKeyFrames() (:622, :638); NULL = none.  Such a row never
+ *                     enters the list and never takes the query's id: it does not count towards maxCommonWords and is skipped as a
+ *                     covisibility neighbour (:704).  Ignored in RELOCALIZATION mode, whose reference has no such test.
+ *   n_candidates    : nNumCandidates (3 at the call site), N_BEST only; 0 returns no candidate.
+ *   d_score[q*n_db + k] : IN AND OUT, mPlaceRecognitionScore / mRelocScore.  The reference writes the field only for the rows that pass the
+ *                     word threshold (:681, :834) and reads it for every covisibility neighbour that carries the query's id (:707-711,
+ *                     :860-864), rows that share a word but did not pass included: for those it reads what an EARLIER query left (the
+ *                     constructor sets mPlaceRecognitionScore to 0 and leaves mRelocScore uninitialised, src/KeyFrame.cc:34-35, :52).  So
+ *                     this is state, one row per query: the entry reads it, overwrites only the rows it scores and leaves the rest byte for
+ *                     byte; a caller that replays the reference's sequence of queries hands each query the previous one's row.  The entry
+ *                     promises "what the reference returns from this state".  Assumed: no database row carries the query's id before the
+ *                     call (the reference's ids are unique and each is queried once).
+ *   d_result[q]     : see above.
+ *   d_loop[q*n_candidates + i], d_merge[..] : N_BEST: vpLoopCand / vpMergeCand as database rows; entries from n_loop / n_merge on are not
+ *                     touched.  d_cand[q*cand_capacity + i]: RELOCALIZATION: vpRelocCandidates; entries from n_loop on are not touched.
+ *   d_common_words[q*n_db + k] : optional (NULL), the words row k shares with query q, connected rows included.
+ * Order: lKFsSharingWords is in order of first encounter - the query's words ascending, each word's inverted list in `add` order - which is
+ * the order of (smallest shared word id, database row); lScoreAndMatch and lAccScoreAndMatch keep it.  RELOCALIZATION never sorts: that is
+ * its output order.  N_BEST's list::sort(compFirst) is stable on a.first > b.first: equal accumulated scores stay in list order.  The
+ * score is L1Scoring::score as written: a double 0, for every common word in ascending id score += fabs(vi - wi) - fabs(vi) - fabs(wi), a
+ * SEQUENTIAL sum of three-rounding terms, then -score/2.0 narrowed to float.  accScore is a float sum in neighbour order, pBestKF the first
+ * strictly greater score, bestAccScore starts at 0.  RELOCALIZATION keeps accScore > 0.75f*bestAccScore, skips another map's keyframe
+ * before the duplicate set, then drops duplicates of pBestKF.  N_BEST walks on while either list is short; a keyframe enters the duplicate
+ * set whether or not it was pushed (a same-map entry met when the loop list is full, a merge candidate of a bad map).
+ * Two launches: k_place_pairs, one wave per (query, row) with the query's words staged in 12*q_capacity bytes of LDS, and k_place_query,
+ * one workgroup per query with 12 bytes per list slot (a power of two of slots) and 4 per row.  Both must fit 160 KB - 512: q_capacity
+ * <= 13610 and n_db <= 8192, else ORBX_ERR_UNSUPPORTED before anything is launched or allocated.  No bound depends on the data: every
+ * list has room for all n_db rows.  n_queries <= 65535.  The pairs' workspace (12 bytes per query and row) belongs to the handle and
+ * grows on first use.  ORBX_ERR_BAD_ARGUMENT is returned before any launch.  Asynchronous on the handle's stream; no CPU path. */
+int orbx_detect_candidates_device(orbx_handle* h, const orbx_vocabulary* v, int mode, int n_db, const uint32_t* d_db_word_ids,
+                                  const double* d_db_word_weights, const int* d_db_n_words, int capacity, const int* d_db_map_id,
+                                  const uint8_t* d_db_flags, const int* d_db_covis, int n_queries, int q_first, int q_step,
+                                  const uint32_t* d_q_word_ids, const double* d_q_word_weights, const int* d_q_n_words, int q_capacity,
+                                  const int* d_q_map_id, const uint8_t* d_connected, int n_candidates, float* d_score, orbx_place_result* d_result,
+                                  int* d_loop, int* d_merge, int* d_cand, int cand_capacity, int* d_common_words);
+
 /* ---- the consumer of the FeatureVector: ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) ------------------
  * (src/ORBmatcher.cc:269-471; Tracking::TrackReferenceKeyFrame, Tracking::Relocalization), Nleft == -1: for n_pairs pairs
  * (keyframe = frame kf_first + p*kf_step, current frame = frame cur_first + p*cur_step of one device-resident batch) the features of
@@ -664,7 +751,7 @@ int orbx_search_by_bow_keyframes_device(orbx_handle* h, int n_pairs, int kf1_fir
  * Nleft = d_n_out[2X], Nright = d_n_out[2X + 1].  kf_step = 0 (one keyframe, many frames) and cur_step = 0 (relocalisation) are allowed.
  *   d_feat_nodes, d_feat_idx, d_n_feat : what orbx_compute_bow_device wrote PER EYE (frames 2X and 2X + 1), same capacity.  The mFeatVec of
  *                 the stacked descriptors is not needed: a node's list there is the left eye's list followed by the right eye's (+ Nleft),
- *                 and the entry walks them so.  (The pair's mBowVec, which KeyFrameDatabase needs and this matcher does not, is what
+ *                 and the entry walks them so.  (The pair's mBowVec, which orbx_detect_candidates_device reads and this matcher does not, is what
  *                 orbx_compute_bow_device gives for the two descriptor blocks packed back to back as one frame.)
  *   d_kf_mp_flags[(2p + eye)*capacity + i] : bit 0 = keypoint i of that eye of the KEYFRAME holds a MapPoint that is not bad (:301-307)
  *   d_kps[f*capacity + i] : the extraction's RAW keypoints of all frames; only .angle is read, of the eye the index falls in (:382-391,
@@ -1387,6 +1474,9 @@ int orbx_debug_two_view_shape(int shape);
 int orbx_debug_sim3_solve_steps(int mask);
 /* orbx_optimize_pose_device has ONE launch form: the launches of its kernel so far in this process (one per accepted call). */
 int orbx_debug_pose_optimization_launches(void);
+/* orbx_detect_candidates_device has ONE launch form of two kernels: the launches so far in this process of k_place_pairs (which = 0; none for
+ * a call with n_db == 0) and of k_place_query (which = 1; one per accepted call). */
+int orbx_debug_place_recognition_launches(int which);
 int orbx_debug_new_map_points_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
