@@ -20,8 +20,12 @@
 // per lane, minThFAST folded into the neighbour maximum).
 //
 // LDS: each wave stages its ROI (<= 45 x 45 for the usual 31..37-px cells) re-aligned so that the cell interior starts
-// on a tile dword (a 31/32-px cell is then 8 dwords wide = 4 wave iterations per pass), then keeps the 8-bit score
-// tile next to it on the same dword grid.  Strides are compile-time so ring offsets are instruction immediates.
+// on a tile dword (a 31/32-px cell is then 8 dwords wide = 4 wave iterations per pass), then keeps the score tile next
+// to it on the same item grid.  The 48 x 45 tile's score tile holds a u16 per pixel: the score pass's two result
+// registers stored as they are, which the NMS pass reads back as the packed pairs it computes on (neighbour pairs by
+// v_alignbyte, no unpacking); the 72 x 69 tile keeps a byte per pixel, unpacked with v_perm (k_fast_body.hpp:
+// ScoreTile has the LDS sums).  Only the tile's apron is zeroed; the score pass writes every interior item.
+// Strides are compile-time so ring offsets are instruction immediates.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -42,8 +46,12 @@ __global__ __launch_bounds__(256, ORBX_FAST_WAVES) void k_fast(const CellDesc* _
                                                typename CandFmt<BIG>::T* __restrict__ candSeg, unsigned* __restrict__ cellCount, int f0, int nFrames,
                                                BlurTail tail, LeafTables lt) {
     using L = FastLds<TS, ROWS>;
-    __shared__ __align__(16) uint8_t smem[L::kTiles];
-    __shared__ __align__(16) uint8_t scoreS[L::kScores];
+    __shared__ __align__(16) uint8_t smem[L::kTiles + ORBX_FAST_LDS_PAD];
+    uint8_t* scoreS = nullptr;      // (pair form: the score tiles share smem with the pixel tiles)
+    if constexpr (!L::kPair) {
+        __shared__ __align__(16) uint8_t scoreArr[L::kScores];
+        scoreS = scoreArr;
+    }
     __shared__ uint8_t codeL[kFastWaves][2][64];
     int chunk, fr;
     if (!xcdChunkFrame(nFrames, chunk, fr)) return;   // all cells of a frame on one XCD: the 6-px ROI overlap of neighbouring cells hits its L2
@@ -71,7 +79,9 @@ __global__ __launch_bounds__(256) void k_fast_wide(const CellDesc* __restrict__ 
                                                     const uint8_t* __restrict__ pyr, int iniTh, int minTh,
                                                     unsigned* __restrict__ candSeg, unsigned* __restrict__ cellCount, int f0, int nFrames,
                                                     BlurTail tail, LeafTables lt) {
-    constexpr int kTileBytes = TS * ROWS, kScoreBytes = TS * (ROWS - 4), DW = TS / 4;
+    constexpr bool PAIR = kFastPairTile<TS>;      // the score tile's form (k_fast_body.hpp: ScoreTile)
+    constexpr int RS = ScoreTile<PAIR, TS>::kStride, IB = ScoreTile<PAIR, TS>::kItem;
+    constexpr int kTileBytes = TS * ROWS, kScoreBytes = RS * (ROWS - 4), DW = TS / 4;
     constexpr int LPR = DW <= 16 ? 8 : 16, RPI = 256 / LPR, STEPS = (ROWS + RPI - 1) / RPI;      // lanes per row while staging, rows per step
     static_assert(DW % 2 == 0 && TS % 8 == 0, "dword pairs per tile row");
     constexpr int kRounds = (DW * (ROWS - 6) + 255) / 256;      // trips of 256 items over the largest cell
@@ -122,13 +132,11 @@ __global__ __launch_bounds__(256) void k_fast_wide(const CellDesc* __restrict__ 
         }
     }
     if (leaf && tid < 128) codeL[tid >> 6][tid & 63] = myCode;
-#pragma unroll
-    for (int i = 0; i < (kScoreBytes + 1023) / 1024; i++)
-        if (tid * 4 + i * 1024 < kScoreBytes) *(unsigned*)(score + tid * 4 + i * 1024) = 0u;
-    __syncthreads();
-    FAST_MID(0);
     const int q0 = (mis + 3) >> 2, q1 = (mis + 2 + cw) >> 2, nq = q1 - q0 + 1;
     const int nItems = nq * ch;
+    clearScoreApron<PAIR, TS, 1>(score, tid, ch, q0, q1);      // (one row below the interior: threads past the last item read the tile's top, not row ch + 1)
+    __syncthreads();
+    FAST_MID(0);
     const int sy = (256 * c.itemRecip) >> 16, sx = 256 - sy * nq;                // 256 / nq, 256 % nq (exact: CellDesc::itemRecip)
     const int y0w = (tid * c.itemRecip) >> 16, qi0w = tid - y0w * nq;             // tid / nq, tid % nq
     // ---- pass 1: scores (one thread = the four pixels of one tile dword) ----
@@ -154,7 +162,7 @@ __global__ __launch_bounds__(256) void k_fast_wide(const CellDesc* __restrict__ 
             const unsigned sB = pairScore(rB);
             unsigned m = qi == 0 ? maskFirst : 0xFFFFFFFFu;
             m = qi == nq - 1 ? (m & maskLast) : m;
-            *(unsigned*)(score + (y + 1) * TS + 4 * (q0 + qi)) = __builtin_amdgcn_perm(sB, sA, 0x06040200u) & m;
+            storeScores<PAIR>(score + (y + 1) * RS + IB * (q0 + qi), sA, sB, PAIR ? pairMaskLo(m) : m, pairMaskHi(m));
             qi += sx; y += sy;
             if (qi >= nq) { qi -= nq; y++; }
         }
@@ -182,22 +190,9 @@ __global__ __launch_bounds__(256) void k_fast_wide(const CellDesc* __restrict__ 
 #pragma unroll
         for (int r = 0; r < kRounds; r++) {
             const bool act = r * 256 + tid < nItems;
-            const uint8_t* base = score + (act ? y * TS + 4 * (q0 + qi) : 4);
-            unsigned U[3], M[3], D[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                U[k] = *(const unsigned*)(base + 4 * k - 4);
-                M[k] = *(const unsigned*)(base + TS + 4 * k - 4);
-                D[k] = *(const unsigned*)(base + 2 * TS + 4 * k - 4);
-            }
-            const unsigned Wa = pkmax3(pairAt<3>(U[0], U[1], U[2]), pairAt<3>(D[0], D[1], D[2]), thPair);
-            const unsigned Wb = pkmax3(pairAt<4>(U[0], U[1], U[2]), pairAt<4>(D[0], D[1], D[2]), thPair);
-            const unsigned Wc = pkmax3(pairAt<5>(U[0], U[1], U[2]), pairAt<5>(D[0], D[1], D[2]), thPair);
-            const unsigned Wd = pkmax3(pairAt<6>(U[0], U[1], U[2]), pairAt<6>(D[0], D[1], D[2]), thPair);
-            const unsigned We = pkmax3(pairAt<7>(U[0], U[1], U[2]), pairAt<7>(D[0], D[1], D[2]), thPair);
-            const unsigned Ma = pairAt<3>(M[0], M[1], M[2]), Mc = pairAt<5>(M[0], M[1], M[2]), Me = pairAt<7>(M[0], M[1], M[2]);
-            const unsigned sA = pairAt<4>(M[0], M[1], M[2]), sB = pairAt<6>(M[0], M[1], M[2]);
-            const unsigned mA = pkmax3(pkmax3(Wa, Wb, Wc), Ma, Mc), mB = pkmax3(pkmax3(Wc, Wd, We), Mc, Me);
+            const uint8_t* base = score + (act ? y * RS + IB * (q0 + qi) : IB);      // (not active: any item of the tile's top, the result is not used)
+            unsigned sA, sB, mA, mB;
+            nmsNeighbourMax<PAIR, TS>(base, thPair, sA, sB, mA, mB);
             unsigned dA, dB;
             asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dA) : "v"(sA), "v"(mA));
             asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dB) : "v"(sB), "v"(mB));

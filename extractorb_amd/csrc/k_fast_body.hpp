@@ -42,6 +42,107 @@ __device__ __forceinline__ unsigned pairAt(unsigned L, unsigned C, unsigned R) {
     else return __builtin_amdgcn_perm(R, C, 0x0C000C00u | (O - 4) | ((O - 3) << 16));
 }
 
+// The two pair masks of a byte mask (0xFF per kept pixel of a tile dword): bytes 0, 1 and bytes 2, 3 of m, each widened to its u16 half
+__device__ __forceinline__ unsigned pairMaskLo(unsigned m) { return __builtin_amdgcn_perm(0u, m, 0x01010000u); }
+__device__ __forceinline__ unsigned pairMaskHi(unsigned m) { return __builtin_amdgcn_perm(0u, m, 0x03030202u); }
+
+// ---- the score tile.  Two forms, chosen per tile shape at compile time (kFastPairTile):
+//   byte form: one byte per pixel on the pixel tile's dword grid (row stride TS, an item = one dword);
+//   pair form: one u16 per pixel, i.e. the score pass's two result registers sA | sB stored as they are (row stride 2 * TS, an item = 8 bytes).
+// Row 0 and rows ch + 1, ch + 2 and the dword left / right of every row's items stand for "outside the cell interior" and hold 0.
+template <bool PAIR, int TS> struct ScoreTile {
+    static constexpr int kStride = PAIR ? 2 * TS : TS;      // bytes per score row
+    static constexpr int kItem = PAIR ? 8 : 4;              // bytes of one item (four pixels) in a score row
+};
+// 48-byte rows take the pair form: k_fast<48,45> with the score rows laid over the pixel tile (orbx_device.hpp: FastAlias; 17 232 B per
+// workgroup as before), k_fast_wide<48,45> with a tile of its own (6.3 KB per workgroup instead of 4.3).  The 72-byte tile (cells up to 63 px)
+// keeps the byte form: its workgroup holds 39 KB already (four per CU); a pair tile of its own would make it 58 KB (two per CU).
+#ifndef ORBX_FAST_PAIR_TILE
+#define ORBX_FAST_PAIR_TILE 1   // 0 (A/B builds): the byte form for every tile
+#endif
+template <int TS> constexpr bool kFastPairTile = ORBX_FAST_PAIR_TILE && TS <= 48;
+
+// The neighbour maximum of the NMS pass, the one statement of it for every kernel and both tile forms.  base: the item in the score row ABOVE
+// the centre row.  Out: sA, sB = the item's four scores as two u16 pairs, mA, mB = per pixel the maximum of its eight neighbours and minThFAST
+// (thPair), so "strict local maximum above minThFAST" is S > m.
+// Pair form: per row the four dwords P | A | B | N (previous pair, the item's two, next pair: one 4-, one 8- and one 4-byte read);
+// V[k] = max(up, down, th) per dword, the three pairs shifted by one pixel (x-1,x) (x+1,x+2) (x+3,x+4) of V and of the centre row by
+// v_alignbyte - the middle one serves both centres - and two 3-input maxima per centre pair: 4 + 6 + 4 instructions.
+// Byte form: nine dwords, the 3 x 5 pairs cut out with v_perm (15), nine maxima.
+template <bool PAIR, int TS>
+__device__ __forceinline__ void nmsNeighbourMax(const uint8_t* base, const unsigned thPair, unsigned& sA, unsigned& sB, unsigned& mA, unsigned& mB) {
+    constexpr int RS = ScoreTile<PAIR, TS>::kStride;
+    if constexpr (PAIR) {
+        unsigned R[3][4];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const uint2 ab = *(const uint2*)(base + r * RS);
+            R[r][0] = *(const unsigned*)(base + r * RS - 4);
+            R[r][1] = ab.x; R[r][2] = ab.y;
+            R[r][3] = *(const unsigned*)(base + r * RS + 8);
+        }
+        unsigned V[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) V[k] = pkmax3(R[0][k], R[2][k], thPair);
+        const unsigned Vl = __builtin_amdgcn_alignbyte(V[1], V[0], 2), Vm = __builtin_amdgcn_alignbyte(V[2], V[1], 2), Vr = __builtin_amdgcn_alignbyte(V[3], V[2], 2);
+        const unsigned Ml = __builtin_amdgcn_alignbyte(R[1][1], R[1][0], 2), Mm = __builtin_amdgcn_alignbyte(R[1][2], R[1][1], 2), Mr = __builtin_amdgcn_alignbyte(R[1][3], R[1][2], 2);
+        sA = R[1][1]; sB = R[1][2];
+        mA = pkmax3(pkmax3(V[1], Vl, Vm), Ml, Mm);
+        mB = pkmax3(pkmax3(V[2], Vm, Vr), Mm, Mr);
+    } else {
+        unsigned U[3], M[3], D[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            U[k] = *(const unsigned*)(base + 4 * k - 4);
+            M[k] = *(const unsigned*)(base + RS + 4 * k - 4);
+            D[k] = *(const unsigned*)(base + 2 * RS + 4 * k - 4);
+        }
+        // pairs a..e = bytes (3,4) (4,5) (5,6) (6,7) (7,8) of L|C|R; up/down maxima per pair column, threshold folded in
+        const unsigned Wa = pkmax3(pairAt<3>(U[0], U[1], U[2]), pairAt<3>(D[0], D[1], D[2]), thPair);
+        const unsigned Wb = pkmax3(pairAt<4>(U[0], U[1], U[2]), pairAt<4>(D[0], D[1], D[2]), thPair);
+        const unsigned Wc = pkmax3(pairAt<5>(U[0], U[1], U[2]), pairAt<5>(D[0], D[1], D[2]), thPair);
+        const unsigned Wd = pkmax3(pairAt<6>(U[0], U[1], U[2]), pairAt<6>(D[0], D[1], D[2]), thPair);
+        const unsigned We = pkmax3(pairAt<7>(U[0], U[1], U[2]), pairAt<7>(D[0], D[1], D[2]), thPair);
+        const unsigned Ma = pairAt<3>(M[0], M[1], M[2]), Mc = pairAt<5>(M[0], M[1], M[2]), Me = pairAt<7>(M[0], M[1], M[2]);
+        sA = pairAt<4>(M[0], M[1], M[2]); sB = pairAt<6>(M[0], M[1], M[2]);
+        mA = pkmax3(pkmax3(Wa, Wb, Wc), Ma, Mc); mB = pkmax3(pkmax3(Wc, Wd, We), Mc, Me);
+    }
+}
+// The score pass's store of one item: sA, sB = the four scores as two u16 pairs, m = the item's byte mask (0xFF per pixel inside the interior)
+// in the byte form, (mLo, mHi) = its pair masks in the pair form.
+template <bool PAIR>
+__device__ __forceinline__ void storeScores(uint8_t* dst, unsigned sA, unsigned sB, unsigned mLo, unsigned mHi) {
+    if constexpr (PAIR) *(uint2*)dst = uint2{sA & mLo, sB & mHi};
+    else *(unsigned*)dst = __builtin_amdgcn_perm(sB, sA, 0x06040200u) & mLo;
+}
+// Zero what the NMS pass reads as "outside the interior" and the score pass does not write (it writes every item of rows 1 .. ch, masked):
+// row 0, the BELOW rows under the interior (whole rows, 8-byte stores), and the dword left of item q0 and right of item q1 of rows 1 .. ch
+// (thread t: row t + 1).  t: the thread's index among the >= 64 that call it (3 * kStride / 8 <= 64, ch <= 63).
+// TRIM (pair form, called BEHIND a score pass that stored every item whole): also the pixels past the interior in the last item of every row,
+// validLast .. 3 of item q1 - then the score pass carries no masks at all (two registers and two v_and per trip).  The registers matter: with
+// the two pair masks k_fast<48,45> needed 58 VGPRs, allocated as 64, and the step was 0.4 % SLOWER than with the byte tile although the kernel
+// alone was 2 % faster; at 53 (allocated 56, as the byte form's 56) the step is 1.4 % faster (profiles/r32_fast_pair_scores.md).  Beside the
+// waves of the kernels that overlap it, 56 registers a wave let one more cell-wave onto a SIMD than 64.  Keep k_fast<48,45> at or under 56.
+template <bool PAIR, int TS, int BELOW, bool TRIM = false>
+__device__ __forceinline__ void clearScoreApron(uint8_t* score, int t, int ch, int q0, int q1, int validLast = 4) {
+    constexpr int RS = ScoreTile<PAIR, TS>::kStride, IB = ScoreTile<PAIR, TS>::kItem, RD = RS / 8;
+    static_assert(RS % 8 == 0 && (1 + BELOW) * RD <= 64, "the zero rows are one trip of 8-byte stores");
+    static_assert(!TRIM || PAIR, "whole u16 pixels");
+    if (t < (1 + BELOW) * RD) {
+        const int r = t / RD, c = t - r * RD;
+        *(uint2*)(score + (r == 0 ? 0 : ch + r) * RS + 8 * c) = uint2{0u, 0u};
+    }
+    if (t < ch) {
+        *(unsigned*)(score + (t + 1) * RS + IB * q0 - 4) = 0u;
+        *(unsigned*)(score + (t + 1) * RS + IB * (q1 + 1)) = 0u;
+        if constexpr (TRIM) {      // (validLast is uniform) 1: pixel 1 and pixels 2, 3; 2: pixels 2, 3; 3: pixel 3
+            uint8_t* last = score + (t + 1) * RS + IB * q1;
+            if (validLast & 1) *(unsigned short*)(last + 2 * validLast) = 0;
+            if (validLast <= 2) *(unsigned*)(last + 4) = 0u;
+        }
+    }
+}
+
 // Ring of the two pixels at bytes P, P+1 of the centre dword (P = 0 or 2) in cv::FAST order, r[16] = the centre pair:
 // L/C/R[d] = the three dwords of tile row (centre row + d - 3).
 template <int P>
@@ -137,6 +238,9 @@ constexpr int kFastWaves = 4;
 #ifndef ORBX_FAST_SKIP
 #define ORBX_FAST_SKIP 0   // diagnostic builds (tools/fast_breakdown.py): 1 = no score pass, 2 = stop after the score pass, 4 = no staging loads
 #endif
+#ifndef ORBX_FAST_LDS_PAD
+#define ORBX_FAST_LDS_PAD 0   // A/B builds: bytes of unused static LDS added to a k_fast workgroup (what a larger tile would cost in resident workgroups)
+#endif
 
 // Atomics on an LDS word whose address the compiler may see as a generic pointer (a body inlined behind pointer arguments): the cast names the
 // address space, so the instruction is a ds_* whatever the optimiser merged around it.
@@ -161,24 +265,32 @@ struct BlurTail { const BlurItem* items; const unsigned short* laneItem; int nLa
 // row's first interior dword), the score tiles as an array of their own (their base is then one scalar, and the NMS pass's nine reads are
 // immediate offsets of ONE address register; inside one array they sat 2 KB behind the pixel tile's base, past the reach of ds_read2's
 // offsets: four v_add per trip), and the cells' x / y path codes (small batches: leaf tables).
+// Pair form: the score tile lives in the pixel tiles' array, one region of FastAlias::kWaveBytes per wave (orbx_device.hpp has the layout and
+// why the two may share bytes); there is no second array.
 template <int TS, int ROWS>
 struct FastLds {
-    static constexpr int kTileBytes = TS * ROWS, kScoreBytes = TS * (ROWS - 3);
-    static constexpr int kTiles = 16 + kFastWaves * kTileBytes, kScores = kFastWaves * kScoreBytes, kCodes = kFastWaves * 2 * 64;
+    static constexpr bool kPair = kFastPairTile<TS>;
+    static constexpr int kTileBytes = TS * ROWS, kScoreBytes = kPair ? 0 : TS * (ROWS - 3);
+    static constexpr int kWaveBytes = kPair ? FastAlias<TS, ROWS>::kWaveBytes : kTileBytes;      // a wave's share of the first array
+    static constexpr int kTiles = 16 + kFastWaves * kWaveBytes, kScores = kFastWaves * kScoreBytes, kCodes = kFastWaves * 2 * 64;
     static constexpr int kScoreOff = (kTiles + 15) & ~15, kCodeOff = (kScoreOff + kScores + 15) & ~15, kBytes = kCodeOff + kCodes;
 };
 
 // One cell on one wave (the whole of k_fast's work).  smem / scoreS / codeL: the workgroup's
-// three LDS arrays (FastLds), chunk: the workgroup's group of four cells, f: the frame.  No workgroup barrier.
+// three LDS arrays (FastLds; scoreS is not used in the pair form), chunk: the workgroup's group of four cells, f: the frame.  No workgroup barrier.
 // BIG: the candidates are written in the two-dword format of frames beyond 4096 px (orbx_device.hpp: CandFmt).
 template <int TS, int ROWS, bool BIG = false>
 __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int nCells, const LevelGeom* __restrict__ lv,
                                          const uint8_t* __restrict__ pyr, int iniTh, int minTh,
                                          typename CandFmt<BIG>::T* __restrict__ candSeg, unsigned* __restrict__ cellCount, LeafTables lt,
                                          uint8_t* smem, uint8_t* scoreS, uint8_t (*codeL)[2][64], int chunk, int f) {
-    constexpr int kTileBytes = TS * ROWS;             // pixel tile
-    constexpr int kScoreBytes = TS * (ROWS - 3);      // score tile: (ch + 2) rows <= ROWS - 4, and one more zero row for the NMS lanes past the last item
-    constexpr int DW = TS / 4;                        // dwords per tile row
+    constexpr bool PAIR = kFastPairTile<TS>;          // the score tile's form (ScoreTile)
+    constexpr int RS = ScoreTile<PAIR, TS>::kStride, IB = ScoreTile<PAIR, TS>::kItem;
+    constexpr int kScoreBytes = RS * (ROWS - 3);      // score tile: (ch + 2) rows <= ROWS - 4, and one more zero row for the NMS lanes past the last item
+    using L = FastLds<TS, ROWS>;
+    using A = FastAlias<TS, ROWS>;                    // (pair form only)
+    static_assert(!PAIR || (A::kScoreStride == RS && A::kScoreItem == IB && kScoreBytes <= A::kWaveBytes), "FastAlias states this tile");
+    constexpr int DW = TS / 4;                       // dwords per tile row
     constexpr int LPR = DW <= 16 ? 8 : 16;            // lanes per row while staging: a lane moves TWO dwords (one 8-byte load, one 8-byte LDS store)
     constexpr int RPI = 64 / LPR;                     // rows per staging step
     constexpr int STEPS = (ROWS + RPI - 1) / RPI;
@@ -189,8 +301,9 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
     FAST_CLOCK_BEGIN
     const CellDesc c = cells[ci];
     const LevelGeom g = lv[c.level];
-    uint8_t* tile = smem + 16 + wave * kTileBytes;
-    uint8_t* score = scoreS + wave * kScoreBytes;
+    uint8_t* const region = smem + 16 + wave * L::kWaveBytes;
+    uint8_t* tile = PAIR ? region + A::kPixelOff : region;
+    uint8_t* score = PAIR ? region : scoreS + wave * kScoreBytes;
     const int roiW = c.roiW, roiH = c.roiH, cw = roiW - 6, ch = roiH - 6;
     // small batches (leaf tables): the x / y path codes of the cell's interior columns and rows are fetched WITH the ROI (lane i: column i and
     // row i) and kept in LDS: read from memory where the emit needs them they were two dependent L2 round trips at the end of every cell
@@ -231,22 +344,24 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
         }
     }
     if (leaf) { codeL[wave][0][lane] = myXc; codeL[wave][1][lane] = myYc; }
-    // zero the score tile (its 1-px apron stands for "outside the ROI interior")
-#pragma unroll
-    for (int i = 0; i < (kScoreBytes + 255) / 256; i++)
-        if (lane * 4 + i * 256 < kScoreBytes) *(unsigned*)(score + lane * 4 + i * 256) = 0u;
-    waveLdsSync();
-    FAST_MID(0);
-
     // "items" of the packed passes: one tile dword (4 pixels) of an interior row; q0..q1 are the dwords that touch it
     const int q0 = (mis + 3) >> 2, q1 = (mis + 2 + cw) >> 2, nq = q1 - q0 + 1;
     const int nItems = nq * ch;
+    constexpr int lo = mis + 3 - 4 * ((mis + 3) >> 2);      // first valid byte of dword q0
+    const int hi = mis + 3 + cw - 4 * q1;                   // valid bytes of dword q1 (1 .. 4)
+    // zero the score tile's apron (it stands for "outside the ROI interior"); the score pass writes the rest.  (Pair form: behind the score
+    // pass, the apron's bytes hold pixel rows until then.)
+    if constexpr (!PAIR) clearScoreApron<PAIR, TS, 2>(score, lane, ch, q0, q1);
+    waveLdsSync();
+    FAST_MID(0);
+
     // ---- pass 1: scores ----
     if (!(ORBX_FAST_SKIP & 1)) {
         // one lane = the four pixels of one tile dword (two packed pairs); 21 dword reads feed 4 scores.  Score row y+1
-        // keeps the tile's column alignment, so the four scores are one dword store; bytes outside the interior
-        // (first / last dword of a row) are written as 0 = "outside the ROI interior".
-        const int lo = mis + 3 - 4 * q0, hi = mis + 3 + cw - 4 * q1;            // first valid byte of dword q0 / valid bytes of q1
+        // keeps the tile's item grid, so the four scores are one store (pair form: the two result registers as they are,
+        // 8 bytes; byte form: packed to a dword); pixels outside the interior (first / last item of a row) are written
+        // as 0 = "outside the ROI interior" (byte form) or zeroed behind the pass (pair form: clearScoreApron, TRIM).
+        static_assert(!PAIR || lo == 0, "the pair form trims the last item of a row only");
         const unsigned maskFirst = 0xFFFFFFFFu << (8 * lo), maskLast = hi >= 4 ? 0xFFFFFFFFu : ~(0xFFFFFFFFu << (8 * hi));
         const int sy = (64 * c.itemRecip) >> 16, sx = 64 - sy * nq;           // 64 / nq, 64 % nq (exact: CellDesc::itemRecip)
         int y = (lane * c.itemRecip) >> 16, qi = lane - y * nq;                  // lane / nq, lane % nq
@@ -254,7 +369,8 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
         // four CONSECUTIVE rows at 12 dwords per row start at banks 0, 12, 24, 4: the fourth collides with the first (every read of the pass
         // 2-way).  Rows 0, 2, 4, 6 start at 0, 24, 16, 8 (and 1, 3, 5, 7 at 12, 4, 28, 20): disjoint.  The order of the items does not matter here.
         if (DW == 12 && nq == 8) y = ((y & 3) << 1) | (y >> 2);
-        auto scoreItem = [&](const uint8_t* base, uint8_t* dst, const unsigned m) {      // base: the item's dword in tile row y (= centre row - 3); dst: in score row y + 1
+        // base: the item's dword in tile row y (= centre row - 3); dst: the item in score row y + 1; mLo, mHi: its mask(s) as storeScores takes them
+        auto scoreItem = [&](const uint8_t* base, uint8_t* dst, const unsigned mLo, const unsigned mHi) {
             unsigned L[7], C[7], R[7];
 #pragma unroll
             for (int d = 0; d < 7; d++) {
@@ -269,34 +385,42 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
             const unsigned sA = pairScore(rA);
             __builtin_amdgcn_sched_barrier(0);
             const unsigned sB = pairScore(rB);
-            *(unsigned*)dst = __builtin_amdgcn_perm(sB, sA, 0x06040200u) & m;
+            storeScores<PAIR>(dst, sA, sB, mLo, mHi);
         };
         if (sx == 0) {
-            // the items of a row divide the wave (8 items: the usual 29..32-px cells; 1, 2, 4, 16): a lane keeps its item column, so its edge mask is
+            // the items of a row divide the wave (8 items: the usual 29..32-px cells; 1, 2, 4, 16): a lane keeps its item column, so its edge masks are
             // fixed and a trip is "sy rows further": two pointer steps and a compare instead of re-deriving (item, row), the masks and the address
             const unsigned m = (qi == 0 ? maskFirst : 0xFFFFFFFFu) & (qi == nq - 1 ? maskLast : 0xFFFFFFFFu);
+            const unsigned mLo = PAIR ? 0xFFFFFFFFu : m, mHi = 0xFFFFFFFFu;
             const uint8_t* base = tile + y * TS + 4 * (q0 + qi);
-            uint8_t* dst = score + (y + 1) * TS + 4 * (q0 + qi);
-            for (; y < ch; y += sy, base += sy * TS, dst += sy * TS) scoreItem(base, dst, m);
+            // (the item's place in score row y + 1 follows from its place in tile row y - one add on a scalar - and is not carried as a register)
+            for (; y < ch; y += sy, base += sy * TS) scoreItem(base, score + RS + (IB / 4) * (base - tile), mLo, mHi);
         } else {
             for (; y < ch;) {
                 unsigned m = qi == 0 ? maskFirst : 0xFFFFFFFFu;
                 m = qi == nq - 1 ? (m & maskLast) : m;
-                scoreItem(tile + y * TS + 4 * (q0 + qi), score + (y + 1) * TS + 4 * (q0 + qi), m);
+                scoreItem(tile + y * TS + 4 * (q0 + qi), score + (y + 1) * RS + IB * (q0 + qi), PAIR ? 0xFFFFFFFFu : m, 0xFFFFFFFFu);
                 qi += sx; y += sy;
                 if (qi >= nq) { qi -= nq; y++; }
             }
         }
     }
+    if constexpr (PAIR) clearScoreApron<PAIR, TS, 2, true>(score, lane, ch, q0, q1, hi);
     waveLdsSync();
     if (ORBX_FAST_SKIP & 2) { if (lane == 0) cellCount[(long long)f * nCells + ci] = 0u; return; }
 
     FAST_MID(1);
-    // ---- pass 2: strict local maxima, four pixels per lane (the score rows keep the tile's dword grid): nine dword
-    //      reads, the 3 x 5 neighbour pairs by v_perm, packed 3-input maxima with minThFAST folded in, so
-    //      "keep" is simply S > max.  Survivors are appended in raster order (lane order, then pixel order inside the
-    //      lane) to a list that reuses the pixel tile (no longer needed) ----
-    unsigned* list = (unsigned*)tile;                   // entry: x | y << 6 | S << 12
+    // ---- pass 2: strict local maxima, four pixels per lane (the score rows keep the tile's item grid): the neighbour
+    //      maximum with minThFAST folded in (nmsNeighbourMax), so "keep" is simply S > max.  Survivors are appended in
+    //      raster order (lane order, then pixel order inside the lane) to a list that reuses the pixel tile (no longer
+    //      needed).
+    //      Banks of the pair form's reads (rows of 24 dwords; a read is served in two groups of 32 lanes = four score rows of 8 items): the 8-byte
+    //      read of A | B has 64 banks and a row's 8 items are 16 consecutive dwords; rows y .. y + 3 start at banks 0, 24, 48, 8 (+ 2 q0), so the
+    //      fourth row shares 8 of its 16 banks with the first: that group takes 2 LDS cycles instead of 1.  The 4-byte reads of P and N have 32
+    //      banks and touch every second dword: rows start at banks 0, 24, 16, 8 and reach over 16 banks each, so every row shares 4 of its 8
+    //      dwords' banks with the next: 2-way as well.  (The byte form: 12 dwords per row, rows at 0, 12, 24, 4: the fourth row's 8 dwords share 4
+    //      banks with the first.)  Raster order fixes which rows a group holds, so unlike pass 1 the rows cannot be re-dealt here. ----
+    unsigned* list = (unsigned*)region;                 // entry: x | y << 6 | S << 12  (pair form: over the score rows the pass has left behind, FastAlias)
     int nMin = 0;
     {
         const unsigned thPair = (unsigned)minTh | ((unsigned)minTh << 16);
@@ -306,22 +430,8 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
         // "negative": only kept pixels are used).  Lanes past the last item (y >= ch) take centre row ch + 1, the zero row below the interior: S = 0
         // keeps nothing, so the pass needs no "active" predicate
         auto nmsTrip = [&](const uint8_t* base, const unsigned xy) {
-            unsigned U[3], M[3], D[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                U[k] = *(const unsigned*)(base + 4 * k - 4);
-                M[k] = *(const unsigned*)(base + TS + 4 * k - 4);
-                D[k] = *(const unsigned*)(base + 2 * TS + 4 * k - 4);
-            }
-            // pairs a..e = bytes (3,4) (4,5) (5,6) (6,7) (7,8) of L|C|R; up/down maxima per pair column, threshold folded in
-            const unsigned Wa = pkmax3(pairAt<3>(U[0], U[1], U[2]), pairAt<3>(D[0], D[1], D[2]), thPair);
-            const unsigned Wb = pkmax3(pairAt<4>(U[0], U[1], U[2]), pairAt<4>(D[0], D[1], D[2]), thPair);
-            const unsigned Wc = pkmax3(pairAt<5>(U[0], U[1], U[2]), pairAt<5>(D[0], D[1], D[2]), thPair);
-            const unsigned Wd = pkmax3(pairAt<6>(U[0], U[1], U[2]), pairAt<6>(D[0], D[1], D[2]), thPair);
-            const unsigned We = pkmax3(pairAt<7>(U[0], U[1], U[2]), pairAt<7>(D[0], D[1], D[2]), thPair);
-            const unsigned Ma = pairAt<3>(M[0], M[1], M[2]), Mc = pairAt<5>(M[0], M[1], M[2]), Me = pairAt<7>(M[0], M[1], M[2]);
-            const unsigned sA = pairAt<4>(M[0], M[1], M[2]), sB = pairAt<6>(M[0], M[1], M[2]);
-            const unsigned mA = pkmax3(pkmax3(Wa, Wb, Wc), Ma, Mc), mB = pkmax3(pkmax3(Wc, Wd, We), Mc, Me);
+            unsigned sA, sB, mA, mB;
+            nmsNeighbourMax<PAIR, TS>(base, thPair, sA, sB, mA, mB);
             unsigned dA, dB;                             // per half: S - max, saturated at 0: nonzero <=> strict maximum above minThFAST
             asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dA) : "v"(sA), "v"(mA));
             asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(dB) : "v"(sB), "v"(mB));
@@ -339,13 +449,13 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
         };
         const int trips = (nItems + 63) >> 6;
         if (sx == 0) {      // a lane keeps its item column (scoreItem has the reason): a trip is sy rows further
-            const uint8_t* base = score + y * TS + 4 * (q0 + qi);
-            const uint8_t* const baseEnd = score + ch * TS + 4 * (q0 + qi);
+            const uint8_t* base = score + y * RS + IB * (q0 + qi);
+            const uint8_t* const baseEnd = score + ch * RS + IB * (q0 + qi);
             unsigned xy = (unsigned)(4 * (q0 + qi) - (mis + 3)) + ((unsigned)y << 6);
-            for (int t = 0; t < trips; t++, base += sy * TS, xy += (unsigned)sy << 6) nmsTrip(base < baseEnd ? base : baseEnd, xy);
+            for (int t = 0; t < trips; t++, base += sy * RS, xy += (unsigned)sy << 6) nmsTrip(base < baseEnd ? base : baseEnd, xy);
         } else {
             for (int t = 0; t < trips; t++) {
-                nmsTrip(score + min(y, ch) * TS + 4 * (q0 + qi), (unsigned)(4 * (q0 + qi) - (mis + 3)) + ((unsigned)y << 6));
+                nmsTrip(score + min(y, ch) * RS + IB * (q0 + qi), (unsigned)(4 * (q0 + qi) - (mis + 3)) + ((unsigned)y << 6));
                 qi += sx; y += sy;
                 if (qi >= nq) { qi -= nq; y++; }
             }
@@ -353,6 +463,7 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
     }
     waveLdsSync();
     // the reference retries the cell at minThFAST only when the first call returned nothing (:835-838)
+    // (counting them in the NMS trips instead - one compare and one scalar count per pixel pair - was timed in round 32: no faster)
     int nIni = 0;
     for (int i0 = 0; i0 < nMin; i0 += 64)
         nIni += __popcll(__ballot(i0 + lane < nMin && (int)(list[i0 + lane] >> 12) > iniTh));
@@ -376,8 +487,9 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
     // touches only a small rectangle of leaf cells (x / y path codes are monotone), so the wave first collects them in LDS (the score tile
     // is dead by now) and sends ONE pair of L2 atomics per touched leaf instead of one per key (100 k keys per frame otherwise: the L2
     // atomics on a few hundred hot lines cost more than the sweep they replace).
-    constexpr int kLeafCap = kScoreBytes / 8;
-    unsigned *tHist = (unsigned*)score, *tBest = tHist + kLeafCap;
+    constexpr int kLeafCap = TS * (ROWS - 3) / 8;      // (the same in both tile forms)
+    static_assert(!PAIR || kLeafCap == A::kLeafCap, "FastAlias states the leaf tables");
+    unsigned *tHist = (unsigned*)(PAIR ? region + A::kLeafOff : score), *tBest = tHist + kLeafCap;
     int xc0 = 0, yc0 = 0, nxl = 1, nLeafLocal = 0;
     const uint8_t *xcL = codeL[wave][0], *ycL = codeL[wave][1];      // code of interior column x / row y of the cell (pixel shift + 3 + x, clamped to the rectangle)
     if (leaf) {

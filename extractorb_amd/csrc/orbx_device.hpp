@@ -100,6 +100,55 @@ constexpr int kFastTileShift = 1;      // tile byte of ROI pixel 0 (k_fast.hip: 
 inline constexpr int fastItemsPerRow(int cw) { return ((kFastTileShift + 2 + cw) >> 2) - ((kFastTileShift + 3) >> 2) + 1; }
 static_assert(sizeof(CellDesc) == 48, "CellDesc layout");
 
+// ---- k_fast's LDS of one cell-wave where the score tile has the pair form (k_fast_body.hpp: ScoreTile) and SHARES its bytes with the pixel
+//      tile.  A separate pair tile would make a <48,45> workgroup 25 296 B (six per CU); measured, that costs the step 2 % (profiles/
+//      r32_fast_pair_scores.md).  Shared, the wave's region is kWaveBytes = 4176 B: the workgroup's 17 232 B of the byte form.
+//        score row r (r = 0 .. ch + 2)   at  kScoreStride * r            (a u16 per pixel, an item = 8 bytes at 8 * q)
+//        pixel row r (r = 0 .. roiH - 1) at  kPixelOff + TS * r          (an item's dword at 4 * q)
+//        survivor list                   at  0                           (grows while the NMS pass walks the score rows from the top)
+//        leaf tables (hist, best)        at  kPixelOff                   (after the NMS pass: the pixel tile and the score rows are dead)
+//      What makes it legal: the lanes of a wave run one instruction together and a wave's LDS operations execute in order, so in every trip of a
+//      pass ALL of the trip's reads are done before its first store.  A store therefore only has to spare what LATER trips read:
+//        score pass: trip t ends in item row R (64 consecutive items in raster order, in either way of dealing the lanes) and writes score rows up
+//          to R + 1; the trips after it read pixel rows from R' = the row of item 64 (t + 1) on (R' = R where the row is split, else R + 1);
+//        NMS pass: after trip t the list holds at most ceil(cw / 2) * ceil((R + 1) / 2) entries (no two survivors are 8-adjacent, and only rows
+//          0 .. R have been visited); the trips after it read score rows from R' on, the first byte being the dword left of item q0.
+//      The apron of the score tile (clearScoreApron) overlaps live pixel rows too, so it is zeroed AFTER the score pass.
+//      ok() replays the trips for one cell; okAll() is asserted below for every (cw, ch) the tile accepts, and tests/test_fast_pair_alias.py
+//      replays the same byte by byte from the passes' own address arithmetic.
+template <int TS, int ROWS>
+struct FastAlias {
+    static constexpr int kScoreStride = 2 * TS, kScoreItem = 8;
+    static constexpr int kPixelOff = TS * (ROWS - 3);               // = TS * (chMax - 1) + 4 * TS: the worst case of the score pass below
+    static constexpr int kWaveBytes = kPixelOff + TS * ROWS;
+    static constexpr int kLeafCap = TS * (ROWS - 3) / 8, kLeafOff = kPixelOff;
+    static constexpr int kMaxInterior = ROWS - 6;                   // cw, ch <= this (ROIs up to ROWS x ROWS)
+    static constexpr bool ok(int cw, int ch) {
+        const int q0 = (kFastTileShift + 3) >> 2, q1 = (kFastTileShift + 2 + cw) >> 2, nq = q1 - q0 + 1, nItems = nq * ch;
+        if (kScoreStride * (ch + 3) > kWaveBytes || kScoreItem * (q1 + 1) + 4 > kScoreStride) return false;      // the score rows and their right apron fit
+        const int listMax = 4 * ((cw + 1) / 2) * ((ch + 1) / 2);
+        if (listMax > kLeafOff || kLeafOff + 8 * kLeafCap > kWaveBytes) return false;                           // the emit reads the list beside the leaf tables
+        for (int t = 0; 64 * (t + 1) < nItems; t++) {                  // every trip with a trip after it
+            const int R = (64 * t + 63) / nq, Rnext = 64 * (t + 1) / nq;
+            const int written = kScoreStride * (R + 1) + kScoreItem * (q1 + 1);            // end of the last score byte the score pass has stored
+            const int livePixels = kPixelOff + TS * Rnext + 4 * (q0 - 1);                  // first pixel byte a later trip reads
+            if (written > livePixels) return false;
+            const int listEnd = 4 * ((cw + 1) / 2) * ((R + 2) / 2);                        // end of the list after the NMS pass's trip t
+            const int liveScores = kScoreStride * Rnext + kScoreItem * q0 - 4;             // first score byte a later trip reads
+            if (listEnd > liveScores) return false;
+        }
+        return true;
+    }
+    static constexpr bool okAll() {
+        for (int cw = 1; cw <= kMaxInterior; cw++)
+            for (int ch = 1; ch <= kMaxInterior; ch++)
+                if (!ok(cw, ch)) return false;
+        return true;
+    }
+};
+static_assert(FastAlias<48, 45>::okAll(), "k_fast<48,45>: a score row or a list entry would overwrite bytes a later trip reads");
+static_assert(FastAlias<48, 45>::kWaveBytes == 4176, "k_fast<48,45>: the workgroup's LDS stays what the byte form needed");
+
 // ---- quad-tree dense phase: leaf grid of a root (k_octree.hip) -------------------------------------------------------------------
 // DivideNode's boxes depend only on the root box, and its x and y decisions are independent, so a key's quadrant path of length
 // kOctDepth below its root is two table look-ups.  Shared by the kernels (k_octree builds the tables in LDS; k_fast reads the host-built
