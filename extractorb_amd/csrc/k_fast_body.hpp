@@ -420,15 +420,21 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
     //      banks and touch every second dword: rows start at banks 0, 24, 16, 8 and reach over 16 banks each, so every row shares 4 of its 8
     //      dwords' banks with the next: 2-way as well.  (The byte form: 12 dwords per row, rows at 0, 12, 24, 4: the fourth row's 8 dwords share 4
     //      banks with the first.)  Raster order fixes which rows a group holds, so unlike pass 1 the rows cannot be re-dealt here. ----
-    unsigned* list = (unsigned*)region;                 // entry: x | y << 6 | S << 12  (pair form: over the score rows the pass has left behind, FastAlias)
+    //      The list (pair form: over the score rows the pass has left behind, FastAlias).  An entry is one dword per kept PIXEL PAIR: the pair's
+    //      score register as the pass holds it (two u16 halves of 0 .. 255) with the coordinates in the bytes the scores leave free:
+    //          bits 0-7 S of the pair's first pixel | 8-13 x of the pair's first pixel (4 * item + 0 or 2) | 16-23 S of its second pixel | 24-29 y
+    //      A trip then spends one v_or per kept pair on the entry; which pixel of the pair was kept, its x and its S are taken from the word
+    //      by the one dense pass over the list below (pass 3).  0 = no entry. ----
+    static_assert(lo == 0, "an item's first pixel is x = 4 * item: bits 0, 1 of an entry's x field are the pair and the pixel of the pair");
+    unsigned* list = (unsigned*)region;
     int nMin = 0;
     {
         const unsigned thPair = (unsigned)minTh | ((unsigned)minTh << 16);
         const int sy = (64 * c.itemRecip) >> 16, sx = 64 - sy * nq;
         int y = (lane * c.itemRecip) >> 16, qi = lane - y * nq;
-        // one trip of 64 items: base = the item's dword in score row y (the row above the centre row), xy = x | y << 6 of its pixel 0 (x may be
-        // "negative": only kept pixels are used).  Lanes past the last item (y >= ch) take centre row ch + 1, the zero row below the interior: S = 0
-        // keeps nothing, so the pass needs no "active" predicate
+        // one trip of 64 items: base = the item's dword in score row y (the row above the centre row), xy = x << 8 | y << 24 of its pixel 0 (x <= 60,
+        // y <= 62 where a pixel can be kept; beyond, y may run past its field: only kept pairs are stored).  Lanes past the last item (y >= ch) take
+        // centre row ch + 1, the zero row below the interior: S = 0 keeps nothing, so the pass needs no "active" predicate
         auto nmsTrip = [&](const uint8_t* base, const unsigned xy) {
             unsigned sA, sB, mA, mB;
             nmsNeighbourMax<PAIR, TS>(base, thPair, sA, sB, mA, mB);
@@ -442,8 +448,11 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
                 int at = nMin;                           // + kept pixels of the lower lanes: one v_mbcnt pair per ballot
                 at = __builtin_amdgcn_mbcnt_hi((unsigned)(bA >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bA, at));
                 at = __builtin_amdgcn_mbcnt_hi((unsigned)(bB >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bB, at));
-                if (fA) { const bool hi = dA > 0xFFFFu; list[at++] = (xy + (hi ? 1u : 0u)) | ((hi ? sA >> 16 : sA & 0xFFFFu) << 12); }
-                if (fB) { const bool hi = dB > 0xFFFFu; list[at] = (xy + (hi ? 3u : 2u)) | ((hi ? sB >> 16 : sB & 0xFFFFu) << 12); }
+                // a lane's first entry (A's, else B's) under one mask; a second one only where both pairs keep a pixel, which most trips skip
+                // (two predicated stores, one per pair, were 2 vector instructions and one mask save / restore more per trip)
+                const unsigned wB = sB | xy | 0x200u;
+                if (fA || fB) list[at] = fA ? (sA | xy) : wB;
+                if (fA && fB) list[at + 1] = wB;
                 nMin += __popcll(bA) + __popcll(bB);
             }
         };
@@ -451,36 +460,22 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
         if (sx == 0) {      // a lane keeps its item column (scoreItem has the reason): a trip is sy rows further
             const uint8_t* base = score + y * RS + IB * (q0 + qi);
             const uint8_t* const baseEnd = score + ch * RS + IB * (q0 + qi);
-            unsigned xy = (unsigned)(4 * (q0 + qi) - (mis + 3)) + ((unsigned)y << 6);
-            for (int t = 0; t < trips; t++, base += sy * RS, xy += (unsigned)sy << 6) nmsTrip(base < baseEnd ? base : baseEnd, xy);
+            unsigned xy = ((unsigned)qi << 10) | ((unsigned)y << 24);
+            for (int t = 0; t < trips; t++, base += sy * RS, xy += (unsigned)sy << 24) nmsTrip(base < baseEnd ? base : baseEnd, xy);
         } else {
             for (int t = 0; t < trips; t++) {
-                nmsTrip(score + min(y, ch) * RS + IB * (q0 + qi), (unsigned)(4 * (q0 + qi) - (mis + 3)) + ((unsigned)y << 6));
+                nmsTrip(score + min(y, ch) * RS + IB * (q0 + qi), ((unsigned)qi << 10) | ((unsigned)y << 24));
                 qi += sx; y += sy;
                 if (qi >= nq) { qi -= nq; y++; }
             }
         }
     }
     waveLdsSync();
-    // the reference retries the cell at minThFAST only when the first call returned nothing (:835-838)
-    // (counting them in the NMS trips instead - one compare and one scalar count per pixel pair - was timed in round 32: no faster)
-    int nIni = 0;
-    for (int i0 = 0; i0 < nMin; i0 += 64)
-        nIni += __popcll(__ballot(i0 + lane < nMin && (int)(list[i0 + lane] >> 12) > iniTh));
-    const bool useIni = nIni > 0;
-    const int total = useIni ? nIni : nMin;
     // every cell owns a fixed, exactly sized segment of the level's candidate arena (no two 8-adjacent NMS survivors
     // => at most ceil(cw/2)*ceil(ch/2) of them), so the emit needs no atomic; the quad-tree kernel compacts the
     // segments in cell order, which is the reference's vToDistributeKeys order (cell row, cell column, y, x)
-    if (lane == 0) cellCount[(long long)f * nCells + ci] = (unsigned)total;
-    FAST_CLOCK_END;
-    FAST_SPAN(1);
-    FAST_MID(2);
-    if (total == 0) return;
-    unsigned base = 0;
     typename CandFmt<BIG>::T* outPos = candSeg + g.candOff + (long long)f * g.candCap + c.segOff;
     const unsigned segCap = (unsigned)(((cw + 1) >> 1) * ((ch + 1) >> 1));
-    const int th = useIni ? iniTh : minTh;
     // Small batches: the quad-tree's first sweep is done here, by 800 waves instead of one workgroup per level (k_octree_body.inc,
     // preCounted): every kept key adds 1 to its leaf cell of its root's 32 x 32 grid and offers (response, then smallest segment slot = first
     // in the reference's vector) as the leaf's best key.  Both operations commute, so the order of the cells' waves does not matter.  A cell
@@ -492,7 +487,7 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
     unsigned *tHist = (unsigned*)(PAIR ? region + A::kLeafOff : score), *tBest = tHist + kLeafCap;
     int xc0 = 0, yc0 = 0, nxl = 1, nLeafLocal = 0;
     const uint8_t *xcL = codeL[wave][0], *ycL = codeL[wave][1];      // code of interior column x / row y of the cell (pixel shift + 3 + x, clamped to the rectangle)
-    if (leaf) {
+    if (leaf && nMin > 0) {      // (ahead of the first trip over the list; a cell without entries has no leaf cell to report)
         xc0 = xcL[0]; yc0 = ycL[0];
         nxl = (int)xcL[cw - 1] - xc0 + 1;
         const int nyl = (int)ycL[ch - 1] - yc0 + 1;
@@ -500,36 +495,52 @@ __device__ __forceinline__ void fastCell(const CellDesc* __restrict__ cells, int
         for (int e = lane; e < nLeafLocal; e += 64) { tHist[e] = 0u; tBest[e] = 0u; }
         waveLdsSync();
     }
-    for (int i0 = 0; i0 < nMin; i0 += 64) {
-        const unsigned e = i0 + lane < nMin ? list[i0 + lane] : 0u;
-        const int s = (int)(e >> 12), x = (int)(e & 63), y = (int)((e >> 6) & 63);
-        const bool keep = s > th;                       // entries hold S > minTh; 0 marks "past the end"
-        const unsigned long long m = __ballot(keep);
-        if (keep) {
-            const unsigned at = base + __popcll(m & ((1ull << lane) - 1));
-            if (at < segCap) {
-                const unsigned kx = (unsigned)(c.shiftX + x + 3), ky = (unsigned)(c.shiftY + y + 3);
-                const typename CandFmt<BIG>::T w = CandFmt<BIG>::make(kx, ky, (unsigned)(s - 1));   // response = S - 1
-                outPos[at] = w;
-                if (leaf) {
-                    const int xc = xcL[x], yc = ycL[y];
-                    const unsigned val = CandFmt<BIG>::respKey(w) | (0xffffffu - ((unsigned)c.segOff + at));
-                    if (nLeafLocal) {
-                        const int li = (yc - yc0) * nxl + (xc - xc0);
-                        // (LDS by type: with the tables reached through the body's pointer arguments the compiler merged this pair with the
-                        // global pair of the other branch into ONE atomic on a generic pointer - a flat_atomic, docs/history/DESIGN_rounds_1-5.md §4i's construct)
-                        ldsAtomicAdd(&tHist[li], 1u);
-                        ldsAtomicMax(&tBest[li], val);
-                    } else {
-                        const unsigned cellOfRoot = leafTableEntry(lt, f, c.level, xc, yc);
-                        atomicAdd(lt.hist + cellOfRoot, 1);
-                        atomicMax(lt.best + cellOfRoot, val);
+    // ---- pass 3: one dense pass over the list decodes, counts and emits.  It runs at iniThFAST; the reference retries the cell at minThFAST
+    //      only when the first call returned nothing (:835-838), and a trip that kept nothing has stored nothing and touched no leaf table,
+    //      so the retry is a second trip of the same loop.  base = the keys kept by the last trip made = the cell's count.
+    //      Decode: a kept pixel is a strict maximum over its eight neighbours and the other pixel of its pair is one of them, so the kept
+    //      pixel is the strictly larger half of the entry: S = max(halves), x = the pair's x + (second half > first half). ----
+    unsigned base = 0;
+#pragma nounroll
+    for (int th = iniTh; nMin > 0; th = minTh) {
+        for (int i0 = 0; i0 < nMin; i0 += 64) {
+            const unsigned e = i0 + lane < nMin ? list[i0 + lane] : 0u;      // 0 marks "past the end": S = 0
+            const int s0 = (int)(e & 0xFFu), s1 = (int)((e >> 16) & 0xFFu);
+            const int s = max(s0, s1), x = (int)((e >> 8) & 63u) + (s1 > s0 ? 1 : 0), y = (int)((e >> 24) & 63u);
+            const bool keep = s > th;                       // entries hold S > minTh
+            const unsigned long long m = __ballot(keep);
+            if (keep) {
+                const unsigned at = base + __popcll(m & ((1ull << lane) - 1));
+                if (at < segCap) {
+                    const unsigned kx = (unsigned)(c.shiftX + x + 3), ky = (unsigned)(c.shiftY + y + 3);
+                    const typename CandFmt<BIG>::T w = CandFmt<BIG>::make(kx, ky, (unsigned)(s - 1));   // response = S - 1
+                    outPos[at] = w;
+                    if (leaf) {
+                        const int xc = xcL[x], yc = ycL[y];
+                        const unsigned val = CandFmt<BIG>::respKey(w) | (0xffffffu - ((unsigned)c.segOff + at));
+                        if (nLeafLocal) {
+                            const int li = (yc - yc0) * nxl + (xc - xc0);
+                            // (LDS by type: with the tables reached through the body's pointer arguments the compiler merged this pair with the
+                            // global pair of the other branch into ONE atomic on a generic pointer - a flat_atomic, docs/history/DESIGN_rounds_1-5.md §4i's construct)
+                            ldsAtomicAdd(&tHist[li], 1u);
+                            ldsAtomicMax(&tBest[li], val);
+                        } else {
+                            const unsigned cellOfRoot = leafTableEntry(lt, f, c.level, xc, yc);
+                            atomicAdd(lt.hist + cellOfRoot, 1);
+                            atomicMax(lt.best + cellOfRoot, val);
+                        }
                     }
                 }
             }
+            base += __popcll(m);
         }
-        base += __popcll(m);
+        if (base != 0u || th == minTh) break;
     }
+    if (lane == 0) cellCount[(long long)f * nCells + ci] = base;
+    FAST_CLOCK_END;
+    FAST_SPAN(1);
+    FAST_MID(2);
+    if (base == 0u) return;
     if (nLeafLocal) {
         waveLdsSync();
         for (int e = lane; e < nLeafLocal; e += 64) {
