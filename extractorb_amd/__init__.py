@@ -14,7 +14,9 @@ from .orbextractor import (KEYPOINT_DTYPE, ORBextractor, OrbxError, build_librar
                            TRACK_RECORD_DTYPE, FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION, FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH,
                            FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR, FRUSTUM_REQUEST, TWO_VIEW_RESULT_DTYPE,
                            TWO_VIEW_STATUS, SIM3_PROBLEM_DTYPE, SIM3_RESULT_DTYPE, SIM3_STATUS, POSE_PROBLEM_DTYPE, POSE_RESULT_DTYPE,
-                           POSE_OPTIMIZATION_STATUS, PLACE_RESULT_DTYPE, PLACE_N_BEST, PLACE_RELOCALIZATION, PLACE_STATUS)
+                           POSE_OPTIMIZATION_STATUS, PLACE_RESULT_DTYPE, PLACE_N_BEST, PLACE_RELOCALIZATION, PLACE_STATUS,
+                           COVIS_RESULT_DTYPE, REDUNDANCY_RESULT_DTYPE, COVIS_UPDATE_CONNECTIONS, COVIS_LOCAL_KEYFRAMES, COVIS_STATUS,
+                           REDUNDANCY_STATUS)
 
 __all__ = ["KEYPOINT_DTYPE", "ORBextractor", "OrbxError", "build_library", "library_path", "load_library",
            "compute_tables", "describe_tables", "describe_levels", "DESCRIBE_LEVEL_FIELDS", "compute_level_sizes", "compute_cell_grid", "header_symbols", "camera", "camera_kb8", "compute_image_bounds", "pinned_empty", "pinned_free", "source_hash", "Vocabulary",
@@ -22,5 +24,6 @@ __all__ = ["KEYPOINT_DTYPE", "ORBextractor", "OrbxError", "build_library", "libr
            "PROJ_QUERY_DTYPE", "TRACK_RECORD_DTYPE", "FRUSTUM_LOCAL_MAP", "FRUSTUM_RELOCALIZATION", "FRUSTUM_FLAG", "FRUSTUM_NEG_DEPTH",
            "FRUSTUM_NOT_IN_IMAGE", "FRUSTUM_DISTANCE", "FRUSTUM_VIEW_COS", "FRUSTUM_FAR", "FRUSTUM_REQUEST", "TWO_VIEW_RESULT_DTYPE", "TWO_VIEW_STATUS",
            "SIM3_PROBLEM_DTYPE", "SIM3_RESULT_DTYPE", "SIM3_STATUS", "POSE_PROBLEM_DTYPE", "POSE_RESULT_DTYPE",
-           "POSE_OPTIMIZATION_STATUS", "PLACE_RESULT_DTYPE", "PLACE_N_BEST", "PLACE_RELOCALIZATION", "PLACE_STATUS"]
+           "POSE_OPTIMIZATION_STATUS", "PLACE_RESULT_DTYPE", "PLACE_N_BEST", "PLACE_RELOCALIZATION", "PLACE_STATUS",
+           "COVIS_RESULT_DTYPE", "REDUNDANCY_RESULT_DTYPE", "COVIS_UPDATE_CONNECTIONS", "COVIS_LOCAL_KEYFRAMES", "COVIS_STATUS", "REDUNDANCY_STATUS"]
 __version__ = "0.1.0"

@@ -23,7 +23,8 @@ void freeAll(orbx_handle* h) {
                    h->d_octArena, h->d_leafHist, h->d_leafBest, h->d_leafCode, h->d_bowWord, h->d_bowNode, h->d_bowWeight, h->d_rowOff, h->d_sadDist,
                    h->d_nMatched, h->d_rowList, h->d_uRight, h->d_depth, h->d_clock, h->d_sim3Rec, h->d_frustumCounts, h->twoViewWork.prep, h->twoViewWork.first,
                    h->twoViewWork.second, h->twoViewWork.score, h->twoViewWork.mats, h->twoViewWork.inl, h->twoViewWork.counted, h->twoViewWork.cosv, h->sim3SolveWork.prep,
-                   h->sim3SolveWork.idx1, h->sim3SolveWork.pts, h->sim3SolveWork.counts, h->sim3SolveWork.its, h->d_placeWords, h->d_placeFirst, h->d_placeScore};
+                   h->sim3SolveWork.idx1, h->sim3SolveWork.pts, h->sim3SolveWork.counts, h->sim3SolveWork.its, h->d_placeWords, h->d_placeFirst, h->d_placeScore, h->d_covisRank,
+                   h->d_covisByRank, h->d_covisDup};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (h->evFork) (void)hipEventDestroy(h->evFork);
     if (h->evJoin) (void)hipEventDestroy(h->evJoin);

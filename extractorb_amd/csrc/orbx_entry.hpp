@@ -59,6 +59,40 @@ inline bool placeUnsupported(int scoring, int nDb, int qCapacity) { return scori
 static_assert(prQueryLdsBytes(kPrMaxDb) <= kLdsBudget && prQueryLdsBytes(kPrMaxDb + 1) > kLdsBudget, "kPrMaxDb is the LDS bound on n_db");
 static_assert(prPairLdsBytes(kPrMaxQueryWords) <= kLdsBudget && prPairLdsBytes(kPrMaxQueryWords + 1) > kLdsBudget, "kPrMaxQueryWords is the LDS bound on q_capacity");
 
+// orbx_covisibility_device: k_covis_vote holds 8 bytes of sort key per list slot - a power of two of slots, every frame may be listed - and a
+// counter word per frame: 12 * 8192 + 48 bytes for 8192 frames; 8193 frames need a sort of 16384 slots (131072 + 32772 + 48 bytes), which
+// does not fit 160 KB - 512.  conn_capacity takes no LDS: the lists are written from the counters and the sorted keys
+inline bool covisFits(int nFrames) { return nFrames <= kCvMaxFrames && fitsLds(cvVoteLdsBytes(nFrames)); }
+// ... what it refuses as ORBX_ERR_BAD_ARGUMENT, the handle apart.  UPDATE_CONNECTIONS reads the three arrays of its self and map tests and
+// writes the ordered block; LOCAL_KEYFRAMES reads and writes none of them.  The list blocks may be NULL when conn_capacity == 0
+inline bool covisBadArgument(int mode, int nPoints, const void* obsOff, const void* obs, const void* mpFlags, int nFrames, const void* kfFlags,
+                             const void* kfMap, const void* kfKey, int nSubjects, const void* subjectMp, const void* subjectN, int capacity,
+                             const void* subjectKf, const void* subjectMap, int connCapacity, const void* counterKf, const void* counterW,
+                             const void* orderedKf, const void* orderedW, const void* result) {
+    const bool update = mode == ORBX_COVIS_UPDATE_CONNECTIONS;
+    return (mode != ORBX_COVIS_UPDATE_CONNECTIONS && mode != ORBX_COVIS_LOCAL_KEYFRAMES) || nPoints < 0 || nFrames < 1 || nSubjects < 1 ||
+           nSubjects > 65535 || capacity < 1 || connCapacity < 0 || !obsOff || !obs || !mpFlags || !kfFlags || !kfKey || !subjectMp || !subjectN ||
+           !result || (update && (!kfMap || !subjectKf || !subjectMap)) || (connCapacity > 0 && (!counterKf || !counterW)) ||
+           (update && connCapacity > 0 && (!orderedKf || !orderedW)) || (long long)nSubjects * capacity > 0x7fffffffLL ||
+           (long long)nSubjects * connCapacity > 0x7fffffffLL;
+}
+inline bool covisUnsupported(int nFrames) { return !covisFits(nFrames); }
+static_assert(cvVoteLdsBytes(kCvMaxFrames) <= kLdsBudget && cvVoteLdsBytes(kCvMaxFrames + 1) > kLdsBudget, "kCvMaxFrames is the LDS bound on n_frames");
+
+// orbx_keyframe_redundancy_device: a state byte per slot (rounded up to a dword) and 48 bytes of scratch words: capacity <= 163280
+inline bool redundancyFits(int capacity) { return capacity <= kRdMaxCapacity && fitsLds(rdLdsBytes(capacity)); }
+// ... what it refuses as ORBX_ERR_BAD_ARGUMENT.  d_mp_nobs and d_slot_state are optional; d_depth / d_th_depth are read when monocular == 0.
+// A NaN redundant_th is refused: no keyframe could be redundant
+inline bool redundancyBadArgument(int nPoints, const void* obsOff, const void* obs, const void* mpFlags, int nFrames, const void* kfFlags,
+                                  const void* kpsUn, const void* nOut, const void* depth, const void* thDepth, int nSubjects, const void* subjectMp,
+                                  const void* subjectN, int capacity, const void* subjectKf, int monocular, float redundantTh, const void* result) {
+    return nPoints < 0 || nFrames < 1 || nSubjects < 1 || nSubjects > 65535 || capacity < 1 || !obsOff || !obs || !mpFlags || !kfFlags || !kpsUn ||
+           !nOut || !subjectMp || !subjectN || !subjectKf || !result || (!monocular && (!depth || !thDepth)) || redundantTh != redundantTh ||
+           (long long)nSubjects * capacity > 0x7fffffffLL;
+}
+inline bool redundancyUnsupported(int capacity) { return !redundancyFits(capacity); }
+static_assert(rdLdsBytes(kRdMaxCapacity) <= kLdsBudget && rdLdsBytes(kRdMaxCapacity + 1) > kLdsBudget, "kRdMaxCapacity is the LDS bound on capacity");
+
 // Sim3Solver::SetRansacParameters' nIterations for N correspondences, before max(1, min(., maxIterations)) (reference src/Sim3Solver.cc:
 // 137-147): epsilon is a FLOAT, pow / log / ceil run in double, minInliers == N gives 1.  The reference assigns the double to an int: a value
 // outside the int range (epsilon^3 below 2^-53 gives log(1) = 0 and an infinite quotient) converts as its x86-64 build does, to INT_MIN.

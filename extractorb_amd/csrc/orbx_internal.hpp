@@ -51,6 +51,8 @@ void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const i
 void launchSim3Solve(hipStream_t, const void*, const float*, const float*, const int*, const int*, const int*, const Sim3SolveParams&, const SsWork&, void*, uint8_t*, int, int);
 void launchPoseOptimization(hipStream_t, const void*, const Keypoint*, const int*, const float*, const int*, const float*, const PoseOptParams&, float*, uint8_t*, void*, int);
 void launchPlaceRecognition(hipStream_t, const PlaceArrays&, const PlaceParams&);
+void launchCovisibility(hipStream_t, const CovisArrays&, const CovisParams&);
+void launchKeyFrameRedundancy(hipStream_t, const CovisArrays&, const CovisParams&);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
 void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
@@ -248,6 +250,9 @@ struct orbx_handle {
     int* d_placeWords = nullptr;
     uint32_t* d_placeFirst = nullptr;
     float* d_placeScore = nullptr;
+    // the covisibility vote's workspace (allocated on first use): frame -> rank of its key, rank -> frame, and a word per 256 frames "two keys are equal"
+    size_t covisFrames = 0;
+    int *d_covisRank = nullptr, *d_covisByRank = nullptr, *d_covisDup = nullptr;
     // stereo matching (allocated on first use)
     struct StereoShape { int pairs = 0, cap = 0, rows = 0; } stereo;      // what the six buffers below are sized for
     int *d_rowOff = nullptr, *d_sadDist = nullptr, *d_nMatched = nullptr;

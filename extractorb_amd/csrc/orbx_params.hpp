@@ -234,6 +234,33 @@ constexpr int prPairRows(int nDb, int nQueries) {
 constexpr int kPrMaxDb = 8192;                            // the largest n_db whose lists fit the LDS budget (orbx_entry.hpp: placeFits)
 constexpr int kPrMaxQueryWords = 13610;                   // the largest q_capacity whose staged query does
 
+struct CovisParams {             // k_covisibility.hip / k_covisibility.hpp: both entries
+    int mode, nPoints, nFrames;                          // mode: orbx_covis_mode (the vote); MapPoints of the CSR; frames of the tables
+    int nSubjects, capacity;                             // slots of a subject's row of d_subject_mp (and keypoints of a frame: redundancy)
+    int th, connCapacity;                                // the vote: th of KeyFrame::UpdateConnections (15); entries of a subject's list blocks
+    int monocular, thObs;                                // redundancy: mbMonocular; thObs (3)
+    float redundantTh;                                   // redundancy: redundant_th (0.9f / 0.5f)
+};
+struct CovisArrays {             // the arrays of orbx_covisibility_device and orbx_keyframe_redundancy_device, and the handle's workspace
+    const int* obsOff; const int* obs; const uint8_t* mpFlags; const int* mpNobs;
+    const uint8_t* kfFlags; const int* kfMap; const uint64_t* kfKey;
+    const Keypoint* kpsUn; const int* nOut; const float* depth; const float* thDepth;
+    const int* subjectMp; const int* subjectN; const int* subjectKf; const int* subjectMap;
+    int* counterKf; int* counterW; int* orderedKf; int* orderedW; void* result; uint8_t* slotState;
+    int* wsRank; int* wsByRank; int* wsDup;              // frame -> rank of its key, rank -> frame, a word per kCvRankBlock frames: two keys equal
+};
+
+constexpr int kCvScratchInts = 12;
+constexpr int kCvRankBlock = 4;                           // frames per workgroup of k_covis_rank (a wave each), and per word of wsDup
+constexpr int cvRankBlocks(int nFrames) { return (nFrames + kCvRankBlock - 1) / kCvRankBlock; }
+// LDS of the two per-subject kernels.  k_covis_vote: 8 bytes of sort key per list slot (a power of two of slots: every frame may be listed),
+// a counter word per frame, the scratch words.  k_keyframe_redundancy: a state byte per slot (held back until every index of the subject
+// has been checked), the scratch words
+constexpr size_t cvVoteLdsBytes(int nFrames) { return (size_t)8 * (size_t)prPow2(nFrames) + (size_t)4 * (size_t)nFrames + 4 * kCvScratchInts; }
+constexpr size_t rdLdsBytes(int capacity) { return (((size_t)capacity + 3) & ~(size_t)3) + 4 * kCvScratchInts; }
+constexpr int kCvMaxFrames = 8192;                        // the largest n_frames whose lists fit the LDS budget (orbx_entry.hpp: covisFits)
+constexpr int kRdMaxCapacity = 163280;                    // the largest capacity whose state bytes do (redundancyFits)
+
 struct Sim3SearchParams {        // k_project_sim3.hip
     float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv;
     float scale[kMaxLevels];       // mvScaleFactors of the handle

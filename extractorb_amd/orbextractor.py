@@ -53,6 +53,13 @@ PLACE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_sharing", "<i4"), ("max_co
 assert PLACE_RESULT_DTYPE.itemsize == 32
 PLACE_N_BEST, PLACE_RELOCALIZATION = 0, 1
 PLACE_STATUS = ("OK", "NO_SHARING", "NONE_SCORED", "EMPTY_DATABASE", "EMPTY_QUERY", "BAD_KEYFRAME", "TRUNCATED")
+# == orbx_covis_result / orbx_redundancy_result / enum orbx_covis_mode / orbx_covis_status / orbx_redundancy_status
+COVIS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_counter", "<i4"), ("n_ordered", "<i4"), ("nmax", "<i4"), ("kf_max", "<i4")])
+REDUNDANCY_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_mps", "<i4"), ("n_redundant", "<i4"), ("redundant", "<i4")])
+assert COVIS_RESULT_DTYPE.itemsize == 20 and REDUNDANCY_RESULT_DTYPE.itemsize == 16
+COVIS_UPDATE_CONNECTIONS, COVIS_LOCAL_KEYFRAMES = 0, 1
+COVIS_STATUS = ("OK", "EMPTY", "TRUNCATED", "BAD_INDEX", "DUPLICATE_KEY")
+REDUNDANCY_STATUS = ("OK", "SKIPPED", "BAD_INDEX")
 FRUSTUM_LOCAL_MAP, FRUSTUM_RELOCALIZATION = 0, 1      # orbx_frustum_mode
 (FRUSTUM_FLAG, FRUSTUM_NEG_DEPTH, FRUSTUM_NOT_IN_IMAGE, FRUSTUM_DISTANCE, FRUSTUM_VIEW_COS, FRUSTUM_FAR,
  FRUSTUM_REQUEST) = range(7)                           # orbx_frustum_exit
@@ -252,6 +259,12 @@ def load_library():
         L.orbx_detect_candidates_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp,
                                                     C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
         L.orbx_debug_place_recognition_launches.argtypes = [C.c_int]
+    if hasattr(L, "orbx_covisibility_device"):           # (likewise)
+        L.orbx_covisibility_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int,
+                                               C.c_int, vp, vp, vp, vp, vp]
+        L.orbx_keyframe_redundancy_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int,
+                                                      C.c_int, C.c_float, vp, vp]
+        L.orbx_debug_covisibility_launches.argtypes = [C.c_int]
     L.orbx_search_by_projection_sim3_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp,
                                                         vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, vp,
                                                         vp, vp, vp, vp, vp]
@@ -674,6 +687,36 @@ class ORBextractor:
     def debug_place_recognition_launches(self, which):
         """launches so far in this process of k_place_pairs (which = 0) / k_place_query (which = 1): the entry has one launch form"""
         return self._L.orbx_debug_place_recognition_launches(which)
+
+    def covisibility_device(self, mode, n_points, d_obs_off, d_obs, d_mp_flags, n_frames, d_kf_flags, d_kf_key, n_subjects, d_subject_mp,
+                            d_subject_n, capacity, conn_capacity, d_counter_kf, d_counter_w, d_result, d_kf_map_id=None, d_subject_kf=None,
+                            d_subject_map_id=None, th=15, d_ordered_kf=None, d_ordered_w=None):
+        """KeyFrame::UpdateConnections (mode COVIS_UPDATE_CONNECTIONS; reference src/KeyFrame.cc:388-511) / the vote of
+        Tracking::UpdateLocalKeyFrames (COVIS_LOCAL_KEYFRAMES; src/Tracking.cc:3030-3102) for n_subjects rows of MapPoints.  d_obs_off / d_obs:
+        update_map_points_device's CSR; d_mp_flags / d_kf_flags: bit 0 isBad(); d_kf_key [f] uint64, the KeyFrame* order; d_subject_mp
+        [s*capacity + i] MapPoint indices or -1, d_subject_n [s]; d_subject_kf / d_subject_map_id / d_kf_map_id (UPDATE_CONNECTIONS); d_counter_*
+        [s*conn_capacity + j] the counter in key order, d_ordered_* the ordered list (UPDATE_CONNECTIONS); d_result one COVIS_RESULT_DTYPE row
+        per subject."""
+        self._check(self._L.orbx_covisibility_device(
+            self._h, int(mode), n_points, _dev(d_obs_off), _dev(d_obs), _dev(d_mp_flags), n_frames, _dev(d_kf_flags), _dev(d_kf_map_id), _dev(d_kf_key),
+            n_subjects, _dev(d_subject_mp), _dev(d_subject_n), capacity, _dev(d_subject_kf), _dev(d_subject_map_id), th, conn_capacity,
+            _dev(d_counter_kf), _dev(d_counter_w), _dev(d_ordered_kf), _dev(d_ordered_w), _dev(d_result)))
+
+    def keyframe_redundancy_device(self, n_points, d_obs_off, d_obs, d_mp_flags, n_frames, d_kf_flags, d_kps_un, d_n_out, n_subjects, d_subject_mp,
+                                   d_subject_n, capacity, d_subject_kf, d_result, monocular=True, d_depth=None, d_th_depth=None, d_mp_nobs=None,
+                                   th_obs=3, redundant_th=0.9, d_slot_state=None):
+        """The test inside LocalMapping::KeyFrameCulling's loop (reference src/LocalMapping.cc:977-1043) for n_subjects keyframes (device frames
+        d_subject_kf[s]) on covisibility_device's tables; d_kf_flags bit 1 = the map's initial keyframe; d_mp_nobs [m] MapPoint::Observations()
+        (None = the list length); d_depth / d_th_depth when not monocular; d_result one REDUNDANCY_RESULT_DTYPE row per subject; d_slot_state
+        [s*capacity + i] optional: 0 not counted, 1 counted, 2 redundant."""
+        self._check(self._L.orbx_keyframe_redundancy_device(
+            self._h, n_points, _dev(d_obs_off), _dev(d_obs), _dev(d_mp_flags), _dev(d_mp_nobs), n_frames, _dev(d_kf_flags), _dev(d_kps_un), _dev(d_n_out),
+            _dev(d_depth), _dev(d_th_depth), n_subjects, _dev(d_subject_mp), _dev(d_subject_n), capacity, _dev(d_subject_kf), 1 if monocular else 0,
+            th_obs, float(redundant_th), _dev(d_result), _dev(d_slot_state)))
+
+    def debug_covisibility_launches(self, which):
+        """launches so far in this process of k_covis_rank (0) / k_covis_vote (1) / k_keyframe_redundancy (2)"""
+        return self._L.orbx_debug_covisibility_launches(which)
 
     def project_last_frame_device(self, n_pairs, last, cur, d_kps, d_kps_un, d_n, capacity, d_mp_flags, d_world, d_poses, cam, bounds,
                                   mbf, mb, th, mono, d_queries):

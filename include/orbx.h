@@ -714,6 +714,121 @@ int orbx_detect_candidates_device(orbx_handle* h, const orbx_vocabulary* v, int 
                                   const int* d_q_map_id, const uint8_t* d_connected, int n_candidates, float* d_score, orbx_place_result* d_result,
                                   int* d_loop, int* d_merge, int* d_cand, int cand_capacity, int* d_common_words);
 
+/* ---- covisibility: the lists of keyframes every chain above starts from ---------------------------------------------------------
+ * One operation of the reference - walk a row of MapPoints, walk each MapPoint's observations, count per observing keyframe - in its
+ * three places, for ONE-CAMERA keyframes (NLeft == -1) and a batch of independent subjects:
+ *   KeyFrame::UpdateConnections (src/KeyFrame.cc:388-511): every new keyframe, after every Fuse, every keyframe loop closing touches;
+ *   the voting half of Tracking::UpdateLocalKeyFrames (src/Tracking.cc:3030-3102): every tracked frame, between
+ *     orbx_optimize_pose_device and orbx_frustum_requests_device;
+ *   the test inside LocalMapping::KeyFrameCulling's loop (src/LocalMapping.cc:977-1043): orbx_keyframe_redundancy_device below.
+ * The tables are the other entries': the observation CSR of orbx_update_map_points_device, the per-keypoint MapPoint row, d_kps_un,
+ * d_n_out, the flags.  All integers (one float product in the redundancy test): the results are the reference's, byte for byte. */
+enum orbx_covis_mode {
+    ORBX_COVIS_UPDATE_CONNECTIONS = 0,     /* KeyFrame::UpdateConnections */
+    ORBX_COVIS_LOCAL_KEYFRAMES = 1         /* Tracking::UpdateLocalKeyFrames up to :3102, before the neighbour expansion */
+};
+enum orbx_covis_status {
+    ORBX_COVIS_OK = 0,
+    ORBX_COVIS_EMPTY = 1,                  /* UPDATE_CONNECTIONS: KFcounter.empty() (:423) returns before anything is assigned: no list entry of
+                                            * the subject is written.  (LOCAL_KEYFRAMES goes on with an empty list and pKFmax NULL: OK, n_counter 0,
+                                            * kf_max -1) */
+    ORBX_COVIS_TRUNCATED = 2,              /* a list is longer than conn_capacity: the row holds the true counts, the first conn_capacity entries
+                                            * of each order are written */
+    ORBX_COVIS_BAD_INDEX = 3,              /* a MapPoint index outside [-1, n_points), a list with d_obs_off[m] < 0, d_obs_off[m+1] < d_obs_off[m] or
+                                            * d_obs_off[m+1] > d_obs_off[n_points], an observing frame outside [0, n_frames), d_subject_kf[s] outside
+                                            * [-1, n_frames): the reference would index out of bounds.  Found before anything of the subject is
+                                            * written; no list entry is.  (A bad MapPoint's list is not read and not checked) */
+    ORBX_COVIS_DUPLICATE_KEY = 4           /* two of the n_frames keys are equal: the frames have no order.  A property of the CALL, said in every
+                                            * subject's row; no list entry of any subject is written */
+};
+/* One row per subject.  EMPTY, BAD_INDEX and DUPLICATE_KEY rows hold zero counts and kf_max -1. */
+typedef struct orbx_covis_result {
+    int32_t status;                /* orbx_covis_status */
+    int32_t n_counter;             /* UPDATE_CONNECTIONS: KFcounter.size() = mConnectedKeyFrameWeights.size(); LOCAL_KEYFRAMES:
+                                    * mvpLocalKeyFrames.size() at :3102; whatever conn_capacity is */
+    int32_t n_ordered;             /* UPDATE_CONNECTIONS: mvpOrderedConnectedKeyFrames.size(); LOCAL_KEYFRAMES: 0 */
+    int32_t nmax;                  /* nmax (:440) / max (:3094) */
+    int32_t kf_max;                /* pKFmax as a device frame: the FIRST strictly greater count in key order; -1 = NULL */
+} orbx_covis_result;
+
+/*   n_points, d_obs_off[n_points + 1], d_obs[o*2 + {0,1}] : exactly orbx_update_map_points_device's CSR of (device frame, keypoint row):
+ *                     MapPoint m's mObservations.  Only the frame is read here.  A std::map holds a keyframe once: an entry is a vote.
+ *   d_mp_flags[m]   : bit 0 = MapPoint::isBad().
+ *   n_frames, d_kf_flags[f], d_kf_map_id[f] : bit 0 = KeyFrame::isBad(); GetMap() as a number (UPDATE_CONNECTIONS; may be NULL otherwise).
+ *   d_kf_key[f]     : the KeyFrame* address, or any number in the same order.  std::map<KeyFrame*,int> iterates in address order and
+ *                     std::sort on pair<int,KeyFrame*> breaks equal weights by address, so the address order is part of the reference's
+ *                     result, and only the caller knows it.  Two frames with one key: ORBX_COVIS_DUPLICATE_KEY.
+ *   d_subject_mp[s*capacity + i], d_subject_n[s] : mvpMapPoints of subject s as MapPoint indices, -1 for NULL - the row
+ *                     orbx_optimize_pose_device takes as its matches; d_subject_n[s] is clamped into [0, capacity].
+ *   d_subject_kf[s] : UPDATE_CONNECTIONS: the subject's own device frame (the mnId == mnId test of :415), -1 for none.  d_subject_map_id[s]:
+ *                     mpMap.  Both may be NULL in LOCAL_KEYFRAMES mode, which has neither test.
+ *   th              : 15 in the reference (:430).
+ * UPDATE_CONNECTIONS: every slot i < N is visited - a MapPoint that stands in two slots votes twice, as :401 does.  Skipped: -1, a bad
+ * MapPoint; an observer that is the subject itself, is bad, or lives in another map (:415).
+ * LOCAL_KEYFRAMES: no self test and no map test; a bad observer IS counted into the map and skipped when the map is walked (:3091): it is
+ * neither listed nor eligible as pKFmax.
+ * Outputs, one block of conn_capacity entries per subject:
+ *   d_counter_kf / d_counter_w [s*conn_capacity + j] : UPDATE_CONNECTIONS: mConnectedKeyFrameWeights, the WHOLE counter, counts below th
+ *                     included, in key-ascending order: what GetConnectedKeyFrames / GetWeight - and orbx_detect_candidates_device's
+ *                     d_connected - are made from.  LOCAL_KEYFRAMES: mvpLocalKeyFrames at :3102 and each one's count, key ascending, no
+ *                     threshold, no sort.
+ *   d_ordered_kf / d_ordered_w [s*conn_capacity + j] : UPDATE_CONNECTIONS only (may be NULL otherwise): mvpOrderedConnectedKeyFrames /
+ *                     mvOrderedWeights - every count >= th, or if there is none the single pair (nmax, pKFmax) (:452-456) - after sort
+ *                     ascending on (weight, key) and push_front: weight descending and, among equal weights, key DESCENDING.  Its first
+ *                     ten are GetBestCovisibilityKeyFrames(10), a row of d_db_covis; its front is mpParent under mbFirstConnection.
+ *   d_result[s]     : see above.  Entries of a block beyond the counts are never touched.
+ * Stays with the caller: the reciprocal AddConnection(this, w) on each listed keyframe and its UpdateBestCovisibles (a sort of THAT
+ * keyframe's weight list); AddChild / the parent bookkeeping; the neighbour expansion of UpdateLocalKeyFrames (:3104 onward); nulling a
+ * frame's bad MapPoints (:3049).  Two-camera keyframes are not built: a rig's observation has two entries and would vote twice.
+ * Two launches: k_covis_rank turns the keys into ranks (a wave per frame), k_covis_vote gives a workgroup per subject with a counter word
+ * per frame and 8 bytes per sort slot (a power of two of slots) in LDS.  They must fit 160 KB - 512: n_frames <= 8192, else
+ * ORBX_ERR_UNSUPPORTED before anything is launched or allocated.  conn_capacity takes no LDS and has no such bound.  n_subjects <= 65535.
+ * The rank tables (8 bytes per frame) belong to the handle and grow on first use.  ORBX_ERR_BAD_ARGUMENT is returned before any launch.
+ * Asynchronous on the handle's stream; no CPU path. */
+int orbx_covisibility_device(orbx_handle* h, int mode, int n_points, const int* d_obs_off, const int* d_obs, const uint8_t* d_mp_flags, int n_frames,
+                             const uint8_t* d_kf_flags, const int* d_kf_map_id, const uint64_t* d_kf_key, int n_subjects, const int* d_subject_mp,
+                             const int* d_subject_n, int capacity, const int* d_subject_kf, const int* d_subject_map_id, int th, int conn_capacity,
+                             int* d_counter_kf, int* d_counter_w, int* d_ordered_kf, int* d_ordered_w, orbx_covis_result* d_result);
+
+enum orbx_redundancy_status {
+    ORBX_REDUNDANCY_OK = 0,
+    ORBX_REDUNDANCY_SKIPPED = 1,           /* the map's initial keyframe or a bad one (:977): nothing is counted, no slot state is written */
+    ORBX_REDUNDANCY_BAD_INDEX = 2          /* as ORBX_COVIS_BAD_INDEX, and: d_subject_kf[s] outside [0, n_frames), an observation's keypoint row
+                                            * outside [0, N_f).  Found before anything of the subject is written; no slot state is */
+};
+typedef struct orbx_redundancy_result {
+    int32_t status;                /* orbx_redundancy_status */
+    int32_t n_mps;                 /* nMPs */
+    int32_t n_redundant;           /* nRedundantObservations */
+    int32_t redundant;             /* 1 when nRedundantObservations > redundant_th*nMPs (:1043): (float)n_redundant > redundant_th*(float)n_mps,
+                                    * ONE float product and a float compare, as the int/float expression evaluates */
+} orbx_redundancy_result;
+
+/* The test inside LocalMapping::KeyFrameCulling's loop (src/LocalMapping.cc:977-1043) for n_subjects one-camera keyframes, on the same
+ * tables.  Subject s is device frame d_subject_kf[s]; d_subject_mp[s*capacity + i] / d_subject_n[s] are its GetMapPointMatches().
+ *   d_mp_nobs[m]    : MapPoint::Observations(), which is NOT the list length (a stereo observation adds 2); NULL = the list length.
+ *   d_kf_flags[f]   : bit 0 = isBad(), bit 1 = "is the map's initial keyframe" (mnId == GetMap()->GetInitKFid()): either gives SKIPPED.
+ *   d_kps_un[f*capacity + i], d_n_out[f] : mvKeysUn of the n_frames frames; only octaves are read.  d_n_out[f] is clamped into [0, capacity].
+ *   d_depth[f*capacity + i], d_th_depth[f] : mvDepth and mThDepth, read when monocular == 0 (:992-996; may be NULL otherwise).  The skip is
+ *                     depth > th || depth < 0 as written: a NaN depth and -0.0 are counted.
+ *   th_obs          : 3.  redundant_th: 0.9f, or 0.5f (inertial and not monocular).
+ * Per slot i < N: NULL and bad MapPoints and far points are skipped; nMPs++; only if Observations() > th_obs the observers OTHER than the
+ * subject whose octave is <= octave_i + 1 are counted - observers are NOT tested for isBad - and the slot is redundant when that count is
+ * > th_obs (the reference's break changes nothing).
+ *   d_slot_state[s*capacity + i] : optional (NULL); 0 = not counted, 1 = counted, 2 = redundant, for i < N of an OK subject.
+ * Stays with the caller: SetBadFlag and its consequences - KeyFrameCulling culls INSIDE its loop, so a later keyframe of the same loop sees
+ * the erased observations; the entry answers, per listed keyframe, what the reference computes from the tables AS THEY STAND, and a caller
+ * who wants the exact sequence refreshes the tables after a cull -; the count > 20 && mbAbortBA / count > 100 cut; every inertial branch
+ * (:1045-1076).  Two-camera keyframes are not built (:1003 reads mvKeysRight[i] with the unshifted i).
+ * One launch, k_keyframe_redundancy, a workgroup per subject with a state byte per slot in LDS: capacity <= 163280, else
+ * ORBX_ERR_UNSUPPORTED before anything is launched.  n_subjects <= 65535.  ORBX_ERR_BAD_ARGUMENT (a NaN redundant_th among the reasons) is
+ * returned before any launch.  Asynchronous on the handle's stream; no CPU path. */
+int orbx_keyframe_redundancy_device(orbx_handle* h, int n_points, const int* d_obs_off, const int* d_obs, const uint8_t* d_mp_flags, const int* d_mp_nobs,
+                                    int n_frames, const uint8_t* d_kf_flags, const orbx_keypoint* d_kps_un, const int* d_n_out, const float* d_depth,
+                                    const float* d_th_depth, int n_subjects, const int* d_subject_mp, const int* d_subject_n, int capacity,
+                                    const int* d_subject_kf, int monocular, int th_obs, float redundant_th, orbx_redundancy_result* d_result,
+                                    uint8_t* d_slot_state);
+
 /* ---- the consumer of the FeatureVector: ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) ------------------
  * (src/ORBmatcher.cc:269-471; Tracking::TrackReferenceKeyFrame, Tracking::Relocalization), Nleft == -1: for n_pairs pairs
  * (keyframe = frame kf_first + p*kf_step, current frame = frame cur_first + p*cur_step of one device-resident batch) the features of
@@ -1477,6 +1592,10 @@ int orbx_debug_pose_optimization_launches(void);
 /* orbx_detect_candidates_device has ONE launch form of two kernels: the launches so far in this process of k_place_pairs (which = 0; none for
  * a call with n_db == 0) and of k_place_query (which = 1; one per accepted call). */
 int orbx_debug_place_recognition_launches(int which);
+/* orbx_covisibility_device has ONE launch form of two kernels, orbx_keyframe_redundancy_device of one: the launches so far in this process
+ * of k_covis_rank (which = 0) and k_covis_vote (1), one each per accepted call of the vote, and of k_keyframe_redundancy (2), one per
+ * accepted call of the redundancy test.  Another `which` returns ORBX_ERR_BAD_ARGUMENT. */
+int orbx_debug_covisibility_launches(int which);
 int orbx_debug_new_map_points_stats(int* out2);
 
 /* the Sim3 projection search (orbx_search_by_projection_sim3_device): out4[0] rounds the fixed point of the last launch's pair 0 needed
