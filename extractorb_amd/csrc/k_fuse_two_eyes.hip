@@ -12,12 +12,12 @@
 //   * KeyFrame::GetFeaturesInArea(u, v, r, bRight) reads that eye's grid (mGrid / mGridRight) and its RAW keypoints (mvKeys / mvKeysRight,
 //     KeyFrame.cc:801-803), and :1524-1528 take position and octave from the same: device frames 2r (left) and 2r + 1 (right) of rig r, the
 //     layout of orbx_frame_finish_two_eyes_device;
-//   * mvuRight of such a keyframe has Nleft entries, all -1 (src/Frame.cc:1150): the reprojection test is always the monocular one (:1547-1557),
-//     and ur, invz, mbf have no observable effect.  (The reference indexes mvuRight with the right eye's own index, :1533 before :1559: past
-//     the array where Nright > Nleft.  -1 is taken there.)
+//   * the reprojection test is always the monocular one (:1547-1557): fuseBest<false>, where k_keyframe_project.hpp says why;
 //   * bestIdx is in the KEYFRAME's numbering (:1559): a right keypoint i is NLeft + i; its descriptor is row i of device frame 2r + 1.
-// Everything after (u, v) up to the cell window is keyFrameIsInImage + keyFrameWindow of k_keyframe_project.hpp, shared with k_fuse and the
-// Sim3 projection search; the window scan is k_fuse's, read through L2: no LDS table, no capacity bound.
+// From k_keyframe_project.hpp, shared with k_fuse and / or the Sim3 projection search: everything after (u, v) up to the cell window
+// (keyFrameIsInImage + keyFrameWindow), the eye's tables (keyFrameView of device frame 2r + eye), the visit of the window with Fuse's
+// candidate tests and strict minimum (fuseBest), the thLow decision, the result stores and the exit codes (fuseFinish, kFuse*).  The tables
+// are read through L2: no LDS table, no capacity bound.
 // LAUNCH SHAPE: one lane per (MapPoint, eye), as k_frustum_two_eyes_check.  With both eyes asked for the eye is the lane's parity; with one eye
 // asked for every lane takes that eye and a workgroup covers twice the MapPoints (no lane idles for an eye nobody wants).  Either way the eye
 // is a run-time index into LDS, never a template or a loop: the KannalaBrandt8 code (two software atan2f, a sincos, the polynomial) is
@@ -43,8 +43,6 @@
 namespace orbx {
 
 namespace {
-enum { kFuse2ExitFlag = 0, kFuse2ExitNegDepth, kFuse2ExitNotInImage, kFuse2ExitDistance, kFuse2ExitNormal, kFuse2ExitEmptyWindow,
-       kFuse2ExitAboveThLow, kFuse2ExitFused };      // == ORBX_FUSE_*
 constexpr int kFuse2Threads = 256;
 constexpr int kFuse2EyeFloats = kRigEyeFloats;      // one eye of a rig keyframe (k_rig_two_eyes.hpp)
 }  // namespace
@@ -71,7 +69,7 @@ __device__ __forceinline__ void fuseTwoEyesLane(const float* __restrict__ mpWorl
     const int eye = both ? (int)(slot & 1) : p.eyes - 1;
     const long long i = both ? slot >> 1 : slot;
     const long long rig = p.kfFirst + (long long)pair * p.kfStep, list = p.mpFirst + (long long)pair * p.mpStep;
-    int code = kFuse2ExitFlag, bestDist = 256, bestIdx = -1;
+    int code = kFuseFlag, bestDist = 256, bestIdx = -1;
     if (i < p.mpCapacity) {
         const long long m = list * p.mpCapacity + i, o = ((long long)pair * 2 + eye) * p.mpCapacity + i;
         const int NM = nMp ? min(max(nMp[list], 0), p.mpCapacity) : p.mpCapacity;
@@ -85,62 +83,27 @@ __device__ __forceinline__ void fuseTwoEyesLane(const float* __restrict__ mpWorl
             const float xw[3] = {mpWorld[3 * m], mpWorld[3 * m + 1], mpWorld[3 * m + 2]};
             float xc[3];
             for (int r = 0; r < 3; r++) xc[r] = gemmRow(e[3 * r], e[3 * r + 1], e[3 * r + 2], xw, 1.0, e[9 + r], true);      // Rcw*p3Dw+tcw (:1456)
-            code = kFuse2ExitNegDepth;
+            code = kFrontNegDepth;
             if (xc[2] < 0.0f) break;                                                         // :1459 (z == 0 and z == -0 go on)
             float u, v;
             kb8Project(k, xc[0], xc[1], xc[2], u, v);                                        // pCamera->project (:1470)
-            code = kFuse2ExitNotInImage;
+            code = kFrontNotInImage;
             if (!keyFrameIsInImage(u, v, p)) break;                                          // :1473
             const float Ow[3] = {e[12], e[13], e[14]};
             KfProjection q;
-            code = keyFrameWindow(u, v, xw, Ow, mpNormal + 3 * m, mpDist + 3 * m, p, q);     // its exits 3 .. 5 are kFuse2ExitDistance .. EmptyWindow
+            code = keyFrameWindow(u, v, xw, Ow, mpNormal + 3 * m, mpDist + 3 * m, p, q);     // kFrontDistance .. kFrontEmptyWindow, or passed
             if (code != kFrontPassed) break;
-            code = kFuse2ExitEmptyWindow;
-            const float r = q.r;
-            const int level = q.level, minCX = q.minCX, maxCX = q.maxCX, minCY = q.minCY, maxCY = q.maxCY;
-            // a candidate's kpLevel is level or level - 1 (:1530): the two mvInvLevelSigma2 it can need
-            const float invHi = p.invSigma2[level], invLo = p.invSigma2[max(level - 1, 0)];
             const long long f = 2 * rig + eye;                                               // mvKeys / mGrid or mvKeysRight / mGridRight
-            const int N = min(max(nOut[f], 0), p.capacity);
+            const KeyFrameView kf = keyFrameView(f, kps, desc, nOut, gridOff, gridIdx, p.capacity);
             const int nLeft = min(max(nOut[2 * rig], 0), p.capacity);                        // pKF->NLeft
-            const int* off = gridOff + f * (kGridCells + 1);
-            const int* gi = gridIdx + f * p.capacity;
-            const Keypoint* K = kps + f * p.capacity;
-            const uint4* D = (const uint4*)(desc + f * p.capacity * 32);
-            const int nIn = min(max(off[kGridCells], 0), N);                                 // (clamped: a corrupt grid must not index past the frame)
             const uint4 dlo = *(const uint4*)(mpDesc + m * 32), dhi = *(const uint4*)(mpDesc + m * 32 + 16);
-            bool any = false;
-            for (int cx = minCX; cx <= maxCX; cx++) {
-                if (minCY > maxCY) break;
-                const int sEnd = min(max(off[cx * kGridRows + maxCY + 1], 0), nIn);
-                for (int s = min(max(off[cx * kGridRows + minCY], 0), nIn); s < sEnd; s++) {
-                    const int idx = min(max(gi[s], 0), p.capacity - 1);
-                    const float kx = K[idx].x, ky = K[idx].y;
-                    if (!(fabsf(__fsub_rn(kx, u)) < r && fabsf(__fsub_rn(ky, v)) < r)) continue;      // KeyFrame.cc:804-808
-                    any = true;
-                    const int lv = K[idx].octave;
-                    if (lv < level - 1 || lv > level) continue;                              // :1530
-                    if (p.reprojCheck) {                                                     // mvuRight is -1: :1547-1557 always
-                        const float inv = lv == level ? invHi : invLo;      // mvInvLevelSigma2[kpLevel]; level - 1 = -1 reads entry 0 (the reference would index past the table)
-                        const float ex = __fsub_rn(u, kx), ey = __fsub_rn(v, ky);
-                        const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        if ((double)__fmul_rn(e2, inv) > 5.99) continue;
-                    }
-                    const uint4 a = D[2 * idx], b = D[2 * idx + 1];
-                    const int dist = hamming256(dlo, dhi, a, b);
-                    if (dist < bestDist) { bestDist = dist; bestIdx = idx; }                 // :1565, strict: the first of equals stays
-                }
-            }
-            if (!any) break;                                                                 // vIndices.empty() (:1509)
-            code = bestIdx >= 0 && bestDist <= p.thLow ? kFuse2ExitFused : kFuse2ExitAboveThLow;      // :1573
-            if (eye) bestIdx += nLeft;                                                       // :1559: the keyframe's numbering
+            if (!fuseBest<false>(kf, q, nullptr, dlo, dhi, p, bestDist, bestIdx)) code = kFrontEmptyWindow;      // vIndices.empty() (:1509); nullptr: <false> never reads UR
+            if (eye && bestIdx >= 0) bestIdx += nLeft;                                       // :1559: the keyframe's numbering
         } while (false);
-        bestIdxOut[o] = code == kFuse2ExitFused ? bestIdx : -1;
-        bestDistOut[o] = bestDist;
-        if (exitOut) exitOut[o] = (uint8_t)code;
+        code = fuseFinish(code, bestIdx, bestDist, p, o, bestIdxOut, bestDistOut, exitOut);
     }
     // the lanes of a wave hold the left eye (both: the even lanes; eyes == 1: all), the right eye (the odd lanes; eyes == 2: all)
-    const unsigned long long fused = __ballot(code == kFuse2ExitFused);
+    const unsigned long long fused = __ballot(code == kFuseFused);
     const unsigned long long leftLanes = both ? 0x5555555555555555ull : p.eyes == 1 ? ~0ull : 0ull;
     if ((threadIdx.x & 63) == 0) {
         if (fused & leftLanes) atomicAdd(&nFused[pair * 2], __popcll(fused & leftLanes));

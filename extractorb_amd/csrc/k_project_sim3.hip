@@ -2,7 +2,9 @@
 //   projection 0: SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming)                           reference src/ORBmatcher.cc:473-586
 //   projection 1: SearchByProjection(pKF, Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming) reference src/ORBmatcher.cc:588-704
 // (callers: src/LoopClosing.cc:730, :755, :1008) for keyframes with NLeft == -1 and the Pinhole model.
-// Up to the cell window the two are Fuse's Sim3 overload: the front end is k_keyframe_project.hpp, shared with k_fuse.hip.  What Fuse does
+// Up to the cell window the two are Fuse's Sim3 overload: the front end (projectIntoKeyFrame), the keyframe's tables with their clamps
+// (keyFrameView; keyFrameSlotsInGrid alone in the settling kernel) and the visit of the window (keyFrameVisitArea) are
+// k_keyframe_project.hpp's, shared with k_fuse.hip and k_fuse_two_eyes.hip; sim3Scan below is this search's body of the visit.  What Fuse does
 // not have: a match CLOSES its keypoint for every later MapPoint of the list (vpMatched[bestIdx] = pMP at :579 / :696 is read back at
 // :558 / :675), so the requests of one call are a sequential chain.  Two kernels:
 //   k_sim3_window  one thread per (pair, MapPoint), grid over the whole GPU as k_fuse: the front end, then the window from L2.  Of the
@@ -49,49 +51,25 @@ struct Sim3Window { float u, v, r; int cells; };
 struct Sim3Record { int keys[kSim3Top]; Sim3Window win; int cnt, pad[3]; };
 static_assert(sizeof(Sim3Record) % 16 == 0, "records are read with 128-bit loads");
 
-// The keyframe of a pair as the scans read it
-struct Sim3KeyFrame {
-    const int* off; const int* gi; const Keypoint* K; const uint4* D; const uint8_t* occ; int nIn, capacity;
-};
-__device__ __forceinline__ Sim3KeyFrame sim3KeyFrame(long long f, int pair, const Keypoint* kpsUn, const uint8_t* desc, const int* nOut,
-                                                     const int* gridOff, const int* gridIdx, const uint8_t* occupied, int capacity) {
-    Sim3KeyFrame k;
-    k.off = gridOff + f * (kGridCells + 1); k.gi = gridIdx + f * capacity; k.K = kpsUn + f * capacity;
-    k.D = (const uint4*)(desc + f * capacity * 32);
-    k.occ = occupied ? occupied + (long long)pair * capacity : nullptr;
-    const int N = min(max(nOut[f], 0), capacity);
-    k.nIn = min(max(k.off[kGridCells], 0), N);      // (clamped: a corrupt grid must not index past the frame - or past closedBy)
-    k.capacity = capacity;
-    return k;
-}
-
-// KeyFrame::GetFeaturesInArea's visit (src/KeyFrame.cc:794-811) with the candidate tests of :555-575 / :672-692.  closedBy == nullptr: the
-// static tests only.  Returns the number of passing candidates, their kSim3Top smallest keys in `keys`; any = vIndices is not empty.
-__device__ __forceinline__ int sim3Scan(const KfProjection& q, const Sim3KeyFrame& kf, const uint4& dlo, const uint4& dhi, int maxDist,
-                                        const int* closedBy, int i, int (&keys)[kSim3Top], bool& any) {
+// The candidate tests of :555-575 / :672-692 over KeyFrame::GetFeaturesInArea's visit of q's window (keyFrameVisitArea).  occ: the pair's
+// vpMatched on entry (may be NULL).  closedBy == nullptr: the static tests only.  Returns the number of passing candidates, their kSim3Top
+// smallest keys in `keys`; any = vIndices is not empty.
+__device__ __forceinline__ int sim3Scan(const KfProjection& q, const KeyFrameView& kf, const uint8_t* occ, const uint4& dlo, const uint4& dhi,
+                                        int maxDist, const int* closedBy, int i, int (&keys)[kSim3Top], bool& any) {
 #pragma unroll
     for (int k = 0; k < kSim3Top; k++) keys[k] = kSim3NoKey;
     int count = 0;
-    any = false;
-    for (int cx = q.minCX; cx <= q.maxCX; cx++) {
-        if (q.minCY > q.maxCY) break;
-        const int sEnd = min(max(kf.off[cx * kGridRows + q.maxCY + 1], 0), kf.nIn);
-        for (int s = min(max(kf.off[cx * kGridRows + q.minCY], 0), kf.nIn); s < sEnd; s++) {
-            const int idx = min(max(kf.gi[s], 0), kf.capacity - 1);
-            const float kx = kf.K[idx].x, ky = kf.K[idx].y;
-            if (!(fabsf(__fsub_rn(kx, q.u)) < q.r && fabsf(__fsub_rn(ky, q.v)) < q.r)) continue;      // KeyFrame.cc:804-808
-            any = true;
-            if (kf.occ && kf.occ[idx]) continue;                                     // vpMatched[idx] on entry (:558, :675)
-            if (closedBy && closedBy[s] < i) continue;                               // ... or set by an earlier request
-            const int lv = kf.K[idx].octave;
-            if (lv < q.level - 1 || lv > q.level) continue;                          // :563, :680
-            const uint4 e = kf.D[2 * idx], g = kf.D[2 * idx + 1];
-            const int dist = hamming256(dlo, dhi, e, g);
-            if (dist > maxDist) continue;                                            // :577, :694 (header: applied before the minimum, same result)
-            count++;
-            sortedInsert(keys, (dist << 16) | s);        // slots are distinct, so keys are: the sorted insert keeps the first of equal distances
-        }
-    }
+    any = keyFrameVisitArea(kf, q, [&](int s, int idx, float, float) {
+        if (occ && occ[idx]) return;                                                 // vpMatched[idx] on entry (:558, :675)
+        if (closedBy && closedBy[s] < i) return;                                     // ... or set by an earlier request
+        const int lv = kf.K[idx].octave;
+        if (lv < q.level - 1 || lv > q.level) return;                                // :563, :680
+        const uint4 e = kf.D[2 * idx], g = kf.D[2 * idx + 1];
+        const int dist = hamming256(dlo, dhi, e, g);
+        if (dist > maxDist) return;                                                  // :577, :694 (header: applied before the minimum, same result)
+        count++;
+        sortedInsert(keys, (dist << 16) | s);        // slots are distinct, so keys are: the sorted insert keeps the first of equal distances
+    });
     return count;
 }
 
@@ -120,10 +98,11 @@ __global__ __launch_bounds__(256) void k_sim3_window(const float* __restrict__ m
         KfProjection q;
         code = projectIntoKeyFrame(poses + (long long)pair * 12, mpWorld + 3 * m, mpNormal + 3 * m, mpDist + 3 * m, p, p.projection, q);
         if (code != kFrontPassed) break;
-        const Sim3KeyFrame kf = sim3KeyFrame(f, pair, kpsUn, desc, nOut, gridOff, gridIdx, occupied, p.capacity);
+        const uint8_t* occ = occupied ? occupied + (long long)pair * p.capacity : nullptr;
+        const KeyFrameView kf = keyFrameView(f, kpsUn, desc, nOut, gridOff, gridIdx, p.capacity);
         const uint4 dlo = *(const uint4*)(mpDesc + m * 32), dhi = *(const uint4*)(mpDesc + m * 32 + 16);
         bool any;
-        count = sim3Scan(q, kf, dlo, dhi, p.maxDist, nullptr, i, keys, any);
+        count = sim3Scan(q, kf, occ, dlo, dhi, p.maxDist, nullptr, i, keys, any);
         code = any ? (int)kSim3NoMatch : (int)kFrontEmptyWindow;                               // vIndices.empty() (:547, :664) comes before any keypoint state
         if (count > kSim3Top) {
             Sim3Window w;
@@ -161,10 +140,11 @@ __device__ __forceinline__ int sim3RoundStep(int i, int pair, int prev, const ui
     KfProjection q;
     q.u = w.u; q.v = w.v; q.r = w.r; q.invz = 0.f;
     q.level = w.cells & 31; q.minCX = (w.cells >> 5) & 63; q.maxCX = (w.cells >> 11) & 63; q.minCY = (w.cells >> 17) & 63; q.maxCY = (w.cells >> 23) & 63;
-    const Sim3KeyFrame kf = sim3KeyFrame(f, pair, kpsUn, desc, nOut, gridOff, gridIdx, occupied, p.capacity);
+    const uint8_t* occ = occupied ? occupied + (long long)pair * p.capacity : nullptr;
+    const KeyFrameView kf = keyFrameView(f, kpsUn, desc, nOut, gridOff, gridIdx, p.capacity);
     const uint4 dlo = *(const uint4*)(mpDesc + m * 32), dhi = *(const uint4*)(mpDesc + m * 32 + 16);
     bool any;
-    sim3Scan(q, kf, dlo, dhi, p.maxDist, closedBy, i, keys, any);
+    sim3Scan(q, kf, occ, dlo, dhi, p.maxDist, closedBy, i, keys, any);
     return keys[0];
 }
 
@@ -194,8 +174,7 @@ __global__ __launch_bounds__(kSettleThreads) void k_sim3_settle(const uint8_t* _
     const int pair = blockIdx.x, tid = threadIdx.x;
     const long long f = p.kfFirst + (long long)pair * p.kfStep;
     const int* gi = gridIdx + f * p.capacity;
-    const int N = min(max(nOut[f], 0), p.capacity);
-    const int nIn = min(max(gridOff[f * (kGridCells + 1) + kGridCells], 0), N);      // as sim3KeyFrame: every slot of a key is below it
+    const int nIn = keyFrameSlotsInGrid(f, nOut, gridOff, p.capacity);      // as the scans' view: every slot of a key is below it
     int* out = matches + (long long)pair * p.capacity;
     for (int s = tid; s < p.capacity; s += kSettleThreads) { closedBy[s] = 0x7fffffff; out[s] = -1; }
     for (int i = tid; i < p.mpCapacity; i += kSettleThreads) dec[i] = kSim3NoKey;

@@ -1,6 +1,7 @@
 """extractorb_amd/csrc/k_match_helpers.hpp is the only statement of four lines of the reference that every matcher kernel uses: ComputeThreeMaxima
 (ORBmatcher.cc:2303-2344), the rotation-histogram bin (:773-783), GetFeaturesInArea's cell window (Frame.cc:666-688) and the sorted best-key
-list.  Here they are called directly: tests/cpp/match_helpers_check.cpp is the header compiled for the host behind tests/cpp/host_shim (as a
+list; k_keyframe_project.hpp on top of it is the only statement of KeyFrame::GetFeaturesInArea's visit (KeyFrame.cc:794-811) with the clamps
+that keep a corrupt grid inside its frame.  Here they are called directly: tests/cpp/match_helpers_check.cpp is the header compiled for the host behind tests/cpp/host_shim (as a
 sanitized stand-alone program), and every answer is compared with an independent statement below - sorting for the maxima and the list, exact
 rational rounding for the bin, float32 steps spelled out for the window.  No GPU."""
 import math
@@ -206,3 +207,133 @@ def test_hamming_256(ask):
     for (a, b), g in zip(pairs, got):
         assert g == [sum(bin(int(x) ^ int(y)).count("1") for x, y in zip(a, b))]
     assert got[1] == [256] and got[2] == [8]
+
+
+# ---- KeyFrame::GetFeaturesInArea's visit ---------------------------------------------------------------------------------------------------
+GRID_CELLS = GRID_COLS * GRID_ROWS
+CELL_PX = 10.0      # this test's own frame: 640 x 480 px from the origin in cells of 10 x 10 px
+
+
+class Grid:
+    """A hand-made keyframe: keypoints (x, y, octave) pushed into the cell they lie in, in list order, as KeyFrame's constructor does, and the
+    tables the kernels read of it - the cells' CSR offsets (cell = ix * GRID_ROWS + iy) and the slot -> keypoint table - with room for
+    `capacity` keypoints and not one entry more."""
+
+    def __init__(self, kps, capacity):
+        self.kps, self.capacity, self.n_out = list(kps), capacity, len(kps)
+        self.cells = [[] for _ in range(GRID_CELLS)]
+        for i, (x, y, _) in enumerate(self.kps):
+            self.cells[int(x // CELL_PX) * GRID_ROWS + int(y // CELL_PX)].append(i)
+        self.off, self.gi = [0], []
+        for c in self.cells:
+            self.gi += c
+            self.off.append(len(self.gi))
+        self.gi += [0] * (capacity - len(self.gi))
+
+    def features_in_area(self, u, v, r, win):
+        """KeyFrame.cc:794-811 on the cells themselves: ix outer, iy inner, push order inside a cell, both coordinates strictly inside r"""
+        out = []
+        for ix in range(win[0], win[1] + 1):
+            for iy in range(win[2], win[3] + 1):
+                for i in self.cells[ix * GRID_ROWS + iy]:
+                    if abs(f32(self.kps[i][0]) - f32(u)) < f32(r) and abs(f32(self.kps[i][1]) - f32(v)) < f32(r):
+                        out.append(i)
+        return out
+
+
+def visit_by_brute_force(g, u, v, r, win):
+    """What the visit may read of tables that need not be a grid at all: only slots below nIn (the grid's total, cut to the frame's count, cut to
+    the capacity), for every column those between its two offsets AS THEY STAND (a decreasing pair holds none), every index pulled into the frame."""
+    n = max(0, min(g.n_out, g.capacity))
+    n_in = max(0, min(g.off[GRID_CELLS], n))
+    seen = []
+    for ix in range(win[0], win[1] + 1):
+        if win[2] > win[3]:
+            break
+        for s in range(n_in):
+            if g.off[ix * GRID_ROWS + win[2]] <= s < g.off[ix * GRID_ROWS + win[3] + 1]:
+                i = min(max(g.gi[s], 0), g.capacity - 1)
+                x, y = (g.kps[i][:2] if i < len(g.kps) else (0.0, 0.0))
+                if abs(f32(x) - f32(u)) < f32(r) and abs(f32(y) - f32(v)) < f32(r):
+                    seen += [s, i]
+    return [int(bool(seen)), n_in, len(seen) // 2] + seen
+
+
+VISIT_KEYPOINTS = [(205.0, 33.0, 0), (57.5, 71.0, 1), (228.0, 38.0, 2), (52.0, 78.0, 0), (100.0, 100.0, 3), (108.0, 100.0, 1),      # 5: exactly r = 8 right of 4
+                   (107.5, 92.5, 0), (100.0, 92.0, 2), (201.0, 36.0, 1), (224.0, 31.0, 0), (635.0, 475.0, 4), (3.0, 2.0, 0)]       # 7: exactly r above 4
+WHOLE = (0, GRID_COLS - 1, 0, GRID_ROWS - 1)
+
+
+def visit_line(g, u, v, r, win, frames=2, f=1):
+    """frame f of `frames` is g; the others are empty keyframes whose tables say so"""
+    n_out, off, gi, kps = [], [], [], []
+    for k in range(frames):
+        n_out.append(g.n_out if k == f else 0)
+        off += g.off if k == f else [0] * (GRID_CELLS + 1)
+        gi += g.gi if k == f else [0] * g.capacity
+        mine = g.kps + [(0.0, 0.0, 0)] * (g.capacity - len(g.kps))
+        kps += mine if k == f else [(0.0, 0.0, 0)] * g.capacity
+    assert len(gi) == frames * g.capacity and len(off) == frames * (GRID_CELLS + 1)
+    return "V %d %d %d %s %s %s %s %s %s %s 0 %d %d %d %d" % (frames, f, g.capacity, " ".join(map(str, n_out)), " ".join(map(str, off)), " ".join(map(str, gi)),
+                                                              " ".join("%s %s %d" % (hexf(x), hexf(y), o) for x, y, o in kps), hexf(u), hexf(v), hexf(r), *win)
+
+
+def test_keyframe_visit(ask):
+    cap = len(VISIT_KEYPOINTS)
+    good = Grid(VISIT_KEYPOINTS, cap)
+    cases = {}
+    cases["one cell"] = (good, 55.0, 75.0, 30.0, (5, 5, 7, 7))
+    cases["one empty cell"] = (good, 305.0, 205.0, 30.0, (30, 30, 20, 20))
+    cases["all cells"] = (good, 320.0, 240.0, 1000.0, WHOLE)
+    cases["all cells, small radius"] = (good, 104.0, 96.0, 6.0, WHOLE)
+    cases["minCY above maxCY"] = (good, 55.0, 75.0, 30.0, (5, 5, 9, 6))
+    cases["minCX above maxCX"] = (good, 55.0, 75.0, 30.0, (6, 5, 7, 7))
+    cases["empty column between two full"] = (good, 215.0, 35.0, 30.0, (20, 22, 3, 3))
+    cases["exactly r away"] = (good, 100.0, 100.0, 8.0, (9, 11, 8, 11))
+    cases["one float above r"] = (good, 100.0, 100.0, float(np.nextafter(f32(8.0), f32(9.0))), (9, 11, 8, 11))
+    corrupt = {}
+    for name, n_out in (("nOut above capacity", cap + 5), ("nOut below 0", -3), ("nOut below the grid's total", 8)):
+        g = Grid(VISIT_KEYPOINTS, cap)
+        g.n_out = n_out
+        corrupt[name] = (g, 320.0, 240.0, 1000.0, WHOLE)
+    g = Grid(VISIT_KEYPOINTS[:8], 8)                     # the offsets speak of 20 slots, the tables have 8
+    g.off = [o + 12 * (c > 600) for c, o in enumerate(g.off)]
+    corrupt["total above N"] = (g, 320.0, 240.0, 1000.0, WHOLE)
+    g = Grid(VISIT_KEYPOINTS, cap)
+    g.off = [o + 100000 for o in g.off]
+    corrupt["every offset far above N"] = (g, 320.0, 240.0, 1000.0, WHOLE)
+    g = Grid(VISIT_KEYPOINTS, cap)
+    g.off = [-o for o in g.off]
+    g.off[GRID_CELLS] = cap
+    corrupt["negative offsets"] = (g, 320.0, 240.0, 1000.0, WHOLE)
+    g = Grid(VISIT_KEYPOINTS, cap)
+    g.off = [cap - o for o in g.off[:GRID_CELLS]] + [cap]      # decreasing throughout: only a window turned round finds a range (slots 9 .. 10) in it
+    corrupt["minCY above maxCY, offsets decreasing"] = (g, 320.0, 240.0, 1000.0, (5, 5, 9, 6))
+    g = Grid(VISIT_KEYPOINTS, cap)
+    g.off[20 * GRID_ROWS + 3],g.off[20 * GRID_ROWS + 4] = g.off[20 * GRID_ROWS + 4], g.off[20 * GRID_ROWS + 3]      # column 20's cell: 2 slots, backwards
+    corrupt["decreasing pair"] = (g, 215.0, 35.0, 30.0, (20, 22, 3, 3))
+    for name, bad in (("gi of -1", -1), ("gi of capacity", cap), ("gi far outside", 1 << 30)):
+        g = Grid(VISIT_KEYPOINTS, cap)
+        g.gi[g.off[10 * GRID_ROWS + 10]] = bad           # the slot of keypoint 4
+        corrupt[name] = (g, 320.0, 240.0, 1000.0, WHOLE)
+    got = ask([visit_line(*c) for c in list(cases.values()) + list(corrupt.values())])
+    for (name, c), out in zip(list(cases.items()) + list(corrupt.items()), got):
+        assert out == visit_by_brute_force(*c), name
+    # on a grid that is one, the brute force is GetFeaturesInArea itself
+    for name, (g, u, v, r, win) in cases.items():
+        want = g.features_in_area(u, v, r, win)
+        assert visit_by_brute_force(g, u, v, r, win)[4::2] == want and visit_by_brute_force(g, u, v, r, win)[0] == int(bool(want)), name
+    answer = dict(zip(list(cases) + list(corrupt), got))
+    assert answer["one cell"][3:] == [good.off[5 * GRID_ROWS + 7], 1, good.off[5 * GRID_ROWS + 7] + 1, 3]
+    assert answer["one empty cell"] == [0, cap, 0] and answer["minCY above maxCY"] == [0, cap, 0] and answer["minCX above maxCX"] == [0, cap, 0]
+    assert answer["all cells"][4::2] == [11, 1, 3, 6, 7, 4, 5, 0, 8, 2, 9, 10]                   # column by column, rows inside (6, 7 lie above 4, 5), push order in a cell
+    assert answer["empty column between two full"][4::2] == [0, 8, 2, 9]
+    assert answer["exactly r away"][4::2] == [6, 4] and answer["one float above r"][4::2] == [6, 7, 4, 5]      # 5 and 7 are exactly 8 px from (100, 100)
+    assert answer["nOut above capacity"] == answer["all cells"] and answer["nOut below 0"] == [0, 0, 0]
+    assert answer["nOut below the grid's total"][1:3] == [8, 8] and answer["total above N"][1:3] == [8, 8]
+    assert answer["every offset far above N"] == [0, cap, 0] and answer["decreasing pair"][4::2] == [2, 9]
+    assert answer["minCY above maxCY, offsets decreasing"] == [0, cap, 0]
+    assert answer["gi of -1"][4::2].count(0) == 2 and 4 not in answer["gi of -1"][4::2]
+    assert answer["gi of capacity"][4::2].count(cap - 1) == 2 and answer["gi far outside"] == answer["gi of capacity"]
+    # a second copy of the same keyframe in frame 0 of one: the frame index only moves the pointers
+    assert ask([visit_line(*cases["all cells"], frames=1, f=0)])[0] == answer["all cells"]
