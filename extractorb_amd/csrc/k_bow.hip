@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_wave_min.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
@@ -178,10 +179,12 @@ __global__ __launch_bounds__(kReduceThreads) void k_bow_reduce(const uint32_t* _
 
 void launchBow(hipStream_t st, const VocabDevice& V, const uint8_t* desc, const int* nOut, int capacity, int levelsUp, uint32_t* featWord,
                double* featWeight, uint32_t* featNode, uint32_t* wordIds, double* wordWeights, int* nWords, uint32_t* fvNodes, uint32_t* fvIdx,
-               int* nFeat, int B) {
+               int* nFeat, int B, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_bow_words, dim3((capacity + 15) / 16, B), dim3(256), 0, st, V, desc, nOut, capacity, levelsUp, featWord, featWeight, featNode);
     int P = 64;                       // the kernel never sorts fewer than 64 keys: the LDS block and the wsum offset follow the same minimum
     while (P < capacity) P <<= 1;
+    pollute(st);
     hipLaunchKernelGGL(k_bow_reduce, dim3(B), dim3(kReduceThreads), (size_t)P * (P <= 8192 ? 16 : 8), st, featWord, featWeight, featNode, nOut, capacity, P, V.scoring, V.weighting,
                        wordIds, wordWeights, nWords, fvNodes, fvIdx, nFeat);
 }

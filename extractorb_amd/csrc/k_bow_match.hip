@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_match_helpers.hpp"
 #include "k_wave_min.hpp"
 #include "orbx_device.hpp"
@@ -65,8 +66,9 @@ __global__ __launch_bounds__(kThreads) void k_search_bow(const uint32_t* __restr
     for (int i = tid; i < MC; i += kThreads) { nodeC[i] = gNodeC[i]; sIdxC[i] = (unsigned short)min(idxC[i], (uint32_t)(cap - 1)); }
     // (the second keyframe's keypoints without a good MapPoint are never candidates (:879-886): closed from the start, marked -2)
     for (int i = tid; i < cap; i += kThreads) {
-        takenBy[i] = p.twoKeyFrames && !(curFlags[(long long)pair * cap + i] & 1) ? -2 : -1;
-        binOf[i] = 255; sFlag[i] = flags[i];
+        // (an index at or above its frame's count names no feature: closed as a candidate, without a MapPoint as a key)
+        takenBy[i] = i >= NC || (p.twoKeyFrames && !(curFlags[(long long)pair * cap + i] & 1)) ? -2 : -1;
+        binOf[i] = 255; sFlag[i] = i < NK ? flags[i] : (uint8_t)0;
     }
     if constexpr (STAGE) {
         for (int i = tid; i < 2 * NK; i += kThreads) sDescK[i] = ((const uint4*)descK)[i];
@@ -154,7 +156,9 @@ __global__ __launch_bounds__(kThreads) void k_search_bow(const uint32_t* __restr
 }
 
 void launchSearchBow(hipStream_t st, const uint32_t* featNodes, const uint32_t* featIdx, const int* nFeat, const uint8_t* kfFlags,
-                     const uint8_t* curFlags, const Keypoint* kps, const uint8_t* desc, const int* nOut, const BowMatchParams& p, int* matches, int* nMatches, int nPairs) {
+                     const uint8_t* curFlags, const Keypoint* kps, const uint8_t* desc, const int* nOut, const BowMatchParams& p, int* matches,
+                     int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     if (bowMatchLdsBytes(p.capacity, true) <= 150 * 1024)
         hipLaunchKernelGGL(k_search_bow<true>, dim3(nPairs), dim3(kThreads), bowMatchLdsBytes(p.capacity, true), st, featNodes, featIdx, nFeat, kfFlags,
                            curFlags, kps, desc, nOut, p, matches, nMatches);

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_match_helpers.hpp"
 #include "k_wave_min.hpp"
 #include "orbx_device.hpp"
@@ -87,8 +88,9 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
     }
     for (int i = tid; i < 2 * capA; i += kThreads) {
         const int e = i >= capA, j = i - e * capA;
-        takenBy[i] = -1; binOf[i] = 255;
-        sFlag[i] = j < cap ? kfFlags[(2LL * pair + e) * cap + j] : (uint8_t)0;
+        // (an index at or above its eye's count names no feature: closed as a candidate, without a MapPoint as a key)
+        takenBy[i] = j < N[2 + e] ? -1 : -2; binOf[i] = 255;
+        sFlag[i] = j < N[e] ? kfFlags[(2LL * pair + e) * cap + j] : (uint8_t)0;
     }
     if constexpr (STAGE) {
 #pragma unroll
@@ -195,7 +197,8 @@ __global__ __launch_bounds__(kThreads) void k_search_bow_two_eyes(const uint32_t
 
 void launchSearchBowTwoEyes(hipStream_t st, const uint32_t* featNodes, const uint32_t* featIdx, const int* nFeat, const uint8_t* kfFlags,
                             const Keypoint* kps, const uint8_t* desc, const int* nOut, const BowTwoEyesParams& p, bool stage, int* matches,
-                            int* nMatches, int nPairs) {
+                            int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     if (stage)
         hipLaunchKernelGGL(k_search_bow_two_eyes<true>, dim3(nPairs), dim3(kThreads), bowTwoEyesLdsBytes(p.capacity, true), st, featNodes, featIdx,
                            nFeat, kfFlags, kps, desc, nOut, p, matches, nMatches);

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_covisibility.hpp"
 
 namespace orbx {
@@ -40,12 +41,15 @@ __global__ __launch_bounds__(kCvThreads) void k_keyframe_redundancy(CovisArrays 
     rdKeyFrame(threadIdx.x, blockIdx.x, a, p, lds);
 }
 
-void launchCovisibility(hipStream_t st, const CovisArrays& a, const CovisParams& p) {
+void launchCovisibility(hipStream_t st, const CovisArrays& a, const CovisParams& p, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_covis_rank, dim3((unsigned)cvRankBlocks(p.nFrames)), dim3(64 * kCvRankBlock), 0, st, a, p);
+    pollute(st);
     hipLaunchKernelGGL(k_covis_vote, dim3((unsigned)p.nSubjects), dim3(kCvThreads), cvVoteLdsBytes(p.nFrames), st, a, p);
 }
 
-void launchKeyFrameRedundancy(hipStream_t st, const CovisArrays& a, const CovisParams& p) {
+void launchKeyFrameRedundancy(hipStream_t st, const CovisArrays& a, const CovisParams& p, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_keyframe_redundancy, dim3((unsigned)p.nSubjects), dim3(kCvThreads), rdLdsBytes(p.capacity), st, a, p);
 }
 

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
 
@@ -131,14 +132,16 @@ __global__ __launch_bounds__(256) void k_stereo_from_rgbd(const Keypoint* __rest
     depthOut[(long long)f * p.capacity + i] = dz;
 }
 void launchStereoFromRgbd(hipStream_t st, const Keypoint* kps, const Keypoint* kpsUn, const int* nOut, const uint8_t* depth,
-                          const RgbdParams& p, float* uRight, float* depthOut, int nFrames) {
+                          const RgbdParams& p, float* uRight, float* depthOut, int nFrames, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((p.capacity + 255) / 256, nFrames), dim3(256), 0, st, kps, kpsUn, nOut, depth, p,
                        uRight, depthOut);
 }
 
 void launchFrameFinish(hipStream_t st, const Keypoint* kps, const int* nOut, const FrameFinishParams& p, Keypoint* kpsUn,
-                       int* gridOff, int* gridIdx, int* nInside, int nFrames) {
+                       int* gridOff, int* gridIdx, int* nInside, int nFrames, LdsPolluter pollute) {
     const size_t lds = (size_t)(kGridCells + 4) * sizeof(int) + (size_t)((p.capacity + 7) & ~7) * sizeof(short);
+    pollute(st);
     hipLaunchKernelGGL(k_frame_finish, dim3(nFrames), dim3(1024), lds, st, kps, nOut, p, kpsUn, gridOff, gridIdx, nInside);
 }
 

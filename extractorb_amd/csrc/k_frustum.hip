@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_frustum_point.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
@@ -108,7 +109,8 @@ __global__ __launch_bounds__(kThreads) void k_frustum(const float* __restrict__ 
 
 void launchFrustum(hipStream_t st, const float* mpWorld, const float* mpNormal, const float* mpDist, const uint8_t* mpDesc, const float* mpAngle,
                    const int* nMp, const uint8_t* mpFlags, const float* poses, const FrustumParams& p, ProjQuery* queries, uint8_t* queryDesc,
-                   int* querySrc, int* nQueries, TrackRecord* track, int* nInView, int nPairs) {
+                   int* querySrc, int* nQueries, TrackRecord* track, int* nInView, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_frustum, dim3(nPairs), dim3(kThreads), 0, st, mpWorld, mpNormal, mpDist, mpDesc, mpAngle, nMp, mpFlags, poses, p, queries,
                        queryDesc, querySrc, nQueries, track, nInView);
 }

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_frustum_two_eyes_point.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
@@ -151,9 +152,11 @@ __global__ __launch_bounds__(kThreads) void k_frustum_two_eyes_place(const uint8
 void launchFrustumTwoEyes(hipStream_t st, const float* mpWorld, const float* mpNormal, const float* mpDist, const uint8_t* mpDesc, const int* nMp,
                           const uint8_t* mpFlags, const float* prevDepth, const float* poses, const FrustumTwoEyesParams& p, int* counts,
                           ProjQuery* queries, uint8_t* queryDesc, int* querySrc, int* nQueries, int* nWanted, TrackRecord* track, int* nInView,
-                          int nPairs) {
+                          int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_frustum_two_eyes_check, dim3(p.groups, nPairs), dim3(kThreads), 0, st, mpWorld, mpNormal, mpDist, nMp, mpFlags, prevDepth,
                        poses, p, track, counts);
+    pollute(st);
     hipLaunchKernelGGL(k_frustum_two_eyes_place, dim3(p.groups, nPairs), dim3(kThreads), 0, st, mpDesc, mpFlags, (const TrackRecord*)track,
                        (const int*)counts, p, queries, queryDesc, querySrc, nQueries, nWanted, nInView);
 }

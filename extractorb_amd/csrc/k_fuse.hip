@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_keyframe_project.hpp"
 #include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
@@ -69,7 +70,8 @@ __global__ __launch_bounds__(256) void k_fuse(const float* __restrict__ mpWorld,
 void launchFuse(hipStream_t st, const float* mpWorld, const float* mpNormal, const float* mpDist, const uint8_t* mpDesc, const int* nMp,
                 const uint8_t* mpFlags, const float* poses, const Keypoint* kpsUn, const float* uRight, const uint8_t* desc, const int* nOut,
                 const int* gridOff, const int* gridIdx, const FuseParams& p, int* bestIdx, int* bestDist, uint8_t* exitCode, int* nFused,
-                int nPairs) {
+                int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_fuse, dim3((p.mpCapacity + 255) / 256, nPairs), dim3(256), 0, st, mpWorld, mpNormal, mpDist, mpDesc, nMp, mpFlags, poses,
                        kpsUn, uRight, desc, nOut, gridOff, gridIdx, p, bestIdx, bestDist, exitCode, nFused);
 }

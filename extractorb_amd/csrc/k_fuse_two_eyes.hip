@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_camera_kb8.hpp"
 #include "k_keyframe_project.hpp"
 #include "k_match_helpers.hpp"
@@ -133,7 +134,8 @@ int fuseTwoEyesGroups(int mpCapacity, int eyes) {
 
 void launchFuseTwoEyes(hipStream_t st, const float* mpWorld, const float* mpNormal, const float* mpDist, const uint8_t* mpDesc, const int* nMp,
                        const uint8_t* mpFlags, const float* poses, const Keypoint* kps, const uint8_t* desc, const int* nOut, const int* gridOff,
-                       const int* gridIdx, const FuseTwoEyesParams& p, int* bestIdx, int* bestDist, uint8_t* exitCode, int* nFused, int nPairs) {
+                       const int* gridIdx, const FuseTwoEyesParams& p, int* bestIdx, int* bestDist, uint8_t* exitCode, int* nFused, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_fuse_two_eyes, dim3(fuseTwoEyesGroups(p.mpCapacity, p.eyes), nPairs), dim3(kFuse2Threads), 0, st, mpWorld, mpNormal, mpDist,
                        mpDesc, nMp, mpFlags, poses, kps, desc, nOut, gridOff, gridIdx, p, bestIdx, bestDist, exitCode, nFused);
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "orbx_params.hpp"
 
 namespace orbx {
@@ -60,7 +61,8 @@ __global__ __launch_bounds__(256) void k_gray(const uint8_t* __restrict__ src, u
     }
 }
 
-void launchGray(hipStream_t st, const uint8_t* src, uint8_t* dst, const GrayParams& p, int nFrames) {
+void launchGray(hipStream_t st, const uint8_t* src, uint8_t* dst, const GrayParams& p, int nFrames, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_gray, dim3((p.cols / 4 + 256) / 256, p.rows, nFrames), dim3(256), 0, st, src, dst, p);
 }
 

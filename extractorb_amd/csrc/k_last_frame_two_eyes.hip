@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_camera_kb8.hpp"
 #include "k_match_helpers.hpp"
 #include "k_project_last_two_eyes_point.hpp"
@@ -247,20 +248,23 @@ __global__ __launch_bounds__(kThreads) void k_search_last_two_eyes(const ProjQue
     if (tid == 0) nMatches[pair] = flags[2] - droppedCount;
 }
 
-void launchKb8Project(hipStream_t st, const float* xyz, const float* cam8, int n, float* uv) {
+void launchKb8Project(hipStream_t st, const float* xyz, const float* cam8, int n, float* uv, LdsPolluter pollute) {
     Kb8Cam c;
     for (int i = 0; i < 8; i++) c.k[i] = cam8[i];
+    pollute(st);
     hipLaunchKernelGGL(k_kb8_project, dim3((n + 255) / 256), dim3(256), 0, st, xyz, c, n, uv);
 }
 
 void launchProjectLastTwoEyes(hipStream_t st, const Keypoint* kps, const int* nOut, const uint8_t* mpFlags, const float* world,
-                              const float* poses, const ProjectTwoEyesParams& p, ProjQuery* queries, int nPairs) {
+                              const float* poses, const ProjectTwoEyesParams& p, ProjQuery* queries, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_project_last_two_eyes, dim3((2 * p.capacity + 255) / 256, nPairs), dim3(256), 0, st, kps, nOut, mpFlags, world, poses, p, queries);
 }
 
 void launchSearchLastTwoEyes(hipStream_t st, const ProjQuery* queries, const uint8_t* qdesc, const Keypoint* kps, const uint8_t* desc,
                              const int* nOut, const int* gridOff, const int* gridIdx, uint8_t* occupied, const LastTwoEyesSearchParams& p,
-                             int* matches, int* nMatches, int nPairs) {
+                             int* matches, int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_search_last_two_eyes, dim3(nPairs), dim3(kThreads), lastTwoEyesLdsBytes(p.capacity), st, queries, qdesc, kps, desc, nOut,
                        gridOff, gridIdx, occupied, p, matches, nMatches);
 }

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_map_point_update.hpp"
 #include "k_wave_min.hpp"
 
@@ -248,8 +249,9 @@ __global__ __launch_bounds__(kMpuThreads) void k_map_point_update(MapPointUpdate
     }
 }
 
-void launchMapPointUpdate(hipStream_t st, bool twoEyes, const MapPointUpdateArrays& a, const MapPointUpdateParams& p) {
+void launchMapPointUpdate(hipStream_t st, bool twoEyes, const MapPointUpdateArrays& a, const MapPointUpdateParams& p, LdsPolluter pollute) {
     const dim3 grid((unsigned)((p.nPoints + kMpuPoints - 1) / kMpuPoints));
+    pollute(st);
     if (twoEyes) hipLaunchKernelGGL(k_map_point_update<true>, grid, dim3(kMpuThreads), 0, st, a, p);
     else hipLaunchKernelGGL(k_map_point_update<false>, grid, dim3(kMpuThreads), 0, st, a, p);
 }

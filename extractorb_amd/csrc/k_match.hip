@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
@@ -241,7 +242,8 @@ __global__ __launch_bounds__(kThreads) void k_search_init(const Keypoint* __rest
 }
 
 void launchSearchInit(hipStream_t st, const Keypoint* kpsUn, const uint8_t* desc, const int* nOut, const int* gridOff,
-                      const int* gridIdx, const InitMatchParams& p, float* prevMatched, int* matches12, int* nMatches, int nPairs) {
+                      const int* gridIdx, const InitMatchParams& p, float* prevMatched, int* matches12, int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_search_init, dim3(nPairs), dim3(kThreads), initMatchLdsBytes(p.capacity, p.slotCapacity), st, kpsUn, desc, nOut, gridOff,
                        gridIdx, p, prevMatched, matches12, nMatches);
 }

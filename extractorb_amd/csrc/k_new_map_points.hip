@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_new_map_points.hpp"
 
 namespace orbx {
@@ -71,14 +72,16 @@ int newMapPointsTiles(int listCapacity) { return (listCapacity + kNmpThreads - 1
 
 void launchNewMapPoints(hipStream_t st, bool twoEyes, const int* pairs, const int* nMatches, const float* poses, const Keypoint* kps,
                         const Keypoint* raw, const float* uRight, const float* depth, const int* nOut, const NewMapPointsParams& params,
-                        uint8_t* exitOut, float* x3dOut, int* nNew, uint8_t* mark1, uint8_t* mark2, int nPairs) {
+                        uint8_t* exitOut, float* x3dOut, int* nNew, uint8_t* mark1, uint8_t* mark2, int nPairs, LdsPolluter pollute) {
     NewMapPointsParams p = params;
     p.tiles = newMapPointsTiles(p.listCapacity);
     p.countStats = g_newMapPointsStatsOn ? 1 : 0;
     void* stats = nullptr;
     if (p.countStats && hipGetSymbolAddress(&stats, HIP_SYMBOL(g_newMapPointsStats)) == hipSuccess) (void)hipMemsetAsync(stats, 0, sizeof(int) * 2, st);
+    pollute(st);
     hipLaunchKernelGGL(k_new_map_points_init, dim3((unsigned)((nPairs + 255) / 256)), dim3(256), 0, st, nNew, nPairs);
     const dim3 grid((unsigned)(nPairs * p.tiles));
+    pollute(st);
     if (twoEyes)
         hipLaunchKernelGGL(k_new_map_points<true>, grid, dim3(kNmpThreads), 0, st, pairs, nMatches, poses, kps, raw, uRight, depth, nOut, p, exitOut,
                            x3dOut, nNew, mark1, mark2);

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_place_recognition.hpp"
 
 namespace orbx {
@@ -49,10 +50,13 @@ __global__ __launch_bounds__(kPrThreads) void k_place_query(PlaceArrays a, Place
     prQuery(threadIdx.x, blockIdx.x, a, p, lds);
 }
 
-void launchPlaceRecognition(hipStream_t st, const PlaceArrays& a, const PlaceParams& p) {
-    if (p.nDb > 0)
+void launchPlaceRecognition(hipStream_t st, const PlaceArrays& a, const PlaceParams& p, LdsPolluter pollute) {
+    if (p.nDb > 0) {
+        pollute(st);
         hipLaunchKernelGGL(k_place_pairs, dim3((unsigned)((p.nDb + p.pairRows - 1) / p.pairRows), (unsigned)p.nQueries), dim3(kPrThreads),
                            prPairLdsBytes(p.qCapacity), st, a, p);
+    }
+    pollute(st);
     hipLaunchKernelGGL(k_place_query, dim3((unsigned)p.nQueries), dim3(kPrThreads), prQueryLdsBytes(p.nDb), st, a, p);
 }
 

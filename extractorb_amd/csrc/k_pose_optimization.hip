@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_pose_optimization.hpp"
 
 namespace orbx {
@@ -40,7 +41,8 @@ __global__ __launch_bounds__(kPoSlots) void k_pose_optimization(const PoseProble
 }
 
 void launchPoseOptimization(hipStream_t st, const void* problems, const Keypoint* kps, const int* nOut, const float* uRight, const int* matches,
-                            const float* world, const PoseOptParams& q, float* poses, uint8_t* outlier, void* result, int nProblems) {
+                            const float* world, const PoseOptParams& q, float* poses, uint8_t* outlier, void* result, int nProblems, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_pose_optimization, dim3((unsigned)nProblems), dim3(kPoSlots), 0, st, (const PoseProblem*)problems, kps, nOut, uRight, matches,
                        world, q, poses, outlier, (PoseResult*)result);
 }

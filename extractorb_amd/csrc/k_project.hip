@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_match_helpers.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
@@ -298,14 +299,16 @@ __global__ __launch_bounds__(kThreads) void k_search_proj(const ProjQuery* __res
 }
 
 void launchProjectLast(hipStream_t st, const Keypoint* kps, const Keypoint* kpsUn, const int* nOut, const uint8_t* mpFlags,
-                       const float* world, const float* poses, const ProjectParams& p, ProjQuery* queries, int nPairs) {
+                       const float* world, const float* poses, const ProjectParams& p, ProjQuery* queries, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_project_last, dim3((p.capacity + 255) / 256, nPairs), dim3(256), 0, st, kps, kpsUn, nOut, mpFlags, world, poses, p, queries);
 }
 
 void launchSearchProj(hipStream_t st, const ProjQuery* queries, const uint8_t* qdesc, const int* nQueries, const Keypoint* kpsUn,
                       const uint8_t* desc, const int* nOut, const int* gridOff, const int* gridIdx, const float* uRight,
-                      uint8_t* occupied, const ProjSearchParams& p, int* matches, int* nMatches, int nPairs) {
+                      uint8_t* occupied, const ProjSearchParams& p, int* matches, int* nMatches, int nPairs, LdsPolluter pollute) {
     // the best-key lists ride in LDS when they fit (640x480 x 1000 features: 103 KB); otherwise every round re-scans the windows
+    pollute(st);
     if (projSearchLdsBytes(p.capacity, p.queryCapacity, true) <= 160 * 1024 - 512)
         hipLaunchKernelGGL(k_search_proj<true>, dim3(nPairs), dim3(kThreads), projSearchLdsBytes(p.capacity, p.queryCapacity, true), st, queries, qdesc,
                            nQueries, kpsUn, desc, nOut, gridOff, gridIdx, uRight, occupied, p, matches, nMatches);

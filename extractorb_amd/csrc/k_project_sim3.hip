@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_keyframe_project.hpp"
 #include "k_sim3_decide.hpp"
 #include "k_match_helpers.hpp"
@@ -232,9 +233,11 @@ __global__ __launch_bounds__(kSettleThreads) void k_sim3_settle(const uint8_t* _
 void launchSim3Search(hipStream_t st, const float* mpWorld, const float* mpNormal, const float* mpDist, const uint8_t* mpDesc, const int* nMp,
                       const uint8_t* mpFlags, const float* poses, const Keypoint* kpsUn, const uint8_t* desc, const int* nOut, const int* gridOff,
                       const int* gridIdx, const uint8_t* occupied, const Sim3SearchParams& p, void* rec, int* matches,
-                      int* matchIdx, int* matchDist, uint8_t* exitCode, int* nMatches, int nPairs) {
+                      int* matchIdx, int* matchDist, uint8_t* exitCode, int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_sim3_window, dim3((p.mpCapacity + 255) / 256, nPairs), dim3(256), 0, st, mpWorld, mpNormal, mpDist, mpDesc, nMp, mpFlags,
                        poses, kpsUn, desc, nOut, gridOff, gridIdx, occupied, p, (Sim3Record*)rec, exitCode);
+    pollute(st);
     hipLaunchKernelGGL(k_sim3_settle, dim3(nPairs), dim3(kSettleThreads), sim3SettleLdsBytes(p.capacity, p.mpCapacity), st, mpDesc, kpsUn, desc,
                        nOut, gridOff, gridIdx, occupied, p, (const Sim3Record*)rec, matches, matchIdx, matchDist, exitCode,
                        nMatches);

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_match_helpers.hpp"
 #include "k_wave_min.hpp"
 #include "orbx_device.hpp"
@@ -302,7 +303,8 @@ __global__ __launch_bounds__(kThreads) void k_search_proj_two_eyes(const ProjQue
 
 void launchSearchProjTwoEyes(hipStream_t st, const ProjQuery* queries, const uint8_t* qdesc, const int* nQueries, const Keypoint* kps,
                              const uint8_t* desc, const int* nOut, const int* gridOff, const int* gridIdx, const int* leftToRight,
-                             const int* rightToLeft, uint8_t* occupied, const TwoEyesSearchParams& p, int* matches, int* nMatches, int nPairs) {
+                             const int* rightToLeft, uint8_t* occupied, const TwoEyesSearchParams& p, int* matches, int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_search_proj_two_eyes, dim3(nPairs), dim3(kThreads), twoEyesSearchLdsBytes(p.capacity, p.queryCapacity), st, queries, qdesc,
                        nQueries, kps, desc, nOut, gridOff, gridIdx, leftToRight, rightToLeft, occupied, p, matches, nMatches);
 }

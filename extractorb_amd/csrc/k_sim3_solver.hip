@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_sim3_solver.hpp"
 
 namespace orbx {
@@ -39,12 +40,12 @@ __global__ __launch_bounds__(kSsLanes) void k_sim3_decide(const Sim3Problem* __r
 }
 
 void launchSim3Solve(hipStream_t st, const void* problems, const float* x1w, const float* x2w, const int* oct1, const int* oct2, const int* rnd,
-                     const Sim3SolveParams& q, const SsWork& w, void* result, uint8_t* flags, int nProblems, int steps) {
+                     const Sim3SolveParams& q, const SsWork& w, void* result, uint8_t* flags, int nProblems, int steps, LdsPolluter pollute) {
     const Sim3Problem* pb = (const Sim3Problem*)problems;
     // steps: bit 0 prepare, bit 1 hypotheses, bit 2 decide (orbx_debug_sim3_solve_steps; a call takes all three)
-    if (steps & 1) hipLaunchKernelGGL(k_sim3_prepare, dim3((unsigned)nProblems), dim3(kSsLanes), 0, st, pb, x1w, x2w, oct1, oct2, q, w, (Sim3Result*)result, flags);
-    if (steps & 2) hipLaunchKernelGGL(k_sim3_hypotheses, dim3((unsigned)((long long)nProblems * q.maxIterations)), dim3(kSsLanes), 0, st, pb, rnd, q, w);
-    if (steps & 4) hipLaunchKernelGGL(k_sim3_decide, dim3((unsigned)nProblems), dim3(kSsLanes), 0, st, pb, rnd, q, w, (Sim3Result*)result, flags);
+    if (steps & 1) { pollute(st); hipLaunchKernelGGL(k_sim3_prepare, dim3((unsigned)nProblems), dim3(kSsLanes), 0, st, pb, x1w, x2w, oct1, oct2, q, w, (Sim3Result*)result, flags); }
+    if (steps & 2) { pollute(st); hipLaunchKernelGGL(k_sim3_hypotheses, dim3((unsigned)((long long)nProblems * q.maxIterations)), dim3(kSsLanes), 0, st, pb, rnd, q, w); }
+    if (steps & 4) { pollute(st); hipLaunchKernelGGL(k_sim3_decide, dim3((unsigned)nProblems), dim3(kSsLanes), 0, st, pb, rnd, q, w, (Sim3Result*)result, flags); }
 }
 
 }  // namespace orbx

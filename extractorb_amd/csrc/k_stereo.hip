@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_wave_min.hpp"
 #include "orbx_device.hpp"
 #include "orbx_params.hpp"
@@ -291,11 +292,14 @@ __global__ __launch_bounds__(1024) void k_stereo_filter(const int* __restrict__ 
 
 void launchStereo(hipStream_t st, const LevelGeom* lv, const uint8_t* pyr, const Keypoint* kps, const uint8_t* desc,
                   const int* nOut, const StereoParams& sp, int rows, int* rowOff, unsigned short* rowList, float* uRight,
-                  float* depth, int* sadDist, int* nMatched, int nPairs) {
+                  float* depth, int* sadDist, int* nMatched, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_stereo_rows, dim3(nPairs), dim3(1024), (size_t)(rows + 1) * sizeof(int), st, kps, nOut, sp, rows,
                        rowOff, rowList);
+    pollute(st);
     hipLaunchKernelGGL(k_stereo_match, dim3((sp.capacity + 3) / 4, nPairs), dim3(256), 0, st, lv, pyr, kps, desc, nOut, sp,
                        rows, rowOff, rowList, uRight, depth, sadDist);
+    pollute(st);
     hipLaunchKernelGGL(k_stereo_filter, dim3(nPairs), dim3(1024), (size_t)((sp.capacity + 3) & ~3) * sizeof(int), st, nOut, sp, uRight,
                        depth, sadDist, nMatched);
 }

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_camera_kb8_unproject.hpp"
 #include "k_lds_vec.hpp"
 #include "k_match_helpers.hpp"
@@ -193,14 +194,16 @@ int stereoFisheyeTiles(int capacity) { return (capacity + kSfThreads - 1) / kSfT
 
 void launchStereoFisheye(hipStream_t st, const Keypoint* kps, const uint8_t* desc, const int* nOut, const int* monoOut,
                          const StereoFisheyeParams& params, int* l2r, int* r2l, float* depth, float* x3d, int* nMatches, int* nDescMatches,
-                         int nRigs) {
+                         int nRigs, LdsPolluter pollute) {
     StereoFisheyeParams p = params;
     p.tiles = stereoFisheyeTiles(p.capacity);
     p.countStats = g_stereoFisheyeStatsOn ? 1 : 0;
     void* stats = nullptr;
     if (p.countStats && hipGetSymbolAddress(&stats, HIP_SYMBOL(g_stereoFisheyeStats)) == hipSuccess) (void)hipMemsetAsync(stats, 0, sizeof(int), st);
     const int groups = (p.capacity + 255) / 256;
+    pollute(st);
     hipLaunchKernelGGL(k_stereo_fisheye_init, dim3((unsigned)(nRigs * groups)), dim3(256), 0, st, p, groups, r2l, nMatches, nDescMatches);
+    pollute(st);
     hipLaunchKernelGGL(k_stereo_fisheye, dim3((unsigned)(nRigs * p.tiles)), dim3(kSfThreads), 0, st, kps, desc, nOut, monoOut, p, l2r, r2l, depth,
                        x3d, nMatches, nDescMatches);
 }

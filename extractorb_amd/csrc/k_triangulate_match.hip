@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_match_helpers.hpp"
 #include "k_wave_min.hpp"
 #include "orbx_device.hpp"
@@ -91,10 +92,10 @@ __global__ __launch_bounds__(kThreads) void k_search_triangulation(const uint32_
     for (int i = tid; i < M1; i += kThreads) { segK[i] = gNode1[i]; idxK[i] = (unsigned short)min(gIdx1[i], (uint32_t)(cap - 1)); }
     for (int i = tid; i < M2; i += kThreads) { nodeC[i] = gNode2[i]; idxC[i] = (unsigned short)min(gIdx2[i], (uint32_t)(cap - 1)); }
     for (int i = tid; i < capA; i += kThreads) {
-        const bool in = i < cap;
         m12[i] = -1; binOf[i] = 255;
-        flag1[i] = in ? (uint8_t)((mpFlags1[(long long)pair * cap + i] & 1) | (uRight && uRight[f1 * cap + i] >= 0.0f ? 2 : 0)) : (uint8_t)1;
-        flag2[i] = in ? (uint8_t)((mpFlags2[(long long)pair * cap + i] & 1) | (uRight && uRight[f2 * cap + i] >= 0.0f ? 2 : 0)) : (uint8_t)1;
+        // (an index at or above the frame's count names no feature: it reads as "holds a MapPoint", which skips a key entry and drops a candidate)
+        flag1[i] = i < N1 ? (uint8_t)((mpFlags1[(long long)pair * cap + i] & 1) | (uRight && uRight[f1 * cap + i] >= 0.0f ? 2 : 0)) : (uint8_t)1;
+        flag2[i] = i < N2 ? (uint8_t)((mpFlags2[(long long)pair * cap + i] & 1) | (uRight && uRight[f2 * cap + i] >= 0.0f ? 2 : 0)) : (uint8_t)1;
         F2 pt = {0.0f, 0.0f};
         int o = 0;
         if (i < N2) { pt.x = kp2[i].x; pt.y = kp2[i].y; o = min(max(kp2[i].octave, 0), p.nlevels - 1); }
@@ -201,7 +202,8 @@ __global__ __launch_bounds__(kThreads) void k_search_triangulation(const uint32_
 void launchSearchTriangulation(hipStream_t st, const uint32_t* featNodes, const uint32_t* featIdx, const int* nFeat, const uint8_t* mpFlags1,
                                const uint8_t* mpFlags2, const Keypoint* kps, const float* uRight, const uint8_t* desc, const int* nOut,
                                const float* f12, const float* epipole, const TriMatchParams& p, bool stage, int* matches12, int* pairs,
-                               int* nMatches, int nPairs) {
+                               int* nMatches, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     if (stage)
         hipLaunchKernelGGL(k_search_triangulation<true>, dim3(nPairs), dim3(kThreads), triMatchLdsBytes(p.capacity, true), st, featNodes, featIdx,
                            nFeat, mpFlags1, mpFlags2, kps, uRight, desc, nOut, f12, epipole, p, matches12, pairs, nMatches);

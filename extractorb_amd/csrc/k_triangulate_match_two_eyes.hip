@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_camera_kb8_unproject.hpp"
 #include "k_lds_vec.hpp"
 #include "k_match_helpers.hpp"
@@ -119,15 +120,15 @@ __device__ __forceinline__ void triTwoEyesStage(int tid, const float* T1, const 
 }
 
 // before the first barrier: slot s = e * capA + i of the per-keypoint tables (flags, the empty match table, keyframe 2's ray); n2 = keyframe
-// 2's keypoints in eye e
+// 2's keypoints in eye e.  An index at or above the eye's count names no feature: a candidate with one reads as "holds a MapPoint" and is
+// dropped (keyframe 1's side of the rule is the kernel's, behind this call: the signature is the host check's)
 __device__ __forceinline__ void triTwoEyesLoadSlot(int s, const TriTwoEyesTables& T, int capA, int cap, int pair, int n2,
                                                    const uint8_t* __restrict__ mpFlags1, const uint8_t* __restrict__ mpFlags2,
                                                    const Keypoint* __restrict__ kp2, const TriMatchTwoEyesParams& p) {
     const int e = s >= capA, i = s - e * capA;
-    const bool in = i < cap;
     T.m12()[s] = -1; T.binOf()[s] = 255;
-    T.flag1()[s] = in ? (uint8_t)(mpFlags1[(2LL * pair + e) * cap + i] & 1) : (uint8_t)1;
-    T.flag2()[s] = in ? (uint8_t)(mpFlags2[(2LL * pair + e) * cap + i] & 1) : (uint8_t)1;
+    T.flag1()[s] = i < cap ? (uint8_t)(mpFlags1[(2LL * pair + e) * cap + i] & 1) : (uint8_t)1;
+    T.flag2()[s] = i < n2 ? (uint8_t)(mpFlags2[(2LL * pair + e) * cap + i] & 1) : (uint8_t)1;
     float rx = 0.0f, ry = 0.0f;
     if (i < n2 && !p.coarse) {                                                                  // pCamera2->unproject(kp2.pt), once per keypoint
         float k2[8];
@@ -294,7 +295,10 @@ __global__ __launch_bounds__(kTriThreads) void k_search_triangulation_two_eyes(
         for (int i = tid; i < M1[e]; i += kTriThreads) { T.segL()[e * capA + i] = gN1[i]; T.idx1()[e * capA + i] = (unsigned short)min(gI1[i], (uint32_t)(cap - 1)); }
         for (int i = tid; i < M2[e]; i += kTriThreads) { T.node2()[e * capA + i] = gN2[i]; T.idx2()[e * capA + i] = (unsigned short)min(gI2[i], (uint32_t)(cap - 1)); }
     }
-    for (int s = tid; s < 2 * capA; s += kTriThreads) triTwoEyesLoadSlot(s, T, capA, cap, pair, N2[s >= capA], mpFlags1, mpFlags2, kp2, p);
+    for (int s = tid; s < 2 * capA; s += kTriThreads) {
+        triTwoEyesLoadSlot(s, T, capA, cap, pair, N2[s >= capA], mpFlags1, mpFlags2, kp2, p);
+        if (s - (s >= capA) * capA >= N1[s >= capA]) T.flag1()[s] = 1;      // a key entry whose index names no feature is skipped before it searches or votes
+    }
     if constexpr (STAGE) {
 #pragma unroll
         for (int e = 0; e < 2; e++)
@@ -372,12 +376,13 @@ __global__ __launch_bounds__(256) void k_kb8_triangulate(const float* __restrict
 
 void launchSearchTriangulationTwoEyes(hipStream_t st, const uint32_t* featNodes, const uint32_t* featIdx, const int* nFeat, const uint8_t* mpFlags1,
                                       const uint8_t* mpFlags2, const float* poses, const Keypoint* kps, const uint8_t* desc, const int* nOut,
-                                      const TriMatchTwoEyesParams& params, bool stage, int* matches12, int* pairs, int* nMatches, int nPairs) {
+                                      const TriMatchTwoEyesParams& params, bool stage, int* matches12, int* pairs, int* nMatches, int nPairs, LdsPolluter pollute) {
     TriMatchTwoEyesParams p = params;
     p.countStats = g_triTwoEyesStatsOn ? 1 : 0;
     void* stats = nullptr;
     if (p.countStats && hipGetSymbolAddress(&stats, HIP_SYMBOL(g_triTwoEyesStats)) == hipSuccess) (void)hipMemsetAsync(stats, 0, sizeof(int) * 2, st);
     const size_t lds = triMatchTwoEyesLdsBytes(p.capacity, stage) - 1024;
+    pollute(st);
     if (stage)
         hipLaunchKernelGGL(k_search_triangulation_two_eyes<true>, dim3(nPairs), dim3(kTriThreads), lds, st, featNodes, featIdx, nFeat, mpFlags1,
                            mpFlags2, poses, kps, desc, nOut, p, matches12, pairs, nMatches);
@@ -386,14 +391,16 @@ void launchSearchTriangulationTwoEyes(hipStream_t st, const uint32_t* featNodes,
                            mpFlags2, poses, kps, desc, nOut, p, matches12, pairs, nMatches);
 }
 
-void launchKb8Unproject(hipStream_t st, const float* uv, const float* cam8, int n, float* rays) {
+void launchKb8Unproject(hipStream_t st, const float* uv, const float* cam8, int n, float* rays, LdsPolluter pollute) {
     Kb8UnprojectParams p;
     for (int i = 0; i < 8; i++) p.k[i] = cam8[i];
     p.n = n;
+    pollute(st);
     hipLaunchKernelGGL(k_kb8_unproject, dim3((n + 255) / 256), dim3(256), 0, st, uv, p, rays);
 }
 
-void launchKb8Triangulate(hipStream_t st, const float* kp1, const float* kp2, const Kb8TriangulateParams& p, float* z, float* x3d) {
+void launchKb8Triangulate(hipStream_t st, const float* kp1, const float* kp2, const Kb8TriangulateParams& p, float* z, float* x3d, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_kb8_triangulate, dim3((p.n + 255) / 256), dim3(256), 0, st, kp1, kp2, p, z, x3d);
 }
 

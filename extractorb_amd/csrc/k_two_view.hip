@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbx_lds_pollute.hpp"
 #include "k_two_view.hpp"
 
 namespace orbx {
@@ -60,11 +61,14 @@ __global__ __launch_bounds__(kTvLanes) void k_two_view_decide(const Keypoint* __
 }
 
 void launchTwoView(hipStream_t st, const Keypoint* kps, const int* nOut, int* matches12, int* nMatches, const int* rnd, const TwoViewParams& q,
-                   const TvWork& w, void* result, float* p3d, uint8_t* tri, int nPairs) {
+                   const TvWork& w, void* result, float* p3d, uint8_t* tri, int nPairs, LdsPolluter pollute) {
+    pollute(st);
     hipLaunchKernelGGL(k_two_view_prepare, dim3((unsigned)nPairs), dim3(kTvLanes), 0, st, kps, nOut, matches12, q, w, (TwoViewResult*)result, p3d, tri);
     const dim3 hyps((unsigned)((long long)nPairs * 2 * q.iterations));
+    pollute(st);
     if (g_twoViewShape) hipLaunchKernelGGL(k_two_view_hypotheses<true>, hyps, dim3(kTvLanes), 0, st, kps, rnd, q, w);
     else hipLaunchKernelGGL(k_two_view_hypotheses<false>, hyps, dim3(kTvLanes), 0, st, kps, rnd, q, w);
+    pollute(st);
     hipLaunchKernelGGL(k_two_view_decide, dim3((unsigned)nPairs), dim3(kTvLanes), 0, st, kps, matches12, nMatches, q, w, (TwoViewResult*)result, p3d, tri);
 }
 

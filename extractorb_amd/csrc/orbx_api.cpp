@@ -212,7 +212,7 @@ int enqueueBatch(orbx_handle* h, int B, const uint8_t* d_imgs, int rows, int col
     if (int rc = uploadLapping(h, B, lap)) return rc;
     const CallState state{h->lastBlurForm, h->lastSplitLevel, h->blurOwed, h->profiling};
     const BatchPlan bp = planBatch(g, gp, lp, state, B, stages);
-    auto pollute = [&](hipStream_t st) { if (h->ldsPollute >= 0) launchLdsPollute(st, lp.numCUs, h->ldsPollute, h->d_sink); };
+    auto pollute = [&](hipStream_t st) { polluteLds(h, st); };
     auto blurTable = [&](hipStream_t st, int v, int blockRows, int f0, int Bn) {
         launchBlur(st, h->d_tiles + gp.blurItemOff[v], h->d_laneItem + gp.blurLaneOff[v], gp.nBlurLanes[v], blockRows, h->d_lv, h->d_pyr, h->d_blur, f0, Bn);
     };

@@ -42,7 +42,7 @@ int orbx_covisibility_device(orbx_handle* h, int mode, int n_points, const int* 
     a.result = d_result; a.wsRank = h->d_covisRank; a.wsByRank = h->d_covisByRank; a.wsDup = h->d_covisDup;
     {
         Prof pr(h, S_FRAME);
-        launchCovisibility(h->stream, a, p);
+        launchCovisibility(h->stream, a, p, ldsPolluter(h));
         g_covisLaunches[0]++;
         g_covisLaunches[1]++;
     }
@@ -72,7 +72,7 @@ int orbx_keyframe_redundancy_device(orbx_handle* h, int n_points, const int* d_o
     a.subjectN = d_subject_n; a.subjectKf = d_subject_kf; a.result = d_result; a.slotState = d_slot_state;
     {
         Prof pr(h, S_FRAME);
-        launchKeyFrameRedundancy(h->stream, a, p);
+        launchKeyFrameRedundancy(h->stream, a, p, ldsPolluter(h));
         g_covisLaunches[2]++;
     }
     return finishLaunch(h);

@@ -100,6 +100,8 @@ int orbx_debug_last_forms(const orbx_handle* h, int* pyramid_form, int* pyramid_
     return ORBX_OK;
 }
 
+int orbx_debug_lds_pollutions(const orbx_handle* h) { return h ? h->ldsPollutions : ORBX_ERR_BAD_ARGUMENT; }
+
 int orbx_debug_last_split_level(const orbx_handle* h) { return h && h->lastBlurForm == kBlurSplitByLevel ? h->lastSplitLevel : 0; }
 
 int orbx_debug_num_candidates(orbx_handle* h, int frame, int level, int* n) {

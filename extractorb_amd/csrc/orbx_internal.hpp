@@ -23,6 +23,7 @@
 #include "orbx_geometry.hpp"
 #include "orbx_batch_plan.hpp"
 #include "orbx_params.hpp"
+#include "orbx_lds_pollute.hpp"
 
 namespace orbx {
 // launch wrappers and LDS sizes, defined in the k_*.hip files (the parameter blocks they take: orbx_params.hpp)
@@ -31,31 +32,31 @@ void launchPyrFirst(hipStream_t, const uint8_t*, long long, long long, const Lev
 void launchResize(hipStream_t, const LevelGeom&, const LevelGeom&, int, int, const ResizeX*, const QuadRec*, const ResizeX*, const TileFoot*,
                   uint8_t*, int, int, bool, int, int);
 size_t bowMatchLdsBytes(int capacity, bool stageDesc);
-void launchSearchBow(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowMatchParams&, int*, int*, int);
+void launchSearchBow(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowMatchParams&, int*, int*, int, LdsPolluter);
 size_t bowTwoEyesLdsBytes(int capacity, bool stage);
-void launchSearchBowTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowTwoEyesParams&, bool, int*, int*, int);
+void launchSearchBowTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const BowTwoEyesParams&, bool, int*, int*, int, LdsPolluter);
 size_t triMatchLdsBytes(int capacity, bool stage);
-void launchSearchTriangulation(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const float*, const uint8_t*, const int*, const float*, const float*, const TriMatchParams&, bool, int*, int*, int*, int);
-void launchFuse(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const float*, const uint8_t*, const int*, const int*, const int*, const FuseParams&, int*, int*, uint8_t*, int*, int);
-void launchFuseTwoEyes(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const FuseTwoEyesParams&, int*, int*, uint8_t*, int*, int);
+void launchSearchTriangulation(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const Keypoint*, const float*, const uint8_t*, const int*, const float*, const float*, const TriMatchParams&, bool, int*, int*, int*, int, LdsPolluter);
+void launchFuse(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const float*, const uint8_t*, const int*, const int*, const int*, const FuseParams&, int*, int*, uint8_t*, int*, int, LdsPolluter);
+void launchFuseTwoEyes(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const FuseTwoEyesParams&, int*, int*, uint8_t*, int*, int, LdsPolluter);
 size_t triMatchTwoEyesLdsBytes(int capacity, bool stage);
-void launchSearchTriangulationTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const TriMatchTwoEyesParams&, bool, int*, int*, int*, int);
-void launchKb8Unproject(hipStream_t, const float*, const float*, int, float*);
-void launchKb8Triangulate(hipStream_t, const float*, const float*, const Kb8TriangulateParams&, float*, float*);
+void launchSearchTriangulationTwoEyes(hipStream_t, const uint32_t*, const uint32_t*, const int*, const uint8_t*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const TriMatchTwoEyesParams&, bool, int*, int*, int*, int, LdsPolluter);
+void launchKb8Unproject(hipStream_t, const float*, const float*, int, float*, LdsPolluter);
+void launchKb8Triangulate(hipStream_t, const float*, const float*, const Kb8TriangulateParams&, float*, float*, LdsPolluter);
 int stereoFisheyeTiles(int capacity);
-void launchStereoFisheye(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const StereoFisheyeParams&, int*, int*, float*, float*, int*, int*, int);
+void launchStereoFisheye(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const StereoFisheyeParams&, int*, int*, float*, float*, int*, int*, int, LdsPolluter);
 int newMapPointsTiles(int listCapacity);
-void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*, const Keypoint*, const Keypoint*, const float*, const float*, const int*, const NewMapPointsParams&, uint8_t*, float*, int*, uint8_t*, uint8_t*, int);
-void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const MapPointUpdateParams&);
-void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const int*, const TwoViewParams&, const TvWork&, void*, float*, uint8_t*, int);
-void launchSim3Solve(hipStream_t, const void*, const float*, const float*, const int*, const int*, const int*, const Sim3SolveParams&, const SsWork&, void*, uint8_t*, int, int);
-void launchPoseOptimization(hipStream_t, const void*, const Keypoint*, const int*, const float*, const int*, const float*, const PoseOptParams&, float*, uint8_t*, void*, int);
-void launchPlaceRecognition(hipStream_t, const PlaceArrays&, const PlaceParams&);
-void launchCovisibility(hipStream_t, const CovisArrays&, const CovisParams&);
-void launchKeyFrameRedundancy(hipStream_t, const CovisArrays&, const CovisParams&);
+void launchNewMapPoints(hipStream_t, bool, const int*, const int*, const float*, const Keypoint*, const Keypoint*, const float*, const float*, const int*, const NewMapPointsParams&, uint8_t*, float*, int*, uint8_t*, uint8_t*, int, LdsPolluter);
+void launchMapPointUpdate(hipStream_t, bool, const MapPointUpdateArrays&, const MapPointUpdateParams&, LdsPolluter);
+void launchTwoView(hipStream_t, const Keypoint*, const int*, int*, int*, const int*, const TwoViewParams&, const TvWork&, void*, float*, uint8_t*, int, LdsPolluter);
+void launchSim3Solve(hipStream_t, const void*, const float*, const float*, const int*, const int*, const int*, const Sim3SolveParams&, const SsWork&, void*, uint8_t*, int, int, LdsPolluter);
+void launchPoseOptimization(hipStream_t, const void*, const Keypoint*, const int*, const float*, const int*, const float*, const PoseOptParams&, float*, uint8_t*, void*, int, LdsPolluter);
+void launchPlaceRecognition(hipStream_t, const PlaceArrays&, const PlaceParams&, LdsPolluter);
+void launchCovisibility(hipStream_t, const CovisArrays&, const CovisParams&, LdsPolluter);
+void launchKeyFrameRedundancy(hipStream_t, const CovisArrays&, const CovisParams&, LdsPolluter);
 size_t sim3SettleLdsBytes(int capacity, int mpCapacity);
 size_t sim3RecordBytes();
-void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int);
+void launchSim3Search(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const uint8_t*, const Sim3SearchParams&, void*, int*, int*, int*, uint8_t*, int*, int, LdsPolluter);
 void launchLdsPollute(hipStream_t, int, int, unsigned*);
 void launchPyrCols(hipStream_t, const uint8_t*, long long, long long, int, const PyrColumn*, int, const ColLevels*, int, const ResizeX*, int, uint8_t*, int, int, bool, int, int, int);
 void launchBlur(hipStream_t, const BlurItem*, const unsigned short*, int, int, const LevelGeom*, const uint8_t*, uint8_t*, int, int);
@@ -70,35 +71,35 @@ void launchDescribe(hipStream_t, const DescLevels&, const uint8_t*, const uint8_
 bool checkUmax(const int* umax16);
 void describeTables(unsigned* pb384, unsigned* plain256);
 hipError_t runPackedSelfTest(hipStream_t, unsigned*, unsigned*);
-void launchFrameFinish(hipStream_t, const Keypoint*, const int*, const FrameFinishParams&, Keypoint*, int*, int*, int*, int);
+void launchFrameFinish(hipStream_t, const Keypoint*, const int*, const FrameFinishParams&, Keypoint*, int*, int*, int*, int, LdsPolluter);
 void launchStereo(hipStream_t, const LevelGeom*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const StereoParams&,
-                  int, int*, unsigned short*, float*, float*, int*, int*, int);
+                  int, int*, unsigned short*, float*, float*, int*, int*, int, LdsPolluter);
 size_t initMatchLdsBytes(int capacity, int slotCapacity);
 int initMatchSlotCapacity(int capacity);
 void launchSearchInit(hipStream_t, const Keypoint*, const uint8_t*, const int*, const int*, const int*, const InitMatchParams&,
-                      float*, int*, int*, int);
+                      float*, int*, int*, int, LdsPolluter);
 size_t projSearchLdsBytes(int capacity, int queryCapacity, bool topList);
 void launchProjectLast(hipStream_t, const Keypoint*, const Keypoint*, const int*, const uint8_t*, const float*, const float*, const ProjectParams&,
-                       ProjQuery*, int);
+                       ProjQuery*, int, LdsPolluter);
 void launchSearchProj(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
-                      const int*, const float*, uint8_t*, const ProjSearchParams&, int*, int*, int);
-void launchFrustum(hipStream_t, const float*, const float*, const float*, const uint8_t*, const float*, const int*, const uint8_t*, const float*, const FrustumParams&, ProjQuery*, uint8_t*, int*, int*, TrackRecord*, int*, int);
+                      const int*, const float*, uint8_t*, const ProjSearchParams&, int*, int*, int, LdsPolluter);
+void launchFrustum(hipStream_t, const float*, const float*, const float*, const uint8_t*, const float*, const int*, const uint8_t*, const float*, const FrustumParams&, ProjQuery*, uint8_t*, int*, int*, TrackRecord*, int*, int, LdsPolluter);
 int frustumTwoEyesGroups(int mpCapacity);
 void launchFrustumTwoEyes(hipStream_t, const float*, const float*, const float*, const uint8_t*, const int*, const uint8_t*, const float*, const float*,
-                          const FrustumTwoEyesParams&, int*, ProjQuery*, uint8_t*, int*, int*, int*, TrackRecord*, int*, int);
+                          const FrustumTwoEyesParams&, int*, ProjQuery*, uint8_t*, int*, int*, int*, TrackRecord*, int*, int, LdsPolluter);
 size_t twoEyesSearchLdsBytes(int capacity, int queryCapacity);
 void launchSearchProjTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const int*, const Keypoint*, const uint8_t*, const int*, const int*,
-                             const int*, const int*, const int*, uint8_t*, const TwoEyesSearchParams&, int*, int*, int);
+                             const int*, const int*, const int*, uint8_t*, const TwoEyesSearchParams&, int*, int*, int, LdsPolluter);
 size_t lastTwoEyesLdsBytes(int capacity);
-void launchKb8Project(hipStream_t, const float*, const float*, int, float*);
+void launchKb8Project(hipStream_t, const float*, const float*, int, float*, LdsPolluter);
 void launchProjectLastTwoEyes(hipStream_t, const Keypoint*, const int*, const uint8_t*, const float*, const float*, const ProjectTwoEyesParams&,
-                              ProjQuery*, int);
+                              ProjQuery*, int, LdsPolluter);
 void launchSearchLastTwoEyes(hipStream_t, const ProjQuery*, const uint8_t*, const Keypoint*, const uint8_t*, const int*, const int*, const int*,
-                             uint8_t*, const LastTwoEyesSearchParams&, int*, int*, int);
+                             uint8_t*, const LastTwoEyesSearchParams&, int*, int*, int, LdsPolluter);
 void launchBow(hipStream_t, const VocabDevice&, const uint8_t*, const int*, int, int, uint32_t*, double*, uint32_t*, uint32_t*, double*, int*,
-               uint32_t*, uint32_t*, int*, int);
-void launchStereoFromRgbd(hipStream_t, const Keypoint*, const Keypoint*, const int*, const uint8_t*, const RgbdParams&, float*, float*, int);
-void launchGray(hipStream_t, const uint8_t*, uint8_t*, const GrayParams&, int);
+               uint32_t*, uint32_t*, int*, int, LdsPolluter);
+void launchStereoFromRgbd(hipStream_t, const Keypoint*, const Keypoint*, const int*, const uint8_t*, const RgbdParams&, float*, float*, int, LdsPolluter);
+void launchGray(hipStream_t, const uint8_t*, uint8_t*, const GrayParams&, int, LdsPolluter);
 void launchClockProbe(hipStream_t, unsigned long long*, int, int, unsigned);
 void launchCopyOut(hipStream_t, const void*, void*, size_t, int);
 }  // namespace orbx
@@ -211,6 +212,7 @@ struct orbx_handle {
     int pendingB = 0;            // frames of the batch begun with orbx_extract_batch_begin and not yet ended
     bool pendingLevels = false;
     int ldsPollute = -1;               // test aid "lds_pollute" (orbx_debug_set_option): every CU's LDS is filled with the byte in front of every kernel
+    int ldsPollutions = 0;             // pollution launches since orbx_create (orbx_debug_lds_pollutions)
     std::string policy;                // the launch-policy switches as read at orbx_create (orbx_debug_policy)
     // the internal stream and the events of the two-half overlap (enqueueBatch)
     hipStream_t aux = nullptr;
@@ -323,6 +325,11 @@ struct Prof {
         }
     }
 };
+
+// The test aid "lds_pollute" of a handle: what a launch* function takes as its last parameter, and the one statement in front of a kernel
+// that a host file launches itself.  Nothing is enqueued unless h->ldsPollute >= 0.
+inline LdsPolluter ldsPolluter(orbx_handle* h) { return LdsPolluter{h->ldsPollute >= 0 ? &launchLdsPollute : nullptr, h->launch.numCUs, h->ldsPollute, h->d_sink, &h->ldsPollutions}; }
+inline void polluteLds(orbx_handle* h, hipStream_t st) { ldsPolluter(h)(st); }
 
 // makeFrameGeom says why it refuses an image size; the code is read off that sentence
 inline int geometryRefusalCode(const std::string& why) {

@@ -36,7 +36,7 @@ int orbx_create_new_map_points_device(orbx_handle* h, int n_pairs, int kf1_first
     {
         Prof pr(h, S_FRAME);
         launchNewMapPoints(h->stream, false, d_pairs, d_n_matches, d_poses, (const Keypoint*)d_kps_un, (const Keypoint*)d_kps, d_u_right, d_depth,
-                           d_n_out, p, d_exit, d_x3d, d_n_new, d_mark1, d_mark2, n_pairs);
+                           d_n_out, p, d_exit, d_x3d, d_n_new, d_mark1, d_mark2, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -60,7 +60,7 @@ int orbx_update_map_points_device(orbx_handle* h, int n_points, const int* d_obs
                                  d_mp_desc, d_mp_normal, d_mp_dist, d_best, d_best_median, d_status};
     {
         Prof pr(h, S_FRAME);
-        launchMapPointUpdate(h->stream, false, a, p);
+        launchMapPointUpdate(h->stream, false, a, p, ldsPolluter(h));
     }
     return finishLaunch(h);
 }

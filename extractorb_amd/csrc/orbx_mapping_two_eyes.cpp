@@ -47,7 +47,7 @@ int orbx_fuse_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first, int kf_
         if (eyes == 3) HIP_TRY(h, hipMemsetAsync(d_n_fused, 0, sizeof(int) * 2 * (size_t)n_pairs, h->stream));
         else HIP_TRY(h, hipMemset2DAsync(d_n_fused + (eyes - 1), 2 * sizeof(int), 0, sizeof(int), (size_t)n_pairs, h->stream));
         launchFuseTwoEyes(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps, d_desc,
-                          d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs);
+                          d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -81,7 +81,7 @@ int orbx_search_for_triangulation_two_eyes_device(orbx_handle* h, int n_pairs, i
     {
         Prof pr(h, S_FRAME);
         launchSearchTriangulationTwoEyes(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, d_poses, (const Keypoint*)d_kps,
-                                         d_desc, d_n_out, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs);
+                                         d_desc, d_n_out, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -94,7 +94,7 @@ int orbx_kb8_unproject_device(orbx_handle* h, int n, const float* d_uv, const or
     fillKb8(k, *cam);
     {
         Prof pr(h, S_FRAME);
-        launchKb8Unproject(h->stream, d_uv, k, n, d_rays);
+        launchKb8Unproject(h->stream, d_uv, k, n, d_rays, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -114,7 +114,7 @@ int orbx_kb8_triangulate_device(orbx_handle* h, int n, const float* d_kp1, const
     p.sigma1 = sigma1; p.sigma2 = sigma2; p.n = n;
     {
         Prof pr(h, S_FRAME);
-        launchKb8Triangulate(h->stream, d_kp1, d_kp2, p, d_z, d_x3d);
+        launchKb8Triangulate(h->stream, d_kp1, d_kp2, p, d_z, d_x3d, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -144,7 +144,7 @@ int orbx_stereo_fisheye_match_device(orbx_handle* h, int n_rigs, int rig_first, 
     {
         Prof pr(h, S_FRAME);
         launchStereoFisheye(h->stream, (const Keypoint*)d_kps, d_desc, d_n_out, d_mono_out, p, d_left_to_right, d_right_to_left, d_depth, d_x3d,
-                            d_n_matches, d_n_desc_matches, n_rigs);
+                            d_n_matches, d_n_desc_matches, n_rigs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -176,7 +176,7 @@ int orbx_create_new_map_points_two_eyes_device(orbx_handle* h, int n_pairs, int 
     {
         Prof pr(h, S_FRAME);
         launchNewMapPoints(h->stream, true, d_pairs, d_n_matches, d_poses, (const Keypoint*)d_kps, nullptr, nullptr, nullptr, d_n_out, p, d_exit,
-                           d_x3d, d_n_new, d_mark1, d_mark2, n_pairs);
+                           d_x3d, d_n_new, d_mark1, d_mark2, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -203,7 +203,7 @@ int orbx_update_map_points_two_eyes_device(orbx_handle* h, int n_points, const i
                                  d_mp_desc, d_mp_normal, d_mp_dist, d_best, d_best_median, d_status};
     {
         Prof pr(h, S_FRAME);
-        launchMapPointUpdate(h->stream, true, a, p);
+        launchMapPointUpdate(h->stream, true, a, p, ldsPolluter(h));
     }
     return finishLaunch(h);
 }

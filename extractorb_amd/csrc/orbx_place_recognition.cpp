@@ -43,7 +43,7 @@ int orbx_detect_candidates_device(orbx_handle* h, const orbx_vocabulary* v, int 
                         h->d_placeWords, h->d_placeFirst, h->d_placeScore};
     {
         Prof pr(h, S_FRAME);
-        launchPlaceRecognition(h->stream, a, p);
+        launchPlaceRecognition(h->stream, a, p, ldsPolluter(h));
         if (n_db > 0) g_placeLaunches[0]++;
         g_placeLaunches[1]++;
     }

@@ -24,7 +24,7 @@ int orbx_optimize_pose_device(orbx_handle* h, int n_problems, int frame_first, i
     const PoseOptParams p{capacity, eyes, n_map_points, h->nlevels, frame_first, frame_step};
     {
         Prof pr(h, S_FRAME);
-        launchPoseOptimization(h->stream, d_problems, (const Keypoint*)d_kps, d_n_out, d_u_right, d_matches, d_mp_world, p, d_poses, d_outlier, d_result, n_problems);
+        launchPoseOptimization(h->stream, d_problems, (const Keypoint*)d_kps, d_n_out, d_u_right, d_matches, d_mp_world, p, d_poses, d_outlier, d_result, n_problems, ldsPolluter(h));
         g_poseOptLaunches++;
     }
     return finishLaunch(h);

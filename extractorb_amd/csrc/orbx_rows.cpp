@@ -43,7 +43,7 @@ int stereoEnqueue(orbx_handle* h, int n_pairs, const Keypoint* d_kps, const uint
     {
         Prof p(h, S_STEREO);
         launchStereo(h->stream, h->d_lv, h->d_pyr, d_kps, d_desc, d_n, sp, rows, h->d_rowOff, h->d_rowList, d_u, d_d, h->d_sadDist,
-                     d_nm, n_pairs);
+                     d_nm, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -141,7 +141,7 @@ int orbx_stereo_from_rgbd_device(orbx_handle* h, int n_frames, const orbx_keypoi
     p.scale = p.isU16 || std::fabs(depth_map_factor - 1.0f) > 1e-5f;      // Tracking.cc:1003
     p.stride = depth_stride_bytes; p.frame = depth_frame_stride_bytes; p.factor = depth_map_factor; p.mbf = mbf;
     launchStereoFromRgbd(h->stream, (const Keypoint*)d_kps, (const Keypoint*)d_kps_un, d_n_out, (const uint8_t*)d_depth, p, d_u_right,
-                         d_depth_out, n_frames);
+                         d_depth_out, n_frames, ldsPolluter(h));
     return finishLaunch(h);
 }
 
@@ -157,7 +157,7 @@ int orbx_gray_from_color_device(orbx_handle* h, int n_frames, const uint8_t* d_s
     p.rows = rows; p.cols = cols; p.channels = channels; p.redFirst = red_first != 0;
     p.srcStride = src_stride; p.srcFrame = src_frame_stride; p.dstStride = gray_stride; p.dstFrame = gray_frame_stride;
     p.aligned = (((uintptr_t)d_src | (uintptr_t)src_stride | (uintptr_t)src_frame_stride) & 3) == 0;
-    launchGray(h->stream, d_src, d_gray, p, n_frames);
+    launchGray(h->stream, d_src, d_gray, p, n_frames, ldsPolluter(h));
     return finishLaunch(h);
 }
 
@@ -175,7 +175,7 @@ static int frameFinish(orbx_handle* h, int n_frames, const orbx_keypoint* d_kps,
     p.capacity = capacity; p.rawGrid = rawGrid;
     {
         Prof pr(h, S_FRAME);
-        launchFrameFinish(h->stream, (const Keypoint*)d_kps, d_n_out, p, (Keypoint*)d_kps_un, d_grid_off, d_grid_idx, d_n_inside, n_frames);
+        launchFrameFinish(h->stream, (const Keypoint*)d_kps, d_n_out, p, (Keypoint*)d_kps_un, d_grid_off, d_grid_idx, d_n_inside, n_frames, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -211,7 +211,7 @@ int orbx_search_for_initialization_device(orbx_handle* h, int n_pairs, int frame
     {
         Prof pr(h, S_FRAME);
         launchSearchInit(h->stream, (const Keypoint*)d_kps_un, d_desc, d_n_out, d_grid_off, d_grid_idx, p, d_prev_matched, d_matches12,
-                         d_n_matches, n_pairs);
+                         d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -233,7 +233,7 @@ int orbx_project_last_frame_device(orbx_handle* h, int n_pairs, int last_first, 
     p.lastFirst = last_first; p.lastStep = last_step; p.curFirst = cur_first; p.curStep = cur_step;
     {
         Prof pr(h, S_FRAME);
-        launchProjectLast(h->stream, (const Keypoint*)d_kps, (const Keypoint*)d_kps_un, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs);
+        launchProjectLast(h->stream, (const Keypoint*)d_kps, (const Keypoint*)d_kps_un, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -261,7 +261,7 @@ int orbx_search_by_projection_device(orbx_handle* h, int n_pairs, int cur_first,
     {
         Prof pr(h, S_FRAME);
         launchSearchProj(h->stream, (const ProjQuery*)d_queries, d_query_desc, d_n_queries, (const Keypoint*)d_kps_un, d_desc, d_n_out, d_grid_off,
-                         d_grid_idx, d_u_right, d_occupied, p, d_matches, d_n_matches, n_pairs);
+                         d_grid_idx, d_u_right, d_occupied, p, d_matches, d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -289,7 +289,7 @@ int orbx_search_by_projection_two_eyes_device(orbx_handle* h, int n_pairs, int p
     {
         Prof pr(h, S_FRAME);
         launchSearchProjTwoEyes(h->stream, (const ProjQuery*)d_queries, d_query_desc, d_n_queries, (const Keypoint*)d_kps, d_desc, d_n_out,
-                                d_grid_off, d_grid_idx, d_left_to_right, d_right_to_left, d_occupied, p, d_matches, d_n_matches, n_pairs);
+                                d_grid_off, d_grid_idx, d_left_to_right, d_right_to_left, d_occupied, p, d_matches, d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -302,7 +302,7 @@ int orbx_kb8_project_device(orbx_handle* h, int n, const float* d_xyz, const orb
     fillKb8(k, *cam);
     {
         Prof pr(h, S_FRAME);
-        launchKb8Project(h->stream, d_xyz, k, n, d_uv);
+        launchKb8Project(h->stream, d_xyz, k, n, d_uv, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -326,7 +326,7 @@ int orbx_project_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int las
     p.lastFirst = last_first; p.lastStep = last_step; p.curFirst = cur_first; p.curStep = cur_step;
     {
         Prof pr(h, S_FRAME);
-        launchProjectLastTwoEyes(h->stream, (const Keypoint*)d_kps, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs);
+        launchProjectLastTwoEyes(h->stream, (const Keypoint*)d_kps, d_n_out, d_mp_flags, d_world, d_poses, p, (ProjQuery*)d_queries, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -349,7 +349,7 @@ int orbx_search_last_frame_two_eyes_device(orbx_handle* h, int n_pairs, int cur_
     {
         Prof pr(h, S_FRAME);
         launchSearchLastTwoEyes(h->stream, (const ProjQuery*)d_queries, d_query_desc, (const Keypoint*)d_kps, d_desc, d_n_out, d_grid_off, d_grid_idx,
-                                d_occupied, p, d_matches, d_n_matches, n_pairs);
+                                d_occupied, p, d_matches, d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -487,7 +487,7 @@ int orbx_compute_bow_device(orbx_handle* h, const orbx_vocabulary* v, int n_fram
     {
         Prof pr(h, S_FRAME);
         launchBow(h->stream, V, d_desc, d_n_out, capacity, levels_up, h->d_bowWord, h->d_bowWeight, h->d_bowNode, d_word_ids, d_word_weights, d_n_words,
-                  d_feat_nodes, d_feat_idx, d_n_feat, n_frames);
+                  d_feat_nodes, d_feat_idx, d_n_feat, n_frames, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -506,7 +506,7 @@ static int searchByBow(orbx_handle* h, int n_pairs, int kf_first, int kf_step, i
     {
         Prof pr(h, S_FRAME);
         launchSearchBow(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, d_cur_mp_flags, (const Keypoint*)d_kps, d_desc, d_n_out, p, d_matches,
-                        d_n_matches, n_pairs);
+                        d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -544,7 +544,7 @@ int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first
     {
         Prof pr(h, S_FRAME);
         launchSearchBowTwoEyes(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf_mp_flags, (const Keypoint*)d_kps, d_desc, d_n_out, p, stage,
-                               d_matches, d_n_matches, n_pairs);
+                               d_matches, d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -574,7 +574,7 @@ int orbx_search_for_triangulation_device(orbx_handle* h, int n_pairs, int kf1_fi
     {
         Prof pr(h, S_FRAME);
         launchSearchTriangulation(h->stream, d_feat_nodes, d_feat_idx, d_n_feat, d_kf1_mp_flags, d_kf2_mp_flags, (const Keypoint*)d_kps_un, d_u_right,
-                                  d_desc, d_n_out, d_f12, d_epipole, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs);
+                                  d_desc, d_n_out, d_f12, d_epipole, p, stage, d_matches12, d_pairs, d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -607,7 +607,7 @@ int orbx_fuse_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int
         Prof pr(h, S_FRAME);
         HIP_TRY(h, hipMemsetAsync(d_n_fused, 0, sizeof(int) * (size_t)n_pairs, h->stream));
         launchFuse(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps_un, d_u_right, d_desc,
-                   d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs);
+                   d_n_out, d_grid_off, d_grid_idx, p, d_best_idx, d_best_dist, d_exit, d_n_fused, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -653,7 +653,7 @@ int orbx_search_by_projection_sim3_device(orbx_handle* h, int n_pairs, int kf_fi
         Prof pr(h, S_FRAME);
         launchSim3Search(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_poses, (const Keypoint*)d_kps_un, d_desc,
                          d_n_out, d_grid_off, d_grid_idx, d_occupied, p, h->d_sim3Rec, d_matches, d_match_idx, d_match_dist, d_exit,
-                         d_n_matches, n_pairs);
+                         d_n_matches, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -686,7 +686,7 @@ int orbx_frustum_requests_device(orbx_handle* h, int n_pairs, int cur_first, int
     {
         Prof pr(h, S_FRAME);
         launchFrustum(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_mp_angle, d_n_mp, d_mp_flags, d_poses, p, (ProjQuery*)d_queries,
-                      d_query_desc, d_query_src, d_n_queries, (TrackRecord*)d_track, d_n_in_view, n_pairs);
+                      d_query_desc, d_query_src, d_n_queries, (TrackRecord*)d_track, d_n_in_view, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }
@@ -728,7 +728,7 @@ int orbx_frustum_requests_two_eyes_device(orbx_handle* h, int n_pairs, int cur_f
         Prof pr(h, S_FRAME);
         launchFrustumTwoEyes(h->stream, d_mp_world, d_mp_normal, d_mp_dist, d_mp_desc, d_n_mp, d_mp_flags, d_mp_prev_depth, d_poses, p,
                              h->d_frustumCounts, (ProjQuery*)d_queries, d_query_desc, d_query_src, d_n_queries, d_n_wanted, (TrackRecord*)d_track,
-                             d_n_in_view, n_pairs);
+                             d_n_in_view, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }

@@ -54,7 +54,7 @@ int orbx_sim3_solve_device(orbx_handle* h, int n_problems, const orbx_sim3_probl
     const Sim3SolveParams p{capacity, max_iterations, min_inliers, h->nlevels};
     {
         Prof pr(h, S_FRAME);
-        launchSim3Solve(h->stream, d_problems, d_x1w, d_x2w, d_octave1, d_octave2, d_rand, p, w, d_result, d_inliers, n_problems, g_sim3SolveSteps);
+        launchSim3Solve(h->stream, d_problems, d_x1w, d_x2w, d_octave1, d_octave2, d_rand, p, w, d_result, d_inliers, n_problems, g_sim3SolveSteps, ldsPolluter(h));
     }
     return finishLaunch(h);
 }

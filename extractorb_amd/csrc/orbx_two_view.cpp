@@ -42,7 +42,7 @@ int orbx_reconstruct_two_views_device(orbx_handle* h, int n_pairs, int frame1_fi
     {
         Prof pr(h, S_FRAME);
         launchTwoView(h->stream, (const Keypoint*)d_kps_un, d_n_out, d_matches12, d_n_matches, d_rand, p, h->twoViewWork, d_result, d_p3d,
-                      d_triangulated, n_pairs);
+                      d_triangulated, n_pairs, ldsPolluter(h));
     }
     return finishLaunch(h);
 }

@@ -177,6 +177,8 @@ def load_library():
     L.orbx_fetch_pyramid.argtypes = [vp, C.c_int, C.POINTER(vp), vp, vp, vp, vp]
     L.orbx_debug_last_forms.argtypes = [vp, ip, ip, ip]
     L.orbx_debug_last_split_level.argtypes = [vp]
+    if hasattr(L, "orbx_debug_lds_pollutions"):      # (an earlier build loaded through ORBX_LIBRARY for an A/B has no such export)
+        L.orbx_debug_lds_pollutions.argtypes = [vp]
     L.orbx_debug_set_option.argtypes = [C.c_char_p, C.c_int]
     if hasattr(L, "orbx_debug_describe_tables"):      # (an earlier build loaded through ORBX_LIBRARY for an A/B has no such export)
         L.orbx_debug_describe_tables.argtypes = [vp, vp]
@@ -1112,6 +1114,12 @@ class ORBextractor:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self._L.orbx_debug_last_forms(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def lds_pollutions(self):
+        """Launches of the LDS polluter on this handle since it was made (include/orbx.h: orbx_debug_lds_pollutions)."""
+        n = self._L.orbx_debug_lds_pollutions(self._h)
+        self._check(min(n, 0))
+        return n
 
     def blurred_level_exists(self, level):
         """whether the last call left a blurred image of `level` (it did not where the blur ran per keypoint inside k_describe)"""

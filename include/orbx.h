@@ -841,6 +841,8 @@ int orbx_keyframe_redundancy_device(orbx_handle* h, int n_points, const int* d_o
  *   nn_ratio = mfNNratio, th_low = ORBmatcher::TH_LOW (50), check_orientation = mbCheckOrientation
  *   d_matches[p*capacity + i]          : out, the keyframe keypoint whose MapPoint keypoint i of the frame receives, -1 = none
  *   d_n_matches[p]                     : out, the return value
+ * A FeatureVector index >= d_n_out of its frame names no feature (here and in orbx_search_by_bow_keyframes_device): a keyframe entry with
+ * one is skipped before it searches or votes in the rotation histogram, a candidate with one is dropped.
  * Asynchronous on the handle's stream.  Errors: ORBX_ERR_UNSUPPORTED if the tables (22 bytes per slot of the capacity rounded up to 16, + 64) do not fit a workgroup's LDS
  * (with 64 more bytes per slot the descriptors are staged in LDS too; without them they are read from L2). */
 int orbx_search_by_bow_device(orbx_handle* h, int n_pairs, int kf_first, int kf_step, int cur_first, int cur_step,
@@ -881,6 +883,8 @@ int orbx_search_by_bow_keyframes_device(orbx_handle* h, int n_pairs, int kf1_fir
  * unless the LEFT best is within th_low; then the left keypoint is written if it passes the ratio test and, whether or not it did, the
  * right best if it is within th_low (its ratio test is disabled, :403).  One keyframe feature can so hand its MapPoint to two keypoints,
  * and a node without an open left candidate never matches a right one.  The rotation histogram takes the pushes of both eyes.
+ * A FeatureVector index >= d_n_out of its eye names no feature: a keyframe entry with one is skipped before it searches or votes in the
+ * rotation histogram, a candidate with one is dropped.
  * Supported: the tables of a search live in LDS,
  *   40 * ((capacity + 15) & ~15) + 64 <= 163 328 bytes      (capacity <= 4080; orbx_max_keypoints() = 1302 of a 1200-feature extractor is inside)
  * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched.  While 104 * ((capacity + 15) & ~15) + 64 <= 163 328
@@ -924,7 +928,10 @@ int orbx_search_by_bow_two_eyes_device(orbx_handle* h, int n_pairs, int kf_first
  * the holder (:1057, :1080): of the passing candidates the smallest distance wins and of equal smallest distances the LAST in list order
  * (the opposite of SearchByBoW).  Rotation histogram and ComputeThreeMaxima as there (:1147-1157, :1174-1193).
  * The scale tables are the handle's (orbx_get_tables).  An octave outside [0, nlevels) is CLAMPED into the tables (the reference would
- * index past them).  Supported: the tables of a pair live in LDS,
+ * index past them).  d_n_feat[f] and d_n_out[f] are clamped into [0, capacity].  A FeatureVector index >= d_n_out of its frame (a stale
+ * count beside an older FeatureVector; orbx_compute_bow_device writes none) names no feature: a keyframe-1 entry with one is skipped
+ * before it searches or votes in the rotation histogram, a keyframe-2 candidate with one is dropped, and both launch forms answer alike.
+ * Supported: the tables of a pair live in LDS,
  *   28 * ((capacity + 15) & ~15) + 64 <= 163 328 bytes      (capacity <= 5824)
  * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched.  While 60 * ((capacity + 15) & ~15) + 64 <= 163 328
  * (capacity <= 2720; orbx_max_keypoints() of a 2000-feature extractor is inside) keyframe 2's descriptors are staged in LDS as well; above,
@@ -1113,6 +1120,8 @@ int orbx_kb8_triangulate_device(orbx_handle* h, int n, const float* d_kp1, const
  * geometric test is pCamera1->epipolarConstrain(pCamera2, kp1, kp2, R12, t12, mvLevelSigma2[kp1.octave], mvLevelSigma2[kp2.octave]) with the
  * cameras and (R12, t12) of the candidate's eye combination; of the passing candidates within th_low the smallest distance wins and of
  * equal distances the LAST in list order; vbMatched2 is never set.  An octave outside [0, nlevels) is CLAMPED into the table.
+ * A FeatureVector index >= d_n_out of its eye names no feature: a keyframe-1 entry with one is skipped before it searches or votes in the
+ * rotation histogram, a keyframe-2 candidate with one is dropped.
  * Supported: the tables of a pair live in LDS, capacity counted over both eyes,
  *   62 * ((capacity + 15) & ~15) + 1024 <= 163 328 bytes      (capacity <= 2608 per eye; 2 x 1302 of a 1200-feature extractor are inside)
  * a larger call returns ORBX_ERR_UNSUPPORTED before anything is launched.  While 126 * ((capacity + 15) & ~15) + 1024 <= 163 328
@@ -1613,6 +1622,10 @@ int orbx_debug_sim3_search_list_length(void);
 int orbx_debug_last_forms(const orbx_handle* h, int* pyramid_form, int* pyramid_cut_px, int* blur_form);
 /* the first level the last call blurred with k_blur when its blur form was 5; 0 otherwise */
 int orbx_debug_last_split_level(const orbx_handle* h);
+/* Launches of the LDS polluter (test aid "lds_pollute", below) on this handle since orbx_create: one in front of EVERY kernel a call enqueues,
+ * the second and later kernels of an entry included, so a test reads off the difference how many kernels an entry call launched behind a
+ * pollution.  0 for ever with the aid off.  NULL handle: ORBX_ERR_BAD_ARGUMENT. */
+int orbx_debug_lds_pollutions(const orbx_handle* h);
 
 /* Test aids.  They cannot be set from the environment: a test calls this BEFORE orbx_create and the handles created afterwards carry the
  * setting.  name = "poison" (byte every device allocation of orbx_create is filled with; -1 = off), "lds_pollute" (byte every CU's LDS is

@@ -127,6 +127,8 @@ def test_argtypes_match_the_header():
     assert declared["orbx_kb8_project_device"] == ["p", "i", "p", "p", "p"]
     assert declared["orbx_sim3_hamming_bound"] == ["i", "f"]
     assert declared["orbx_host_alloc"] == ["size"] and declared["orbx_abi_version"] == []
+    assert declared["orbx_debug_lds_pollutions"] == ["p"] and L.orbx_debug_lds_pollutions.argtypes == [ctypes.c_void_p]
+    assert L.orbx_debug_lds_pollutions(None) == -2
     assert declared["orbx_gray_from_color_device"] == ["p", "i", "p", "i", "i", "i", "i", "ptrdiff", "ptrdiff", "p", "ptrdiff", "ptrdiff"]
 
 

@@ -116,8 +116,9 @@ def test_oracle_search_by_bow_degenerate_inputs():
     assert n == 0 and (m == -1).all()
 
 
-def _run_gpu(pairs, nnratio, th_low, check, cap):
-    """pairs: list of synthetic_pair dicts; frames 2p = keyframe, 2p + 1 = current frame of pair p."""
+def _run_gpu(pairs, nnratio, th_low, check, cap, counts=None):
+    """pairs: list of synthetic_pair dicts; frames 2p = keyframe, 2p + 1 = current frame of pair p.  counts: d_n_out as the device is
+    handed it (a stale count beside arrays and a FeatureVector that hold more)."""
     import torch
     B = 2 * len(pairs)
     desc = np.zeros((B, cap, 32), np.uint8); kps = np.zeros((B, cap), X.KEYPOINT_DTYPE)
@@ -128,6 +129,8 @@ def _run_gpu(pairs, nnratio, th_low, check, cap):
             desc[f, :len(d)] = d; kps[f, :len(k)] = k; nout[f] = len(d)
             fn[f, :len(fv[0])] = fv[0]; fi[f, :len(fv[1])] = fv[1]; nfeat[f] = len(fv[0])
         flags[i, :len(p["flags"])] = p["flags"]
+    if counts is not None:
+        nout[:] = counts
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8) if a.dtype.fields else np.ascontiguousarray(a)).cuda()
     d_m = torch.full((len(pairs), cap), -7, dtype=torch.int32, device="cuda"); d_nm = torch.zeros(len(pairs), dtype=torch.int32, device="cuda")
     ex = X.ORBextractor(1000)
@@ -151,6 +154,41 @@ def test_gpu_search_by_bow_equals_oracle(case):
         assert int(nm[i]) == n, "pair %d" % i
         assert m[i, :len(want)].tolist() == want.tolist(), "pair %d" % i
         assert (m[i, len(want):] == -1).all()
+
+
+def _cut(p, nk, nf):
+    """the pair as the walk sees it when the counts say nk and nf: the first rows, and the FeatureVectors without the entries past them"""
+    kk, kf = p["fv_k"][1] < nk, p["fv_f"][1] < nf
+    return dict(dk=p["dk"][:nk], df=p["df"][:nf], kps_k=p["kps_k"][:nk], kps_f=p["kps_f"][:nf], flags=p["flags"][:nk],
+                fv_k=(p["fv_k"][0][kk], p["fv_k"][1][kk]), fv_f=(p["fv_f"][0][kf], p["fv_f"][1][kf]))
+
+
+def test_cut_pairs_differ_from_the_full_ones_where_the_phantoms_would_match():
+    rng = np.random.default_rng(77)
+    p = synthetic_pair(rng, 300, 400, 6)
+    c = _cut(p, 260, 340)
+    assert (p["fv_k"][1] >= 260).sum() > 20 and (p["fv_f"][1] >= 340).sum() > 30
+    n_full, m_full = O.search_by_bow(p["fv_k"], p["fv_f"], p["flags"], p["kps_k"], p["dk"], p["kps_f"], p["df"])
+    n_cut, m_cut = O.search_by_bow(c["fv_k"], c["fv_f"], c["flags"], c["kps_k"], c["dk"], c["kps_f"], c["df"])
+    assert n_cut > 50 and m_full[:340].tolist() != m_cut.tolist()      # features past the counts take part in the full search
+    bn, bm = brute(c, 0.7, 50, True)
+    assert bn == n_cut and bm.tolist() == m_cut.tolist()
+
+
+@pytest.mark.gpu
+def test_gpu_feature_vector_indices_at_or_above_the_count_name_no_feature():
+    """include/orbx.h: a FeatureVector index >= d_n_out of its frame names no feature.  The device is handed the full arrays and FeatureVectors
+    beside stale counts, under polluted LDS (the staged form would compare such a candidate through LDS nobody wrote); the oracle is handed
+    the pairs cut at the counts.  Exact."""
+    rng = np.random.default_rng(77)
+    full = [synthetic_pair(rng, 300 - 17 * i, 400 - 31 * i, 6) for i in range(2)]
+    cuts = [_cut(p, len(p["dk"]) - 40, len(p["df"]) - 60) for p in full]
+    X.debug_set_option("lds_pollute", 0xC3)
+    nm, m = _run_gpu(full, 0.7, 50, True, 512, counts=[n for c in cuts for n in (len(c["dk"]), len(c["df"]))])
+    for i, c in enumerate(cuts):
+        n, want = O.search_by_bow(c["fv_k"], c["fv_f"], c["flags"], c["kps_k"], c["dk"], c["kps_f"], c["df"], 0.7, 50, True)
+        assert n > 40 and int(nm[i]) == n, "pair %d" % i
+        assert m[i, :len(want)].tolist() == want.tolist() and (m[i, len(want):] == -1).all(), "pair %d" % i
 
 
 @pytest.mark.gpu

@@ -178,16 +178,16 @@ def brute(s, only_stereo=False, coarse=False, th_low=50, check_orientation=True)
         c2 = np.array(l2[node])
         ok2 = (b["mp"][c2] & 1) == 0
         if only_stereo:
-            ok2 &= b["ur"][c2] >= 0
+            ok2 &= b["ur"][c2] >= 0                      # (mvuRight >= 0 is the test: a NaN is not stereo)
         e = s["ep"][None] - p2[c2]
         near = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) < f32(100) * SF[b["kps"]["octave"][c2]]
         for i1 in l1[node]:
-            if a["mp"][i1] & 1 or (only_stereo and a["ur"][i1] < 0):
+            if a["mp"][i1] & 1 or (only_stereo and not a["ur"][i1] >= 0):
                 continue
             dist = POPCOUNT[a["desc"][i1][None] ^ b["desc"][c2]].sum(1)
             ok = ok2 & (dist <= th_low)
-            if a["ur"][i1] < 0:
-                ok &= ~(near & (b["ur"][c2] < 0))
+            if not a["ur"][i1] >= 0:
+                ok &= ~(near & ~(b["ur"][c2] >= 0))
             if not coarse:
                 ok &= np.array([bool(ok[j]) and epipolar_constrain(a["kps"]["x"][i1], a["kps"]["y"][i1], p2[i2, 0], p2[i2, 1], s["F"],
                                                                    SIG2[b["kps"]["octave"][i2]]) for j, i2 in enumerate(c2)], bool)
